@@ -14,7 +14,12 @@ Synthetic data (no dataset, no SD2 weights in the reference): seeded normal weig
 c_concat = [blocky right-half mask | 4 latent channels ~ N(0, 0.18215^2)], contexts ~ N(0,1) [77,1024].  The VAE and
 prompt encoder are outside the path (host PyTorch code) and outside the timed region.
 
-The printed JSON line also carries
+`--dump-outputs DIR` writes what the last timed step computed -- the sampled latents, DIR/samples.npy -- for an output-for-output
+comparison of two builds: weights, inputs and the eta = 1 noise (torch's default generators, seeded 4321 + rank) are the same
+for the same arguments.
+
+With --side-measurements the printed JSON line also carries (off by default: together they take far longer than the timed
+steps, and a plain run's wall time should be the model build plus (warmup + steps) samplings)
   roofline     : the dominant kernel family (implicit-GEMM conv/linear `gemm_conv_kernel`) timed live with HIP events on
                  its launch stream in one instrumented eager UNet step: achieved = algorithmic FLOPs / sum of durations;
   cpu_baseline : the CPU oracle (oracle/, fp32 torch, this box's host cores) on a bounded sample of the same workload.
@@ -331,7 +336,33 @@ def vae_timing(B, device):
     return out
 
 
-def train_bench(a, rank, world, device, model=None, steps=None):
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write {name: tensor} as DIR/<name>.npy in float32 (float64 tensors stay float64), at most
+    DUMP_BUDGET_BYTES in all.  An array larger than what is left of the budget is replaced by a fixed sample of its
+    flattened elements (seeded index draw, sorted), so that two runs with the same arguments write comparable files."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    written = {}
+    for name, t in arrays.items():
+        x = t.detach().float() if t.dtype != torch.float64 else t.detach()
+        room = max(0, left - 256)        # less the .npy header
+        sampled = x.numel() * x.element_size() > room
+        if sampled:
+            idx = torch.randperm(x.numel(), generator=torch.Generator().manual_seed(0))[:room // x.element_size()].sort().values
+            x = x.reshape(-1)[idx.to(x.device)]
+        arr = x.cpu().numpy()
+        path = os.path.join(dirname, name + ".npy")
+        np.save(path, arr)
+        left -= os.path.getsize(path)
+        written[name] = {"shape": list(arr.shape), "dtype": str(arr.dtype), "sampled_from": list(t.shape) if sampled else None}
+    return {"dir": os.path.abspath(dirname), "arrays": written}
+
+
+def train_bench(a, rank, world, device, model=None, steps=None, dump=None):
     """`--workload train` (not the metric; SURVEY 8f-2 / BASELINE configs[4]): one optimisation step of the prompt tokens
     through the frozen UNet at canvas 256x512 (latent 32x64), per-GPU batch 16: p_losses forward + HIP backward to the
     context + AdamW on the tokens (stand-in for `special_embeddings`, 73 x 1024), loss scale 2^14, data-parallel
@@ -449,6 +480,12 @@ def train_bench(a, rank, world, device, model=None, steps=None):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = tt.item()
     assert torch.isfinite(loss)
+    dumped = None
+    if dump is not None and rank == 0:     # what the last timed step hands its caller: the loss and the updated trainables
+        arrays = {"loss": loss.detach().reshape(1), "prompt_tokens": tokens}
+        if pose_mlp is not None:
+            arrays.update({"pose_mlp." + k: v for k, v in pose_mlp.state_dict().items()})
+        dumped = dump_outputs(dump, arrays)
     peak_gb = torch.cuda.max_memory_allocated(device) / 2 ** 30
     model.eval()
     with torch.no_grad():      # forward alone, same shapes (eager, like the training forward)
@@ -486,7 +523,7 @@ def train_bench(a, rank, world, device, model=None, steps=None):
                        "per_gpu_batch": Bt, "parallelism": f"dp{world} (all-reduce of the trainable token / pose-MLP gradients only)"},
             "forward_only_ms": fwd_ms, "final_loss": float(loss.detach()), "peak_memory_gib": peak_gb,
             "recompute_in_backward": bool(getattr(a, "recompute", False)), "hip_graph": graph is not None,
-            "loss_scale": scaler["scale"], "skipped_steps": scaler["skipped"]}
+            "loss_scale": scaler["scale"], "skipped_steps": scaler["skipped"], **({"dump_outputs": dumped} if dumped else {})}
 
 
 def host_cpu():
@@ -871,6 +908,9 @@ def _main():
     ap.add_argument("--workload", default="single", choices=["single", "mv5", "mv4", "train"],
                     help="single = configs[1] (the metric); mv5 / mv4 = multi-view config 4 on one GPU; train = training step "
                          "(configs[4]-like) -- neither is the metric")
+    ap.add_argument("--side-measurements", action="store_true",
+                    help="after the metric, also measure roofline / kernel table / traffic, sustained MFMA peak, shared-prefix sampling, "
+                         "UNet-step events, batch sweep, VAE, training and the CPU baseline (the --no-* flags below drop single ones)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 --pmc passes that measure roofline.traffic")
@@ -880,6 +920,9 @@ def _main():
     ap.add_argument("--train-graph", action="store_true", help="train workload: capture the whole step into one hipGraph")
     ap.add_argument("--recompute", action="store_true", help="train workload: recompute blocks in the backward (use_checkpoint)")
     ap.add_argument("--dump-kernels", default=None, help="write per-launch (shape, us, TFLOP/s) records as JSON lines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, <= 64 MB in all; rank 0): "
+                         "the sampled latents, or for --workload train the loss and the updated prompt tokens / pose MLP")
     ap.add_argument("--mv-shard", action="store_true",
                     help="mv5 workload in its configs[3] form: ONE canvas per rank (--gpus 4 = view_num - 1), per-block RCCL "
                          "all-gather of the reference halves + broadcast of the target half, captured in the hipGraph")
@@ -894,6 +937,8 @@ def _main():
     ap.add_argument("--task", default="nvs", choices=["nvs", "refill"],
                     help="train workload: nvs = BASELINE configs[4] as stated (NVSLDM, prompt tokens + pose MLP); refill = RefInpaintLDM tokens only")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # `python bench.py --gpus N` on its own: re-launch as N ranks (one per GPU) under torch.distributed.run, like the driver does
@@ -947,7 +992,7 @@ def _main():
     _STAGE[0] = "workload"
     if a.workload == "train":
         _STAGE[0] = "train workload"
-        res = train_bench(a, rank, world, device)
+        res = train_bench(a, rank, world, device, dump=a.dump_outputs)
         if selftest is not None:
             res["selftest"] = selftest
         if rank == 0:
@@ -984,6 +1029,10 @@ def _main():
         seed = 1234 + rank // 2     # a pair works on the same samples and draws the same DDIM noise
         torch.manual_seed(4321 + rank // 2)
         torch.cuda.manual_seed(4321 + rank // 2)
+    else:
+        # the sampler's eta = 1 noise comes from torch's default generators, whose CUDA seed is random unless set: seeded per
+        # rank, so that the same arguments sample the same images (--dump-outputs)
+        torch.manual_seed(4321 + rank)
 
     _STAGE[0] = "build_model"
     model = build_model(device, a.workload)
@@ -1022,7 +1071,7 @@ def _main():
         sample_once(model, batch, B)
     barrier()
     _STAGE[0] = "timed region"
-    hw = HwSampler(device).start() if rank == 0 else None      # shader clock / socket power over exactly the timed region
+    hw = HwSampler(device).start() if rank == 0 and a.side_measurements else None      # shader clock / socket power over exactly the timed region
     t0 = time.perf_counter()
     for _ in range(a.steps):
         out = sample_once(model, batch, B)
@@ -1034,6 +1083,10 @@ def _main():
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = tt.item()
     assert torch.isfinite(out).all()
+    dumped = None
+    if a.dump_outputs is not None and rank == 0:
+        _STAGE[0] = "dump outputs"
+        dumped = dump_outputs(a.dump_outputs, {"samples": out})
     _STAGE[0] = "report"
     ms_per_step = 1e3 * dt / a.steps
     images_per_s = replicas * samples_per_step * a.steps / dt
@@ -1054,6 +1107,8 @@ def _main():
            "per_unet_step_ms": unet_step_ms}
     if selftest is not None:
         res["selftest"] = selftest
+    if dumped is not None:
+        res["dump_outputs"] = dumped
     if a.workload != "single":
         res["config"]["workload"] = (f"config 4 ({a.workload}): {MV_WORKLOADS[a.workload]}, {samples_per_step} sample(s) = {B} "
                                      f"canvases per GPU (UNet batch {2 * B}), {S_DDIM} DDIM steps, cfg=2.5, eta=1.0, fp16")
@@ -1085,7 +1140,7 @@ def _main():
     if S_DDIM != 50:
         res["config"]["note"] = f"NOT the metric's configuration: {S_DDIM} DDIM steps per sampling (test / smoke run)"
 
-    if rank == 0 and not a.no_roofline and not (a.mv_shard and world == 1):      # (the instrumented eager step is not built for simulated peers)
+    if rank == 0 and a.side_measurements and not a.no_roofline and not (a.mv_shard and world == 1):      # (the instrumented eager step is not built for simulated peers)
         kern, fl = kernel_roofline(model, batch, B, a.dump_kernels)
         g = kern["gemm_conv"]
         traffic, traffic_note = None, "not measured (--no-traffic / multi-GPU / other workload)"
@@ -1120,7 +1175,7 @@ def _main():
         res["kernels"] = {"attention_kernel": kern["attention"], "xattn_block_kernel": kern.get("xattn_block"), "ffn_block_kernel": kern.get("ffn_block"), "stin_block_kernel": kern.get("stin_block"), "rowlin_kernel": kern.get("rowlin"),
                           "unet_step": {"algorithmic_tflop": 2 * B * fl["total"] / 1e12, "ms": unet_step_ms,
                                         "tflops": step_tflops, "frac_of_mfma_peak": step_tflops / MFMA_PEAK_TFLOPS}}
-    if rank == 0 and not a.no_roofline and a.workload == "single":
+    if rank == 0 and a.side_measurements and not a.no_roofline and a.workload == "single":
         # side measurements, reported beside the metric and never inside `value`; a failure here must not cost the bench line
         def side(name, fn):
             try:
@@ -1172,7 +1227,7 @@ def _main():
                 finally:
                     a.dtype, a.train_graph = "f16", prev_graph
             side("training_256x512_b16_bf16", train_bf16)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.side_measurements and not a.no_cpu_baseline:
         try:
             res["cpu_baseline"] = cpu_baseline()
         except Exception as e:      # noqa: BLE001

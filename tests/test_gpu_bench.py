@@ -19,7 +19,8 @@ def _json_lines(out):
 
 
 def test_bench_single_gpu_json_contract():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--side-measurements",
+                        "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = _json_lines(p.stdout)

@@ -201,8 +201,10 @@ def test_dropin_timestep_embedding_host_branch(golden):
     import leftrefill_amd.dropin as dropin
     dropin.install()
     from ldm.modules.diffusionmodules.util import timestep_embedding
-    out = timestep_embedding(torch.tensor([1, 21, 481, 981]), 320).numpy()
-    np.testing.assert_allclose(out, golden("ops")["timestep_embedding_320"], rtol=0, atol=2e-6)
+    from tests.test_oracle_golden import libm_atol
+    t = torch.tensor([1, 21, 481, 981])
+    out = timestep_embedding(t, 320).numpy()
+    np.testing.assert_array_less(np.abs(out - golden("ops")["timestep_embedding_320"]), libm_atol(t, 320))
 
 
 def test_state_dict_contract_full_config():

@@ -10,6 +10,14 @@ import torch
 from oracle import ddim_ref, golden_spec as G, unet_ref, weights
 
 
+def libm_atol(t, dim, max_period=10000):
+    """Per-element bound of the sinusoidal embedding for 1 ulp of libm difference in exp (the frequencies) and in cos / sin."""
+    half = dim // 2
+    freqs = torch.exp(-np.log(max_period) * torch.arange(0, half, dtype=torch.float32) / half).numpy()
+    arg = t.numpy().astype(np.float64)[:, None] * np.spacing(freqs)[None]
+    return 2e-6 + np.concatenate([arg, arg], axis=-1)
+
+
 @pytest.mark.parametrize("name,kind,p", G.OP_CASES, ids=[c[0] for c in G.OP_CASES])
 def test_op_matches_reference(golden, name, kind, p):
     ref = golden("ops")[name]
@@ -23,8 +31,9 @@ def test_timestep_embedding(golden):
     for dim in (320, 64):
         ref = golden("ops")[f"timestep_embedding_{dim}"]
         out = unet_ref.timestep_embedding(t, dim).numpy()
-        # cos/sin of fp32 arguments up to 981 rad: identical formula, allow 1 ulp of libm difference
-        np.testing.assert_allclose(out, ref, rtol=0, atol=2e-6)
+        # identical formula, allow 1 ulp of libm difference in each of exp and cos / sin: an ulp of the frequency f moves the
+        # argument t * f by t * ulp(f) rad (up to 981 rad here), hence the per-element bound
+        np.testing.assert_array_less(np.abs(out - ref), libm_atol(t, dim))
         assert np.allclose(out[:, 0], np.cos(t.numpy().astype(np.float32)), atol=1e-6)  # cos first
 
 
