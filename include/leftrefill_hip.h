@@ -92,6 +92,10 @@ int lr_layernorm(const lr_half* x, const float* gamma, const float* beta, float 
  * replaces: timestep_embedding (util.py:154-174; cos first), UNetModel.time_embed (openaimodel.py:528-532) and the
  *           22 ResBlock.emb_layers (217-223) batched as one [sum Cout][1280] weight. */
 int lr_timestep_embedding(const int64_t* t, int N, int dim, lr_half* out, lr_stream_t s);
+/* replaces: timestep_embedding (util.py:154-174) at continuous times -- `timesteps[:, None].float() * freqs` of the fp32 times
+ *           DPM-Solver feeds the model (dpm_solver.py:239-240, 999.0, 899.1, ...).  Same expression as lr_timestep_embedding
+ *           with t read as fp32: an integer-valued t gives the same bytes (ABI 27). */
+int lr_timestep_embedding_f32(const float* t, int N, int dim, lr_half* out, lr_stream_t s);
 /* out[m][n] = act_out( sum_k act_in(a[m][k]) * w[n][k] + bias[n] ), M <= 16; act: 0 none, 1 SiLU. K % 8 == 0. */
 int lr_linear_small_m(const lr_half* a, int lda, const lr_half* w, const float* bias, lr_half* out, int ldo, int M,
                       int N, int K, int act_in, int act_out, lr_stream_t s);
@@ -376,6 +380,30 @@ int lr_ddim_cfg_step(const float* x, const void* eps, int eps_is_f32, const floa
                      float* pred_x0, int64_t numel, float cfg_scale, float a_t, float a_prev, float sigma_t,
                      float sqrt_one_minus_at, lr_stream_t s);
 
+/* ---- fused classifier-free-guidance + PLMS update (ABI 27) -------------------------------------------------------
+ * replaces: PLMSSampler.p_sample_plms after the model call (plms.py:189-190 CFG combine, 225-241 multistep combination,
+ *           204-223 pred_x0 / x_prev with sigma = 0): e = e_u + s (e_c - e_u) rounded in the eps dtype;
+ *           e' = (w[0] e + w[1] hist[0] + ... + w[n_hist] hist[n_hist-1]) / divisor, left to right;
+ *           pred_x0 = (x - sqrt(1-a_t) e') / sqrt(a_t); x_prev = sqrt(a_prev) pred_x0 + sqrt(1-a_prev) e'.
+ * hist: n_hist (0..3) fp32 [numel] CFG-combined eps of earlier steps, newest first; weights: n_hist + 1 integer weights
+ *   (55,-59,37,-9 / 24; 23,-16,5 / 12; 3,-1 / 2; 1,1 / 2 for the second pass of the first step; 1 / 1).
+ * e_out (NULL = not written): fp32 [numel] CFG-combined e of this evaluation, the next step's history.  No device->host sync. */
+int lr_plms_cfg_step(const float* x, const void* eps, int eps_is_f32, const float* const* hist, int n_hist, const float* weights,
+                     float divisor, float* e_out, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float a_t,
+                     float a_prev, float sqrt_one_minus_at, lr_stream_t s);
+
+/* ---- fused classifier-free-guidance + DPM-Solver++ multistep update (ABI 27) ---------------------------------------
+ * replaces: model_wrapper's CFG combine (dpm_solver.py:302-314), DPM_Solver.data_prediction_fn (360-373, no thresholding) and
+ *           the predict_x0 updates: dpm_solver_first_update (469-514) for x0_prev == NULL, else
+ *           multistep_dpm_solver_second_update (723-778, solver_type 'dpm_solver').
+ *   x0_out = m0 = (x - sigma_s e) / alpha_s       (the next step's history)
+ *   order 1: x_next = ratio x - c m0                     ratio = sigma_t / sigma_s, c = alpha_t expm1(-h)
+ *   order 2: x_next = ratio x - c m0 - c_half D          c = alpha_t (exp(-h) - 1), c_half = 0.5 c, D = inv_r0 (m0 - x0_prev)
+ * The per-step scalars are computed once per sampling on the host, in fp32, in the reference's order. */
+int lr_dpmpp_cfg_step(const float* x, const void* eps, int eps_is_f32, const float* x0_prev, float* x0_out, float* x_next,
+                      int64_t numel, float cfg_scale, float sigma_s, float alpha_s, float ratio, float c, float c_half,
+                      float inv_r0, lr_stream_t s);
+
 /* ==== backward of the same operators (training with frozen weights: input gradients only) =========================
  * replaces: what torch.autograd derives for the reference's modules under `loss.backward()` (train_inpainting.py:141 ->
  *           LatentDiffusion.p_losses, ldm/models/diffusion/ddpm.py:900-935), recomputed per block by
@@ -459,6 +487,7 @@ int lr_nchw_f32_to_nhwc_bf16(const float* x1, int C1, const float* x2, int C2, l
 int lr_nhwc_f16_to_nchw_bf16(const lr_half* y, int Cstride, int C, void* out, int out_is_f32, int N, int H, int W,
     lr_stream_t s);
 int lr_timestep_embedding_bf16(const int64_t* t, int N, int dim, lr_half* out, lr_stream_t s);
+int lr_timestep_embedding_f32_bf16(const float* t, int N, int dim, lr_half* out, lr_stream_t s);
 int lr_linear_small_m_bf16(const lr_half* a, int lda, const lr_half* w, const float* bias, lr_half* out, int ldo, int
     M, int N, int K, int act_in, int act_out, lr_stream_t s);
 int lr_mv_gather_bf16(const lr_half* x, lr_half* seq, int b, int v, int s, int C, lr_stream_t st);
@@ -466,6 +495,11 @@ int lr_mv_scatter_bf16(const lr_half* seq, lr_half* x, int b, int v, int s, int 
 int lr_ddim_cfg_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* noise, float* x_prev, float*
     pred_x0, int64_t numel, float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at,
     lr_stream_t s);
+int lr_plms_cfg_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* const* hist, int n_hist, const float*
+    weights, float divisor, float* e_out, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float a_t, float a_prev,
+    float sqrt_one_minus_at, lr_stream_t s);
+int lr_dpmpp_cfg_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* x0_prev, float* x0_out, float* x_next,
+    int64_t numel, float cfg_scale, float sigma_s, float alpha_s, float ratio, float c, float c_half, float inv_r0, lr_stream_t s);
 int lr_geglu_fwd_bf16(const lr_half* pre, lr_half* out, int M, int H, lr_stream_t s);
 int lr_geglu_bwd_bf16(const lr_half* pre, const lr_half* dy, lr_half* dpre, int M, int H, lr_stream_t s);
 int lr_sumpool2x2_bf16(const lr_half* x, lr_half* y, int N, int H, int W, int C, lr_stream_t s);

@@ -47,10 +47,12 @@ __global__ void nhwc_to_nchw_kernel(const T* __restrict__ y, int Cstride, int C,
 
 // ---------------------------------------------------------------------------------------------------------------
 // timestep_embedding (util.py:154-174): out[n][0:half] = cos(t * f_j), out[n][half:] = sin(t * f_j),
-// f_j = exp(-ln(10000) * j / half), all in fp32 with the exact libm-class functions (t up to 981 rad: no fast-math).
+// f_j = exp(-ln(10000) * j / half), all in fp32 with the exact libm-class functions (t up to 999 rad: no fast-math).
+// TT = int64_t (discrete-time samplers) or float (continuous-time samplers: DPM-Solver feeds t = 949.05, ...); an
+// integer-valued float t gives the same bytes as the int64 entry.
 // ---------------------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void timestep_embedding_kernel(const int64_t* __restrict__ t, int N, int dim, T* __restrict__ out) {
+template <typename TT, typename T>
+__global__ void timestep_embedding_kernel(const TT* __restrict__ t, int N, int dim, T* __restrict__ out) {
   const int half = dim >> 1;
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= N * half) return;
@@ -231,6 +233,125 @@ __global__ void ddim_cfg_step_kernel(const float* __restrict__ x, const EpsT* __
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Fused sampler updates of the PLMS and DPM-Solver++ samplers: CFG combine + multistep combination + update, one pass.
+// The element arithmetic keeps the reference's order of operations op by op (no contraction into fma), so the fp32 result
+// matches torch's eager evaluation of the same expression.  V = 4: 16-byte fp32 / 8-byte 16-bit accesses (numel % 4 == 0
+// and aligned buffers), V = 1: scalar.
+// ---------------------------------------------------------------------------------------------------------------
+template <int V>
+__device__ __forceinline__ void ld_f32(const float* __restrict__ p, long long i, float (&v)[V]) {
+  if constexpr (V == 4) {
+    const float4 q = *reinterpret_cast<const float4*>(p + i);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+  } else {
+    v[0] = p[i];
+  }
+}
+
+template <int V>
+__device__ __forceinline__ void st_f32(float* __restrict__ p, long long i, const float (&v)[V]) {
+  if constexpr (V == 4) *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
+  else p[i] = v[0];
+}
+
+template <int V, typename EpsT>
+__device__ __forceinline__ void ld_eps(const EpsT* __restrict__ p, long long i, float (&v)[V]) {
+  if constexpr (V == 4 && sizeof(EpsT) == 2) {
+    const uint2 q = *reinterpret_cast<const uint2*>(p + i);
+    const EpsT* h = reinterpret_cast<const EpsT*>(&q);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = (float)h[k];
+  } else if constexpr (V == 4) {
+    ld_f32<4>(reinterpret_cast<const float*>(p), i, v);
+  } else {
+    v[0] = (float)p[i];
+  }
+}
+
+// e = e_u + s (e_c - e_u), rounded in the eps dtype exactly as ddim_cfg_step_kernel does
+template <typename EpsT, typename T>
+__device__ __forceinline__ float cfg_combine(float eu, float ec, float scale) {
+#pragma clang fp contract(off)
+  if constexpr (sizeof(EpsT) == 2) {
+    const T d = (T)(ec - eu);
+    const T sd = (T)(scale * (float)d);
+    return (float)(T)(eu + (float)sd);
+  } else {
+    return eu + scale * (ec - eu);
+  }
+}
+
+// PLMS (pseudo linear multistep, sigma = 0): e' = (w0 e + w1 h1 + w2 h2 + w3 h3) / div over the n_hist newest history
+// entries, then pred_x0 = (x - sqrt(1 - a_t) e') / sqrt(a_t), x_prev = sqrt(a_prev) pred_x0 + sqrt(1 - a_prev) e'.
+template <int V, typename EpsT, typename T>
+__global__ void plms_cfg_step_kernel(const float* __restrict__ x, const EpsT* __restrict__ eps, const float* __restrict__ h1,
+                                     const float* __restrict__ h2, const float* __restrict__ h3, float* __restrict__ e_out,
+                                     float* __restrict__ x_prev, float* __restrict__ pred_x0, long long numel, int n_hist,
+                                     float scale, float w0, float w1, float w2, float w3, float div, float sqrt_at,
+                                     float sqrt_1m_at, float sqrt_aprev, float dir_coef) {
+#pragma clang fp contract(off)
+  const long long groups = numel / V;
+  for (long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
+    const long long i = g * V;
+    float eu[V], ec[V], xv[V], a[V], b[V], c[V], e[V], p0[V], xp[V];
+    ld_eps<V, EpsT>(eps, i, eu);
+    ld_eps<V, EpsT>(eps, numel + i, ec);
+    ld_f32<V>(x, i, xv);
+    if (n_hist > 0) ld_f32<V>(h1, i, a);
+    if (n_hist > 1) ld_f32<V>(h2, i, b);
+    if (n_hist > 2) ld_f32<V>(h3, i, c);
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      e[k] = cfg_combine<EpsT, T>(eu[k], ec[k], scale);
+      float acc = w0 * e[k];                         // integer weights, left to right, then ONE division (plms.py:225-241)
+      if (n_hist > 0) acc = acc + w1 * a[k];
+      if (n_hist > 1) acc = acc + w2 * b[k];
+      if (n_hist > 2) acc = acc + w3 * c[k];
+      const float ep = acc / div;
+      p0[k] = (xv[k] - sqrt_1m_at * ep) / sqrt_at;
+      xp[k] = sqrt_aprev * p0[k] + dir_coef * ep;
+    }
+    if (e_out) st_f32<V>(e_out, i, e);
+    st_f32<V>(pred_x0, i, p0);
+    st_f32<V>(x_prev, i, xp);
+  }
+}
+
+// DPM-Solver++ multistep (data prediction, solver_type 'dpm_solver'): m0 = (x - sigma_s e) / alpha_s, then
+//   order 1: x_t = ratio x - c m0,                     c = alpha_t expm1(-h)
+//   order 2: x_t = ratio x - c m0 - c_half D,          c = alpha_t (e^-h - 1), c_half = 0.5 c, D = inv_r0 (m0 - m1)
+template <int V, typename EpsT, typename T>
+__global__ void dpmpp_cfg_step_kernel(const float* __restrict__ x, const EpsT* __restrict__ eps, const float* __restrict__ x0_prev,
+                                      float* __restrict__ x0_out, float* __restrict__ x_next, long long numel, float scale,
+                                      float sigma_s, float alpha_s, float ratio, float c, float c_half, float inv_r0) {
+#pragma clang fp contract(off)
+  const long long groups = numel / V;
+  for (long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
+    const long long i = g * V;
+    float eu[V], ec[V], xv[V], m1[V], m0[V], xt[V];
+    ld_eps<V, EpsT>(eps, i, eu);
+    ld_eps<V, EpsT>(eps, numel + i, ec);
+    ld_f32<V>(x, i, xv);
+    if (x0_prev) ld_f32<V>(x0_prev, i, m1);
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      const float e = cfg_combine<EpsT, T>(eu[k], ec[k], scale);
+      m0[k] = (xv[k] - sigma_s * e) / alpha_s;
+      float v = ratio * xv[k] - c * m0[k];
+      if (x0_prev) {
+        const float D = inv_r0 * (m0[k] - m1[k]);
+        v = v - c_half * D;
+      }
+      xt[k] = v;
+    }
+    st_f32<V>(x0_out, i, m0);
+    st_f32<V>(x_next, i, xt);
+  }
+}
+
+static inline bool aligned16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
+
 static inline int grid_for(long long total, int block, int cap = 4096) {
   long long g = (total + block - 1) / block;
   if (g > cap) g = cap;
@@ -238,7 +359,7 @@ static inline int grid_for(long long total, int block, int cap = 4096) {
   return (int)g;
 }
 
-extern "C" int lr_abi_version(void) { return 26; }
+extern "C" int lr_abi_version(void) { return 27; }
 
 #ifdef LR_DEV_VARIANTS
 // developer build only: name -> value table behind LR_DEV (common.h); set through lr_dev_set by the Python front end
@@ -292,11 +413,11 @@ static int lr_nhwc_f16_to_nchw_t(const lr_half* y, int Cstride, int C, void* out
   return lr_launch_status();
 }
 
-template <typename T>
-static int lr_timestep_embedding_t(const int64_t* t, int N, int dim, lr_half* out, lr_stream_t s) {
+template <typename TT, typename T>
+static int lr_timestep_embedding_t(const TT* t, int N, int dim, lr_half* out, lr_stream_t s) {
   if (!t || !out || N <= 0 || dim < 2) return LR_E_ARG;
   const int total = N * (dim / 2);
-  hipLaunchKernelGGL(timestep_embedding_kernel<T>, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)s, t, N, dim,
+  hipLaunchKernelGGL((timestep_embedding_kernel<TT, T>), dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)s, t, N, dim,
                      (T*)out);
   return lr_launch_status();
 }
@@ -368,6 +489,69 @@ static int lr_ddim_cfg_step_t(const float* x, const void* eps, int eps_is_f32, c
   return lr_launch_status();
 }
 
+template <int V, typename EpsT, typename T>
+static void launch_plms(const float* x, const void* eps, const float* h1, const float* h2, const float* h3, float* e_out,
+                        float* x_prev, float* pred_x0, long long numel, int n_hist, float scale, const float* w, float div,
+                        float sqrt_at, float sqrt_1m_at, float sqrt_aprev, float dir_coef, hipStream_t s) {
+  hipLaunchKernelGGL((plms_cfg_step_kernel<V, EpsT, T>), dim3(grid_for(numel / V, 256)), dim3(256), 0, s, x, (const EpsT*)eps,
+                     h1, h2, h3, e_out, x_prev, pred_x0, numel, n_hist, scale, w[0], w[1], w[2], w[3], div, sqrt_at, sqrt_1m_at,
+                     sqrt_aprev, dir_coef);
+}
+
+template <typename T>
+static int lr_plms_cfg_step_t(const float* x, const void* eps, int eps_is_f32, const float* const* hist, int n_hist,
+                              const float* weights, float divisor, float* e_out, float* x_prev, float* pred_x0, int64_t numel,
+                              float cfg_scale, float a_t, float a_prev, float sqrt_one_minus_at, lr_stream_t s) {
+  if (!x || !eps || !x_prev || !pred_x0 || !weights || numel <= 0 || n_hist < 0 || n_hist > 3 || divisor == 0.f) return LR_E_ARG;
+  if (n_hist > 0 && !hist) return LR_E_ARG;
+  const float* h[3] = {nullptr, nullptr, nullptr};
+  for (int k = 0; k < n_hist; ++k) {
+    if (!hist[k]) return LR_E_ARG;
+    h[k] = hist[k];
+  }
+  float w[4] = {weights[0], 0.f, 0.f, 0.f};
+  for (int k = 0; k < n_hist; ++k) w[k + 1] = weights[k + 1];
+  // same fp32 scalar arithmetic as the reference's 0-dim fp32 tensors (plms.py:204-223, sigma = 0)
+  const float sqrt_at = sqrtf(a_t);
+  const float sqrt_aprev = sqrtf(a_prev);
+  const float dir_coef = sqrtf(1.0f - a_prev - 0.0f);
+  const bool vec = numel % 4 == 0 && aligned16(x) && aligned16(h[0]) && aligned16(h[1]) && aligned16(h[2]) && aligned16(e_out) &&
+                   aligned16(x_prev) && aligned16(pred_x0) && ((uintptr_t)eps & (eps_is_f32 ? 15 : 7)) == 0;
+  hipStream_t st = (hipStream_t)s;
+  if (eps_is_f32) {
+    if (vec) launch_plms<4, float, T>(x, eps, h[0], h[1], h[2], e_out, x_prev, pred_x0, numel, n_hist, cfg_scale, w, divisor, sqrt_at, sqrt_one_minus_at, sqrt_aprev, dir_coef, st);
+    else launch_plms<1, float, T>(x, eps, h[0], h[1], h[2], e_out, x_prev, pred_x0, numel, n_hist, cfg_scale, w, divisor, sqrt_at, sqrt_one_minus_at, sqrt_aprev, dir_coef, st);
+  } else {
+    if (vec) launch_plms<4, T, T>(x, eps, h[0], h[1], h[2], e_out, x_prev, pred_x0, numel, n_hist, cfg_scale, w, divisor, sqrt_at, sqrt_one_minus_at, sqrt_aprev, dir_coef, st);
+    else launch_plms<1, T, T>(x, eps, h[0], h[1], h[2], e_out, x_prev, pred_x0, numel, n_hist, cfg_scale, w, divisor, sqrt_at, sqrt_one_minus_at, sqrt_aprev, dir_coef, st);
+  }
+  return lr_launch_status();
+}
+
+template <int V, typename EpsT, typename T>
+static void launch_dpmpp(const float* x, const void* eps, const float* x0_prev, float* x0_out, float* x_next, long long numel,
+                         float scale, float sigma_s, float alpha_s, float ratio, float c, float c_half, float inv_r0, hipStream_t s) {
+  hipLaunchKernelGGL((dpmpp_cfg_step_kernel<V, EpsT, T>), dim3(grid_for(numel / V, 256)), dim3(256), 0, s, x, (const EpsT*)eps,
+                     x0_prev, x0_out, x_next, numel, scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0);
+}
+
+template <typename T>
+static int lr_dpmpp_cfg_step_t(const float* x, const void* eps, int eps_is_f32, const float* x0_prev, float* x0_out, float* x_next,
+                               int64_t numel, float cfg_scale, float sigma_s, float alpha_s, float ratio, float c, float c_half,
+                               float inv_r0, lr_stream_t s) {
+  if (!x || !eps || !x0_out || !x_next || numel <= 0 || alpha_s == 0.f) return LR_E_ARG;
+  const bool vec = numel % 4 == 0 && aligned16(x) && aligned16(x0_prev) && aligned16(x0_out) && aligned16(x_next) &&
+                   ((uintptr_t)eps & (eps_is_f32 ? 15 : 7)) == 0;
+  hipStream_t st = (hipStream_t)s;
+  if (eps_is_f32) {
+    if (vec) launch_dpmpp<4, float, T>(x, eps, x0_prev, x0_out, x_next, numel, cfg_scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0, st);
+    else launch_dpmpp<1, float, T>(x, eps, x0_prev, x0_out, x_next, numel, cfg_scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0, st);
+  } else {
+    if (vec) launch_dpmpp<4, T, T>(x, eps, x0_prev, x0_out, x_next, numel, cfg_scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0, st);
+    else launch_dpmpp<1, T, T>(x, eps, x0_prev, x0_out, x_next, numel, cfg_scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0, st);
+  }
+  return lr_launch_status();
+}
 
 // =====================================================================================================================
 // Backward helpers (training with frozen weights)
@@ -514,8 +698,10 @@ extern "C" int lr_nchw_f32_to_nhwc_f16(const float* x1, int C1, const float* x2,
 extern "C" int lr_nchw_f32_to_nhwc_bf16(const float* x1, int C1, const float* x2, int C2, lr_half* y, int Cpad, int N, int H, int W, lr_stream_t s) { return lr_nchw_f32_to_nhwc_t<bf16>(x1, C1, x2, C2, y, Cpad, N, H, W, s); }
 extern "C" int lr_nhwc_f16_to_nchw(const lr_half* y, int Cstride, int C, void* out, int out_is_f32, int N, int H, int W, lr_stream_t s) { return lr_nhwc_f16_to_nchw_t<f16>(y, Cstride, C, out, out_is_f32, N, H, W, s); }
 extern "C" int lr_nhwc_f16_to_nchw_bf16(const lr_half* y, int Cstride, int C, void* out, int out_is_f32, int N, int H, int W, lr_stream_t s) { return lr_nhwc_f16_to_nchw_t<bf16>(y, Cstride, C, out, out_is_f32, N, H, W, s); }
-extern "C" int lr_timestep_embedding(const int64_t* t, int N, int dim, lr_half* out, lr_stream_t s) { return lr_timestep_embedding_t<f16>(t, N, dim, out, s); }
-extern "C" int lr_timestep_embedding_bf16(const int64_t* t, int N, int dim, lr_half* out, lr_stream_t s) { return lr_timestep_embedding_t<bf16>(t, N, dim, out, s); }
+extern "C" int lr_timestep_embedding(const int64_t* t, int N, int dim, lr_half* out, lr_stream_t s) { return lr_timestep_embedding_t<int64_t, f16>(t, N, dim, out, s); }
+extern "C" int lr_timestep_embedding_bf16(const int64_t* t, int N, int dim, lr_half* out, lr_stream_t s) { return lr_timestep_embedding_t<int64_t, bf16>(t, N, dim, out, s); }
+extern "C" int lr_timestep_embedding_f32(const float* t, int N, int dim, lr_half* out, lr_stream_t s) { return lr_timestep_embedding_t<float, f16>(t, N, dim, out, s); }
+extern "C" int lr_timestep_embedding_f32_bf16(const float* t, int N, int dim, lr_half* out, lr_stream_t s) { return lr_timestep_embedding_t<float, bf16>(t, N, dim, out, s); }
 extern "C" int lr_linear_small_m(const lr_half* a, int lda, const lr_half* w, const float* bias, lr_half* out, int ldo, int M, int N, int K, int act_in, int act_out, lr_stream_t s) { return lr_linear_small_m_t<f16>(a, lda, w, bias, out, ldo, M, N, K, act_in, act_out, s); }
 extern "C" int lr_linear_small_m_bf16(const lr_half* a, int lda, const lr_half* w, const float* bias, lr_half* out, int ldo, int M, int N, int K, int act_in, int act_out, lr_stream_t s) { return lr_linear_small_m_t<bf16>(a, lda, w, bias, out, ldo, M, N, K, act_in, act_out, s); }
 extern "C" int lr_mv_gather(const lr_half* x, lr_half* seq, int b, int v, int s, int C, lr_stream_t st) { return lr_mv_gather_t<f16>(x, seq, b, v, s, C, st); }
@@ -524,6 +710,10 @@ extern "C" int lr_mv_scatter(const lr_half* seq, lr_half* x, int b, int v, int s
 extern "C" int lr_mv_scatter_bf16(const lr_half* seq, lr_half* x, int b, int v, int s, int C, lr_stream_t st) { return lr_mv_scatter_t<bf16>(seq, x, b, v, s, C, st); }
 extern "C" int lr_ddim_cfg_step(const float* x, const void* eps, int eps_is_f32, const float* noise, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, lr_stream_t s) { return lr_ddim_cfg_step_t<f16>(x, eps, eps_is_f32, noise, x_prev, pred_x0, numel, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, s); }
 extern "C" int lr_ddim_cfg_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* noise, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, lr_stream_t s) { return lr_ddim_cfg_step_t<bf16>(x, eps, eps_is_f32, noise, x_prev, pred_x0, numel, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, s); }
+extern "C" int lr_plms_cfg_step(const float* x, const void* eps, int eps_is_f32, const float* const* hist, int n_hist, const float* weights, float divisor, float* e_out, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float a_t, float a_prev, float sqrt_one_minus_at, lr_stream_t s) { return lr_plms_cfg_step_t<f16>(x, eps, eps_is_f32, hist, n_hist, weights, divisor, e_out, x_prev, pred_x0, numel, cfg_scale, a_t, a_prev, sqrt_one_minus_at, s); }
+extern "C" int lr_plms_cfg_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* const* hist, int n_hist, const float* weights, float divisor, float* e_out, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float a_t, float a_prev, float sqrt_one_minus_at, lr_stream_t s) { return lr_plms_cfg_step_t<bf16>(x, eps, eps_is_f32, hist, n_hist, weights, divisor, e_out, x_prev, pred_x0, numel, cfg_scale, a_t, a_prev, sqrt_one_minus_at, s); }
+extern "C" int lr_dpmpp_cfg_step(const float* x, const void* eps, int eps_is_f32, const float* x0_prev, float* x0_out, float* x_next, int64_t numel, float cfg_scale, float sigma_s, float alpha_s, float ratio, float c, float c_half, float inv_r0, lr_stream_t s) { return lr_dpmpp_cfg_step_t<f16>(x, eps, eps_is_f32, x0_prev, x0_out, x_next, numel, cfg_scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0, s); }
+extern "C" int lr_dpmpp_cfg_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* x0_prev, float* x0_out, float* x_next, int64_t numel, float cfg_scale, float sigma_s, float alpha_s, float ratio, float c, float c_half, float inv_r0, lr_stream_t s) { return lr_dpmpp_cfg_step_t<bf16>(x, eps, eps_is_f32, x0_prev, x0_out, x_next, numel, cfg_scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0, s); }
 extern "C" int lr_geglu_fwd(const lr_half* pre, lr_half* out, int M, int H, lr_stream_t s) { return lr_geglu_fwd_t<f16>(pre, out, M, H, s); }
 extern "C" int lr_geglu_fwd_bf16(const lr_half* pre, lr_half* out, int M, int H, lr_stream_t s) { return lr_geglu_fwd_t<bf16>(pre, out, M, H, s); }
 extern "C" int lr_geglu_bwd(const lr_half* pre, const lr_half* dy, lr_half* dpre, int M, int H, lr_stream_t s) { return lr_geglu_bwd_t<f16>(pre, dy, dpre, M, H, s); }

@@ -11,6 +11,19 @@ from ldm.models.diffusion.ddim import DDIMSampler
 from ldm.models.diffusion.ddpm import LatentInpaintDiffusion
 
 
+def make_sampler(name, model):
+    """"ddim" | "plms" | "dpm_solver" -> the drop-in sampler of that name over `model`."""
+    if name == "ddim":
+        return DDIMSampler(model)
+    if name == "plms":
+        from ldm.models.diffusion.plms import PLMSSampler
+        return PLMSSampler(model)
+    if name == "dpm_solver":
+        from ldm.models.diffusion.dpm_solver import DPMSolverSampler
+        return DPMSolverSampler(model)
+    raise ValueError(f"unknown sampler {name!r}: 'ddim', 'plms' or 'dpm_solver'")
+
+
 class RefInpaintLDM(LatentInpaintDiffusion):
     def __init__(self, *args, **kwargs):
         data_cfg = kwargs.pop('data_config', None)
@@ -34,7 +47,8 @@ class RefInpaintLDM(LatentInpaintDiffusion):
         return self.get_learned_conditioning([""] * N)
 
     @torch.no_grad()
-    def log_images(self, batch, N=4, ddim_steps=50, ddim_eta=0.0, unconditional_guidance_scale=9.0, **kwargs):
+    def log_images(self, batch, N=4, ddim_steps=50, ddim_eta=0.0, unconditional_guidance_scale=9.0, sampler="ddim", **kwargs):
+        """sampler: "ddim" (the reference's), "plms" or "dpm_solver"; ddim_steps is the step count of any of them."""
         use_ddim = ddim_steps is not None
         log = dict()
         z, c = self.get_input(batch, self.first_stage_key, bs=N)
@@ -47,20 +61,20 @@ class RefInpaintLDM(LatentInpaintDiffusion):
             samples, _ = self.sample_log(cond={"c_concat": [c_concat], "c_crossattn": [c_crossattn]}, batch_size=N,
                                          ddim=use_ddim, ddim_steps=ddim_steps, eta=ddim_eta,
                                          unconditional_guidance_scale=unconditional_guidance_scale,
-                                         unconditional_conditioning=uc_full)
+                                         unconditional_conditioning=uc_full, sampler=sampler)
         elif unconditional_guidance_scale == 0.0:
             uc_cross = self.get_unconditional_conditioning(N)
             samples, _ = self.sample_log(cond={"c_concat": [c_concat], "c_crossattn": [uc_cross]}, batch_size=N,
-                                         ddim=use_ddim, ddim_steps=ddim_steps, eta=ddim_eta)
+                                         ddim=use_ddim, ddim_steps=ddim_steps, eta=ddim_eta, sampler=sampler)
         else:
             samples, _ = self.sample_log(cond={"c_concat": [c_concat], "c_crossattn": [c_crossattn]}, batch_size=N,
-                                         ddim=use_ddim, ddim_steps=ddim_steps, eta=ddim_eta)
+                                         ddim=use_ddim, ddim_steps=ddim_steps, eta=ddim_eta, sampler=sampler)
         log["pred"] = self.decode_first_stage(samples)
         return log
 
     @torch.no_grad()
-    def sample_log(self, cond, batch_size, ddim, ddim_steps, **kwargs):
-        sampler = DDIMSampler(self)
+    def sample_log(self, cond, batch_size, ddim, ddim_steps, sampler="ddim", **kwargs):
+        sampler = make_sampler(sampler, self)
         _, _, h, w = cond["c_concat"][0].shape
         shape = (self.channels, h, w)   # latent size comes from c_concat (reference 77-79)
         return sampler.sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)

@@ -17,7 +17,80 @@ from leftrefill_amd import ops
 from ldm.modules.diffusionmodules.util import make_ddim_sampling_parameters, make_ddim_timesteps, noise_like
 
 
-class DDIMSampler(object):
+class CFGModelEval(object):
+    """What every sampler of this package does around one model evaluation (DDIM, PLMS, DPM-Solver++): the [uncond; cond]
+    batch built once per sampling, the CFG shared-prefix flag, the embedding rows of every timestep of the sampling computed up
+    front and each step's timestep named to the UNet on the host -- so each evaluation is one replay of the same captured step."""
+
+    def _unet(self):
+        return getattr(getattr(self.model, "model", None), "diffusion_model", None)
+
+    def _prepare_timesteps(self, steps):
+        """The schedule is known before the first step: the UNet computes the embedding rows of all its timesteps in one go
+        (UNetModel.prepare_timesteps) and each step names its timestep on the host (`_step_hint`)."""
+        unet = self._unet()
+        if hasattr(unet, "prepare_timesteps"):
+            unet.prepare_timesteps(int(s_) for s_ in steps)
+
+    def _step_hint(self, step):
+        """step: the host timestep of this evaluation -- an int, or the exact fp32 value of a continuous time (a python float)."""
+        unet = self._unet()
+        if hasattr(unet, "prepare_timesteps"):
+            unet._t_host = None if step is None else (step if isinstance(step, float) else int(step))
+
+    # the conditioning is constant over the loop: build the [uncond; cond] batch once instead of 50 torch.cat calls
+    def _prepare_cfg_inputs(self, c, uc, scale):
+        self._cfg_cache = None
+        self._cfg_shared = False
+        if uc is None or scale == 1. or not isinstance(c, dict):
+            return
+        c_in = {}
+        for k in c:
+            if isinstance(c[k], list):
+                c_in[k] = [torch.cat([uc[k][i], c[k][i]]) for i in range(len(c[k]))]
+            else:
+                c_in[k] = torch.cat([uc[k], c[k]])
+        self._cfg_cache = (id(c), id(uc), c_in)
+        # the two halves of the CFG batch differ only in the cross-attention context when every other conditioning tensor
+        # is the same for uncond and cond: checked once per sampling, lets the UNet share the context-free prefix
+        import os
+        self._cfg_shared = os.environ.get("LEFTREFILL_CFG_SHARED_PREFIX", "1") != "0" and all(
+            all(torch.equal(u_, c_) for u_, c_ in zip(uc[k], c[k])) if isinstance(c[k], list) else torch.equal(uc[k], c[k])
+            for k in c if k != "c_crossattn")
+
+    def _cfg_eps(self, x, c, t, unconditional_conditioning, scale):
+        """One model evaluation on the [uncond; cond] batch (one UNet call, uncond half first, ddim.py:317-342) -> (eps [2B, ...]
+        contiguous, the guidance scale to combine it with).  Without an unconditional pass (or at scale 1) the single output is
+        returned twice with scale 1.0, so e_u + 1.0 (e_c - e_u) = e.  Split-CFG across ranks is the caller's business."""
+        if unconditional_conditioning is None or scale == 1.:
+            e = self.model.apply_model(x, t, c)
+            return torch.cat([e, e]).contiguous(), 1.0      # degenerate CFG: e_u = e_c = e  ->  e_t = e
+        cache = getattr(self, "_cfg_cache", None)
+        if cache is not None and cache[0] == id(c) and cache[1] == id(unconditional_conditioning):
+            c_in = cache[2]
+        elif isinstance(c, torch.Tensor):          # plain-tensor conditioning (apply_model wraps it by the conditioning key)
+            c_in = torch.cat([unconditional_conditioning, c])
+        else:
+            assert isinstance(c, dict) and isinstance(unconditional_conditioning, dict)
+            c_in = {k: ([torch.cat([unconditional_conditioning[k][i], c[k][i]]) for i in range(len(c[k]))]
+                        if isinstance(c[k], list) else torch.cat([unconditional_conditioning[k], c[k]]))
+                    for k in c}
+        x_in = torch.cat([x] * 2)
+        t_in = torch.cat([t] * 2)
+        unet = self._unet()
+        shared = (cache is not None and c_in is cache[2] and getattr(self, "_cfg_shared", False)
+                  and hasattr(unet, "cfg_shared_prefix"))
+        if shared:
+            unet.cfg_shared_prefix = True
+        try:
+            eps = self.model.apply_model(x_in, t_in, c_in)   # [2B, 4, h, w], uncond half first (ddim.py:317-342)
+        finally:
+            if shared:
+                unet.cfg_shared_prefix = False
+        return eps.contiguous(), scale
+
+
+class DDIMSampler(CFGModelEval):
     def __init__(self, model, schedule="linear", **kwargs):
         super().__init__()
         self.model = model
@@ -150,41 +223,6 @@ class DDIMSampler(object):
                 callback(i)
         return img[0], {}
 
-    def _unet(self):
-        return getattr(getattr(self.model, "model", None), "diffusion_model", None)
-
-    def _prepare_timesteps(self, steps):
-        """The schedule is known before the first step: the UNet computes the embedding rows of all its timesteps in one go
-        (UNetModel.prepare_timesteps) and each step names its timestep on the host (`_step_hint`)."""
-        unet = self._unet()
-        if hasattr(unet, "prepare_timesteps"):
-            unet.prepare_timesteps(int(s_) for s_ in steps)
-
-    def _step_hint(self, step):
-        unet = self._unet()
-        if hasattr(unet, "prepare_timesteps"):
-            unet._t_host = None if step is None else int(step)
-
-    # the conditioning is constant over the loop: build the [uncond; cond] batch once instead of 50 torch.cat calls
-    def _prepare_cfg_inputs(self, c, uc, scale):
-        self._cfg_cache = None
-        self._cfg_shared = False
-        if uc is None or scale == 1. or not isinstance(c, dict):
-            return
-        c_in = {}
-        for k in c:
-            if isinstance(c[k], list):
-                c_in[k] = [torch.cat([uc[k][i], c[k][i]]) for i in range(len(c[k]))]
-            else:
-                c_in[k] = torch.cat([uc[k], c[k]])
-        self._cfg_cache = (id(c), id(uc), c_in)
-        # the two halves of the CFG batch differ only in the cross-attention context when every other conditioning tensor
-        # is the same for uncond and cond: checked once per sampling, lets the UNet share the context-free prefix
-        import os
-        self._cfg_shared = os.environ.get("LEFTREFILL_CFG_SHARED_PREFIX", "1") != "0" and all(
-            all(torch.equal(u_, c_) for u_, c_ in zip(uc[k], c[k])) if isinstance(c[k], list) else torch.equal(uc[k], c[k])
-            for k in c if k != "c_crossattn")
-
     @torch.no_grad()
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
@@ -210,11 +248,7 @@ class DDIMSampler(object):
         x = x.float().contiguous()
         device = x.device
         scale = float(unconditional_guidance_scale)
-        if unconditional_conditioning is None or scale == 1.:
-            e = self.model.apply_model(x, t, c)
-            eps = torch.cat([e, e])      # degenerate CFG: e_u = e_c = e  ->  e_t = e
-            scale = 1.0
-        else:
+        if unconditional_conditioning is not None and scale != 1.:
             from leftrefill_amd import dist as lrd
             if lrd.split_cfg_active():
                 # cond / uncond passes on two ranks (or, without a process group, one after the other): batch B each, one
@@ -242,27 +276,7 @@ class DDIMSampler(object):
                 sigma = float(self.ddim_sigmas[index])
                 return ops.ddim_cfg_step(x, eps.contiguous(), noise, scale, self.ddim_alphas[index], self.ddim_alphas_prev[index],
                                          sigma * float(temperature), self.ddim_sqrt_one_minus_alphas[index])
-            cache = getattr(self, "_cfg_cache", None)
-            if cache is not None and cache[0] == id(c) and cache[1] == id(unconditional_conditioning):
-                c_in = cache[2]
-            else:
-                assert isinstance(c, dict) and isinstance(unconditional_conditioning, dict)
-                c_in = {k: ([torch.cat([unconditional_conditioning[k][i], c[k][i]]) for i in range(len(c[k]))]
-                            if isinstance(c[k], list) else torch.cat([unconditional_conditioning[k], c[k]]))
-                        for k in c}
-            x_in = torch.cat([x] * 2)
-            t_in = torch.cat([t] * 2)
-            unet = getattr(getattr(self.model, "model", None), "diffusion_model", None)
-            shared = (cache is not None and c_in is cache[2] and getattr(self, "_cfg_shared", False)
-                      and hasattr(unet, "cfg_shared_prefix"))
-            if shared:
-                unet.cfg_shared_prefix = True
-            try:
-                eps = self.model.apply_model(x_in, t_in, c_in)   # [2B, 4, h, w], uncond half first (ddim.py:317-342)
-            finally:
-                if shared:
-                    unet.cfg_shared_prefix = False
-        eps = eps.contiguous()
+        eps, scale = self._cfg_eps(x, c, t, unconditional_conditioning, scale)
         # randn is drawn every step like the reference (ddim.py:378), also when sigma_t == 0
         noise = noise_like(x.shape, device, repeat_noise)
         sigma = float(self.ddim_sigmas[index])

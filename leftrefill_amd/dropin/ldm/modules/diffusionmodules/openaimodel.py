@@ -17,6 +17,7 @@ from abc import abstractmethod
 
 import os
 
+import numpy as np
 import torch
 import torch as th
 import torch.nn as nn
@@ -379,7 +380,7 @@ class UNetModel(nn.Module):
         return act
 
     def _embed(self, timesteps):
-        """timesteps [M] int64 -> [M, sum Cout]: sinusoidal embedding, time MLP (reference openaimodel.py:775-776) and the
+        """timesteps [M] int64 or fp32 -> [M, sum Cout]: sinusoidal embedding, time MLP (reference openaimodel.py:775-776) and the
         emb_layers projection of every ResBlock (266) as one batched GEMV.  A row depends on its own timestep only."""
         P = self._plan
         t_emb = ops.timestep_embedding(timesteps, self.model_channels, self.compute_dtype)
@@ -397,15 +398,19 @@ class UNetModel(nn.Module):
         if not EMB_TABLE:
             self._emb_table = {}
             return
-        steps = [int(s_) for s_ in dict.fromkeys(int(s_) for s_ in steps)]
+        # integer timesteps (DDIM, PLMS) are keyed by int, continuous ones (DPM-Solver) by their exact fp32 value and embedded
+        # at that value (lr_timestep_embedding_f32); an integer-valued float shares the int's key, its row is the same bytes
+        steps = list(dict.fromkeys(_t_key(s_) for s_ in steps))
         dev = next(self.parameters()).device
         table = {}
         with torch.no_grad():
-            for i in range(0, len(steps), 16):
-                chunk = steps[i:i + 16]
-                rows = self._embed(torch.tensor(chunk, device=dev, dtype=torch.int64))
-                for j, s_ in enumerate(chunk):
-                    table[s_] = rows[j]
+            for kind in (int, float):
+                ks = [s_ for s_ in steps if type(s_) is kind]
+                for i in range(0, len(ks), 16):
+                    chunk = ks[i:i + 16]
+                    rows = self._embed(torch.tensor(chunk, device=dev, dtype=torch.int64 if kind is int else torch.float32))
+                    for j, s_ in enumerate(chunk):
+                        table[s_] = rows[j]
         self._emb_table = table
         self._emb_table_plan = self._plan      # rows belong to THIS packing: a re-pack (changed weights) drops them (see _emb_rows)
 
@@ -417,7 +422,7 @@ class UNetModel(nn.Module):
         hint = self.__dict__.get("_t_host")
         if self.__dict__.get("_emb_table_plan") is not self._plan:      # prepare() re-packed since the table was built: stale rows
             self._emb_table = {}
-        row = self.__dict__.get("_emb_table", {}).get(hint) if hint is not None else None
+        row = self.__dict__.get("_emb_table", {}).get(_t_key(hint)) if hint is not None else None
         if row is not None and row.dtype == self.compute_dtype:
             rows = row.unsqueeze(0).expand(N, -1)
             return rows.contiguous() if out is None else out.copy_(rows)
@@ -565,7 +570,8 @@ class UNetModel(nn.Module):
         assert y is None, "must specify y if and only if the model is class-conditional"
         self.prepare()
         x = x.float().contiguous()
-        timesteps = timesteps.to(torch.int64).contiguous()
+        # the dtype decides, not the values (no host sync): integer timesteps stay int64, floating ones fp32 (continuous time)
+        timesteps = timesteps.to(torch.float32 if timesteps.is_floating_point() else torch.int64).contiguous()
         ctx_src = context
         if torch.is_grad_enabled() and x.requires_grad:
             raise NotImplementedError("gradient w.r.t. the noisy latent is not produced (p_losses feeds x_noisy without grad)")
@@ -594,10 +600,19 @@ class UNetModel(nn.Module):
         return g.replay(x, timesteps, context, ctx_src)
 
 
+def _t_key(t):
+    """Key of a timestep's embedding row: an int for integer timesteps, the exact fp32 value (as a python float) otherwise."""
+    if isinstance(t, (float, np.floating)):
+        return float(np.float32(t))
+    return int(t)
+
+
 class _StepGraph:
     """One captured hipGraph of the UNet forward for a fixed (x, context) shape."""
 
     def __init__(self, model, x, t, ctx, shared_prefix=False):
+        # t reaches the captured work only through the embedding rows `self.emb` (filled by `replay` from the caller's t, int64 or
+        # fp32): the graph does not depend on the dtype of t, and a continuous-time step replays the graph a DDIM step captured
         self.model = model
         self.x = x.clone()
         self.t = t.clone()

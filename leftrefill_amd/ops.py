@@ -232,10 +232,12 @@ def layer_norm(x, gamma, beta, eps=1e-5):
 
 
 def timestep_embedding(t, dim, dtype=torch.float16):
+    """t [N]: a floating-point t is embedded at its fp32 value (continuous-time samplers), any other dtype as int64."""
     lib = _lib.load()
-    t = t.to(torch.int64).contiguous()
+    name = "lr_timestep_embedding_f32" if t.is_floating_point() else "lr_timestep_embedding"
+    t = t.to(torch.float32 if t.is_floating_point() else torch.int64).contiguous()
     out = torch.empty(t.shape[0], dim, device=t.device, dtype=dtype)
-    _lib.check(_fn(lib, "lr_timestep_embedding", dtype)(_p(t), t.shape[0], dim, _p(out), _stream()), "timestep_embedding")
+    _lib.check(_fn(lib, name, dtype)(_p(t), t.shape[0], dim, _p(out), _stream()), "timestep_embedding")
     return out
 
 
@@ -853,3 +855,47 @@ def ddim_cfg_step(x, eps, noise, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus
                                     x.numel(), float(cfg_scale), float(a_t), float(a_prev), float(sigma_t),
                                     float(sqrt_one_minus_at), _stream()), "ddim_cfg_step")
     return x_prev, pred
+
+
+def _eps16(eps):
+    return torch.bfloat16 if eps.dtype == torch.bfloat16 else torch.float16
+
+
+def plms_cfg_step(x, eps, hist, weights, divisor, cfg_scale, a_t, a_prev, sqrt_one_minus_at, write_e=True):
+    """One PLMS update (sigma = 0).  x [B,...] fp32; eps [2B,...] fp16|bf16|fp32 (uncond first); hist: up to 3 fp32 tensors
+    like x, newest first; weights: len(hist) + 1 integer weights, divisor their common denominator.
+    Returns (x_prev, pred_x0, e): e is this evaluation's CFG-combined eps in fp32 (None unless write_e)."""
+    lib = _lib.load()
+    assert x.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous()
+    assert eps.numel() == 2 * x.numel() and eps.dtype in (torch.float16, torch.bfloat16, torch.float32)
+    assert len(hist) <= 3 and len(weights) == len(hist) + 1
+    for h in hist:
+        assert h.dtype == torch.float32 and h.is_contiguous() and h.numel() == x.numel() and h.device == x.device
+    ptrs = (ctypes.c_void_p * 3)(*[h.data_ptr() for h in hist], *([None] * (3 - len(hist))))
+    w = (ctypes.c_float * 4)(*[float(w_) for w_ in weights], *([0.0] * (4 - len(weights))))
+    x_prev = torch.empty_like(x)
+    pred = torch.empty_like(x)
+    e = torch.empty_like(x) if write_e else None
+    _lib.check(_fn(lib, "lr_plms_cfg_step", _eps16(eps))(_p(x), _p(eps), int(eps.dtype == torch.float32), ctypes.addressof(ptrs),
+                                                         len(hist), ctypes.addressof(w),
+                                                         float(divisor), _p(e), _p(x_prev), _p(pred), x.numel(), float(cfg_scale),
+                                                         float(a_t), float(a_prev), float(sqrt_one_minus_at), _stream()),
+               "plms_cfg_step")
+    return x_prev, pred, e
+
+
+def dpmpp_cfg_step(x, eps, x0_prev, cfg_scale, sigma_s, alpha_s, ratio, c, c_half=0.0, inv_r0=0.0):
+    """One DPM-Solver++ multistep update: order 1 when x0_prev is None, else order 2.  x [B,...] fp32; eps [2B,...]
+    fp16|bf16|fp32 (uncond first); x0_prev fp32 like x.  Returns (x_next, x0) -- x0 is this step's data prediction."""
+    lib = _lib.load()
+    assert x.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous()
+    assert eps.numel() == 2 * x.numel() and eps.dtype in (torch.float16, torch.bfloat16, torch.float32)
+    if x0_prev is not None:
+        assert x0_prev.dtype == torch.float32 and x0_prev.is_contiguous() and x0_prev.numel() == x.numel()
+    x_next = torch.empty_like(x)
+    x0 = torch.empty_like(x)
+    _lib.check(_fn(lib, "lr_dpmpp_cfg_step", _eps16(eps))(_p(x), _p(eps), int(eps.dtype == torch.float32), _p(x0_prev), _p(x0),
+                                                          _p(x_next), x.numel(), float(cfg_scale), float(sigma_s), float(alpha_s),
+                                                          float(ratio), float(c), float(c_half), float(inv_r0), _stream()),
+               "dpmpp_cfg_step")
+    return x_next, x0

@@ -93,6 +93,9 @@ def main():
     ap.add_argument("--metric_output", type=str, default="metric_outputs")
     ap.add_argument("--ngpu", type=int, default=1)       # parsed but unused, like the reference (62, 99)
     ap.add_argument("--fp16", action="store_true")       # idem (63)
+    ap.add_argument("--sampler", type=str, default="ddim", choices=["ddim", "plms", "dpm_solver"],
+                    help="plms needs --eta 0; dpm_solver ignores eta (reference dpm_solver/sampler.py)")
+    ap.add_argument("--steps", type=int, default=50, help="sampler steps (the reference's log_images default: 50)")
     ap.add_argument("--synthetic", type=int, default=0)
     ap.add_argument("--pretrained", type=str, default="pretrained_models/512-inpainting-ema.ckpt")
     ap.add_argument("--lpips_weights", type=str, default=None, help="comma-separated state-dict files for LPIPS(alex)")
@@ -132,7 +135,8 @@ def main():
     with torch.no_grad(), torch.autocast("cuda"):
         for bi, batch in enumerate(batches):
             batch = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in batch.items()}
-            out = model.log_images(batch, batch["image"].shape[0], unconditional_guidance_scale=a.cfg, ddim_eta=a.eta)
+            out = model.log_images(batch, batch["image"].shape[0], unconditional_guidance_scale=a.cfg, ddim_eta=a.eta,
+                                       ddim_steps=a.steps, **({} if a.sampler == "ddim" else {"sampler": a.sampler}))
             if not torch.isfinite(out["pred"]).all():
                 bad = (~torch.isfinite(out["pred"])).float().mean().item()
                 print(f"WARNING: {100 * bad:.2f} % of the decoded prediction is not finite (batch {bi})")
