@@ -404,6 +404,35 @@ int lr_dpmpp_cfg_step(const float* x, const void* eps, int eps_is_f32, const flo
                       int64_t numel, float cfg_scale, float sigma_s, float alpha_s, float ratio, float c, float c_half,
                       float inv_r0, lr_stream_t s);
 
+/* ---- DDIM inversion step: classifier-free guidance + x_next = c1 x + c2 e (ABI 28) ---------------------------------
+ * replaces: DDIMSampler.encode after the model call (ddim.py:411-421): e = e_u + s (e_c - e_u) rounded in the eps dtype exactly
+ *           as lr_ddim_cfg_step; x_next = c1 x + c2 e, two products and an add, each rounded in fp32 (no fused multiply-add).
+ *           c2 is a 0-dim tensor in the reference, cast to the dtype of eps: with 16-bit eps, c2 and the product c2 e are
+ *           rounded to the eps dtype (pass c2 already rounded from float64 to that dtype, so it is not rounded twice).
+ * c1 = sqrt(a_next / a), c2 = sqrt(a_next) (sqrt(1/a_next - 1) - sqrt(1/a - 1)): host scalars formed in the reference's dtype
+ * chain (a_next fp32, a float64), rounded to fp32.  x, x_next: fp32 [numel]; eps [2 numel], uncond half first.  A scale-1 call
+ * (no unconditional pass) passes the single eps twice. */
+int lr_ddim_inv_cfg_step(const float* x, const void* eps, int eps_is_f32, float* x_next, int64_t numel, float cfg_scale,
+                         float c1, float c2, lr_stream_t s);
+
+/* ---- three-way guidance + DDIM update of StructureDDIMSampler (ABI 28) ----------------------------------------------
+ * replaces: p_sample_ddim_guide (ddim.py:605-607 combine, 623-647 update): eps [3 numel] = uncond, cond, cond_simple;
+ *           e = e_u + s ((w e_c + (1 - w) e_s) - e_u), each operation rounded in the eps dtype; then pred_x0 / x_prev as
+ *           lr_ddim_cfg_step (op by op in fp32).  one_minus_cond_weight: (1 - w) formed in double by the caller, as python does.
+ * noise may be NULL (sigma = 0).  Coefficients are host scalars. */
+int lr_ddim_cfg3_step(const float* x, const void* eps, int eps_is_f32, const float* noise, float* x_prev, float* pred_x0,
+                      int64_t numel, float cfg_scale, float cond_weight, float one_minus_cond_weight, float a_t, float a_prev,
+                      float sigma_t, float sqrt_one_minus_at, lr_stream_t s);
+
+/* ---- DDIM forward noising with a per-sample step (ABI 28) ----------------------------------------------------------
+ * replaces: DDIMSampler.stochastic_encode (ddim.py:436-449): out[b] = sa[b] x0[b] + s1ma[b] noise[b] with
+ *           sa = sqrt(ddim_alphas)[t[b]], s1ma = ddim_sqrt_one_minus_alphas[t[b]] (extract_into_tensor), all fp32.
+ * x0, noise, out: fp32 [B][per_sample]; sa, s1ma: HOST arrays of B floats, passed by value -- B <= LR_Q_SAMPLE_MAX_B per call
+ * (larger batches: one call per chunk of samples). */
+#define LR_Q_SAMPLE_MAX_B 32
+int lr_ddim_q_sample(const float* x0, const float* noise, float* out, int B, int64_t per_sample, const float* sa,
+                     const float* s1ma, lr_stream_t s);
+
 /* ==== backward of the same operators (training with frozen weights: input gradients only) =========================
  * replaces: what torch.autograd derives for the reference's modules under `loss.backward()` (train_inpainting.py:141 ->
  *           LatentDiffusion.p_losses, ldm/models/diffusion/ddpm.py:900-935), recomputed per block by
@@ -500,6 +529,11 @@ int lr_plms_cfg_step_bf16(const float* x, const void* eps, int eps_is_f32, const
     float sqrt_one_minus_at, lr_stream_t s);
 int lr_dpmpp_cfg_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* x0_prev, float* x0_out, float* x_next,
     int64_t numel, float cfg_scale, float sigma_s, float alpha_s, float ratio, float c, float c_half, float inv_r0, lr_stream_t s);
+int lr_ddim_inv_cfg_step_bf16(const float* x, const void* eps, int eps_is_f32, float* x_next, int64_t numel, float cfg_scale,
+    float c1, float c2, lr_stream_t s);
+int lr_ddim_cfg3_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* noise, float* x_prev, float* pred_x0,
+    int64_t numel, float cfg_scale, float cond_weight, float one_minus_cond_weight, float a_t, float a_prev, float sigma_t,
+    float sqrt_one_minus_at, lr_stream_t s);
 int lr_geglu_fwd_bf16(const lr_half* pre, lr_half* out, int M, int H, lr_stream_t s);
 int lr_geglu_bwd_bf16(const lr_half* pre, const lr_half* dy, lr_half* dpre, int M, int H, lr_stream_t s);
 int lr_sumpool2x2_bf16(const lr_half* x, lr_half* y, int N, int H, int W, int C, lr_stream_t s);

@@ -350,6 +350,109 @@ __global__ void dpmpp_cfg_step_kernel(const float* __restrict__ x, const EpsT* _
   }
 }
 
+// DDIM inversion (DDIMSampler.encode, ddim.py:411-421): x_next = c1 x + c2 e.  c1, c2 are 0-dim float64 tensors in the
+// reference, cast to the dtype of the tensor they multiply: with fp16 / bf16 eps, c2 is rounded to that dtype and so is the
+// product c2 e; c1 x and the sum are fp32.
+template <int V, typename EpsT, typename T>
+__global__ void ddim_inv_cfg_step_kernel(const float* __restrict__ x, const EpsT* __restrict__ eps, float* __restrict__ x_next,
+                                         long long numel, float scale, float c1, float c2) {
+#pragma clang fp contract(off)
+  const long long groups = numel / V;
+  for (long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
+    const long long i = g * V;
+    float eu[V], ec[V], xv[V], xn[V];
+    ld_eps<V, EpsT>(eps, i, eu);
+    ld_eps<V, EpsT>(eps, numel + i, ec);
+    ld_f32<V>(x, i, xv);
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      const float e = cfg_combine<EpsT, T>(eu[k], ec[k], scale);
+      const float a = c1 * xv[k];
+      float b;
+      if constexpr (sizeof(EpsT) == 2) b = (float)(T)((float)(T)c2 * e);
+      else b = c2 * e;
+      xn[k] = a + b;
+    }
+    st_f32<V>(x_next, i, xn);
+  }
+}
+
+// Three-way guidance of StructureDDIMSampler.p_sample_ddim_guide (ddim.py:605-607), eps [3 numel] = uncond, cond, cond_simple:
+// e = e_u + s ((w e_c + (1 - w) e_s) - e_u), every operation rounded in the eps dtype; then the DDIM update of ddim.py:623-647
+// (pred_x0 = (x - sqrt(1 - a_t) e) / sqrt(a_t), x_prev = sqrt(a_prev) pred_x0 + dir_coef e + sigma noise) in fp32.
+// The fp32 product of an fp32 scalar and a 16-bit value, as a value: torch rounds it to fp32 first, then to the 16-bit dtype.
+// Without the empty asm the compiler fuses multiply + narrowing into one v_fma_mix (a single rounding to 16 bits), which differs
+// from the reference in the last 16-bit place whenever the scalar is not exactly representable in a few bits (w = 0.7).
+__device__ __forceinline__ float f32_rounded(float v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
+template <typename EpsT, typename T>
+__device__ __forceinline__ float cfg3_combine(float eu, float ec, float es, float scale, float w, float w1m) {
+#pragma clang fp contract(off)
+  if constexpr (sizeof(EpsT) == 2) {
+    const T a = (T)f32_rounded(w * ec);
+    const T b = (T)f32_rounded(w1m * es);
+    const T m = (T)((float)a + (float)b);
+    const T d = (T)((float)m - eu);
+    const T sd = (T)f32_rounded(scale * (float)d);
+    return (float)(T)(eu + (float)sd);
+  } else {
+    return eu + scale * ((w * ec + w1m * es) - eu);
+  }
+}
+
+template <int V, typename EpsT, typename T>
+__global__ void ddim_cfg3_step_kernel(const float* __restrict__ x, const EpsT* __restrict__ eps, const float* __restrict__ noise,
+                                      float* __restrict__ x_prev, float* __restrict__ pred_x0, long long numel, float scale,
+                                      float w, float w1m, float sqrt_at, float sqrt_1m_at, float sqrt_aprev, float dir_coef,
+                                      float sigma) {
+#pragma clang fp contract(off)
+  const long long groups = numel / V;
+  for (long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
+    const long long i = g * V;
+    float eu[V], ec[V], es[V], xv[V], nz[V], p0[V], xp[V];
+    ld_eps<V, EpsT>(eps, i, eu);
+    ld_eps<V, EpsT>(eps, numel + i, ec);
+    ld_eps<V, EpsT>(eps, 2 * numel + i, es);
+    ld_f32<V>(x, i, xv);
+    if (noise) ld_f32<V>(noise, i, nz);
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      const float e = cfg3_combine<EpsT, T>(eu[k], ec[k], es[k], scale, w, w1m);
+      p0[k] = (xv[k] - sqrt_1m_at * e) / sqrt_at;
+      float v = sqrt_aprev * p0[k] + dir_coef * e;
+      if (noise) v = v + sigma * nz[k];
+      xp[k] = v;
+    }
+    st_f32<V>(pred_x0, i, p0);
+    st_f32<V>(x_prev, i, xp);
+  }
+}
+
+// DDIMSampler.stochastic_encode (ddim.py:436-449): out = sa[b] x0 + s1ma[b] noise, sample b = blockIdx.y; the coefficient pairs
+// are kernel arguments (at most LR_Q_SAMPLE_MAX_B samples per launch).
+struct QSampleCoefs { float sa[LR_Q_SAMPLE_MAX_B]; float s1ma[LR_Q_SAMPLE_MAX_B]; };
+
+template <int V>
+__global__ void ddim_q_sample_kernel(const float* __restrict__ x0, const float* __restrict__ noise, float* __restrict__ out,
+                                     long long per_sample, const QSampleCoefs C) {
+#pragma clang fp contract(off)
+  const long long base = (long long)blockIdx.y * per_sample;
+  const float sa = C.sa[blockIdx.y], s1ma = C.s1ma[blockIdx.y];
+  const long long groups = per_sample / V;
+  for (long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
+    const long long i = base + g * V;
+    float xv[V], nv[V], o[V];
+    ld_f32<V>(x0, i, xv);
+    ld_f32<V>(noise, i, nv);
+#pragma unroll
+    for (int k = 0; k < V; ++k) o[k] = sa * xv[k] + s1ma * nv[k];
+    st_f32<V>(out, i, o);
+  }
+}
+
 static inline bool aligned16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
 
 static inline int grid_for(long long total, int block, int cap = 4096) {
@@ -359,7 +462,7 @@ static inline int grid_for(long long total, int block, int cap = 4096) {
   return (int)g;
 }
 
-extern "C" int lr_abi_version(void) { return 27; }
+extern "C" int lr_abi_version(void) { return 28; }
 
 #ifdef LR_DEV_VARIANTS
 // developer build only: name -> value table behind LR_DEV (common.h); set through lr_dev_set by the Python front end
@@ -553,6 +656,76 @@ static int lr_dpmpp_cfg_step_t(const float* x, const void* eps, int eps_is_f32, 
   return lr_launch_status();
 }
 
+template <int V, typename EpsT, typename T>
+static void launch_ddim_inv(const float* x, const void* eps, float* x_next, long long numel, float scale, float c1, float c2,
+                            hipStream_t s) {
+  hipLaunchKernelGGL((ddim_inv_cfg_step_kernel<V, EpsT, T>), dim3(grid_for(numel / V, 256)), dim3(256), 0, s, x,
+                     (const EpsT*)eps, x_next, numel, scale, c1, c2);
+}
+
+template <typename T>
+static int lr_ddim_inv_cfg_step_t(const float* x, const void* eps, int eps_is_f32, float* x_next, int64_t numel, float cfg_scale,
+                                  float c1, float c2, lr_stream_t s) {
+  if (!x || !eps || !x_next || numel <= 0) return LR_E_ARG;
+  const bool vec = numel % 4 == 0 && aligned16(x) && aligned16(x_next) && ((uintptr_t)eps & (eps_is_f32 ? 15 : 7)) == 0;
+  hipStream_t st = (hipStream_t)s;
+  if (eps_is_f32) {
+    if (vec) launch_ddim_inv<4, float, T>(x, eps, x_next, numel, cfg_scale, c1, c2, st);
+    else launch_ddim_inv<1, float, T>(x, eps, x_next, numel, cfg_scale, c1, c2, st);
+  } else {
+    if (vec) launch_ddim_inv<4, T, T>(x, eps, x_next, numel, cfg_scale, c1, c2, st);
+    else launch_ddim_inv<1, T, T>(x, eps, x_next, numel, cfg_scale, c1, c2, st);
+  }
+  return lr_launch_status();
+}
+
+template <int V, typename EpsT, typename T>
+static void launch_ddim_cfg3(const float* x, const void* eps, const float* noise, float* x_prev, float* pred_x0, long long numel,
+                             float scale, float w, float w1m, float sqrt_at, float sqrt_1m_at, float sqrt_aprev, float dir_coef,
+                             float sigma, hipStream_t s) {
+  hipLaunchKernelGGL((ddim_cfg3_step_kernel<V, EpsT, T>), dim3(grid_for(numel / V, 256)), dim3(256), 0, s, x, (const EpsT*)eps,
+                     noise, x_prev, pred_x0, numel, scale, w, w1m, sqrt_at, sqrt_1m_at, sqrt_aprev, dir_coef, sigma);
+}
+
+template <typename T>
+static int lr_ddim_cfg3_step_t(const float* x, const void* eps, int eps_is_f32, const float* noise, float* x_prev, float* pred_x0,
+                               int64_t numel, float cfg_scale, float cond_weight, float one_minus_cond_weight, float a_t,
+                               float a_prev, float sigma_t, float sqrt_one_minus_at, lr_stream_t s) {
+  if (!x || !eps || !x_prev || !pred_x0 || numel <= 0) return LR_E_ARG;
+  // same fp32 scalar arithmetic as the reference's [b,1,1,1] fp32 tensors (ddim.py:623-645), as lr_ddim_cfg_step
+  const float sqrt_at = sqrtf(a_t);
+  const float sqrt_aprev = sqrtf(a_prev);
+  const float dir_coef = sqrtf(1.0f - a_prev - sigma_t * sigma_t);
+  const bool vec = numel % 4 == 0 && aligned16(x) && aligned16(noise) && aligned16(x_prev) && aligned16(pred_x0) &&
+                   ((uintptr_t)eps & (eps_is_f32 ? 15 : 7)) == 0;
+  hipStream_t st = (hipStream_t)s;
+  const float w = cond_weight, w1m = one_minus_cond_weight;
+  if (eps_is_f32) {
+    if (vec) launch_ddim_cfg3<4, float, T>(x, eps, noise, x_prev, pred_x0, numel, cfg_scale, w, w1m, sqrt_at, sqrt_one_minus_at, sqrt_aprev, dir_coef, sigma_t, st);
+    else launch_ddim_cfg3<1, float, T>(x, eps, noise, x_prev, pred_x0, numel, cfg_scale, w, w1m, sqrt_at, sqrt_one_minus_at, sqrt_aprev, dir_coef, sigma_t, st);
+  } else {
+    if (vec) launch_ddim_cfg3<4, T, T>(x, eps, noise, x_prev, pred_x0, numel, cfg_scale, w, w1m, sqrt_at, sqrt_one_minus_at, sqrt_aprev, dir_coef, sigma_t, st);
+    else launch_ddim_cfg3<1, T, T>(x, eps, noise, x_prev, pred_x0, numel, cfg_scale, w, w1m, sqrt_at, sqrt_one_minus_at, sqrt_aprev, dir_coef, sigma_t, st);
+  }
+  return lr_launch_status();
+}
+
+extern "C" int lr_ddim_q_sample(const float* x0, const float* noise, float* out, int B, int64_t per_sample, const float* sa,
+                                const float* s1ma, lr_stream_t s) {
+  if (!x0 || !noise || !out || !sa || !s1ma || B <= 0 || B > LR_Q_SAMPLE_MAX_B || per_sample <= 0) return LR_E_ARG;
+  QSampleCoefs C{};
+  for (int b = 0; b < B; ++b) {
+    C.sa[b] = sa[b];
+    C.s1ma[b] = s1ma[b];
+  }
+  const bool vec = per_sample % 4 == 0 && aligned16(x0) && aligned16(noise) && aligned16(out);
+  const int V = vec ? 4 : 1;
+  dim3 grid(grid_for(per_sample / V, 256, (4096 + B - 1) / B), B), block(256);
+  if (vec) hipLaunchKernelGGL(ddim_q_sample_kernel<4>, grid, block, 0, (hipStream_t)s, x0, noise, out, (long long)per_sample, C);
+  else hipLaunchKernelGGL(ddim_q_sample_kernel<1>, grid, block, 0, (hipStream_t)s, x0, noise, out, (long long)per_sample, C);
+  return lr_launch_status();
+}
+
 // =====================================================================================================================
 // Backward helpers (training with frozen weights)
 // =====================================================================================================================
@@ -714,6 +887,10 @@ extern "C" int lr_plms_cfg_step(const float* x, const void* eps, int eps_is_f32,
 extern "C" int lr_plms_cfg_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* const* hist, int n_hist, const float* weights, float divisor, float* e_out, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float a_t, float a_prev, float sqrt_one_minus_at, lr_stream_t s) { return lr_plms_cfg_step_t<bf16>(x, eps, eps_is_f32, hist, n_hist, weights, divisor, e_out, x_prev, pred_x0, numel, cfg_scale, a_t, a_prev, sqrt_one_minus_at, s); }
 extern "C" int lr_dpmpp_cfg_step(const float* x, const void* eps, int eps_is_f32, const float* x0_prev, float* x0_out, float* x_next, int64_t numel, float cfg_scale, float sigma_s, float alpha_s, float ratio, float c, float c_half, float inv_r0, lr_stream_t s) { return lr_dpmpp_cfg_step_t<f16>(x, eps, eps_is_f32, x0_prev, x0_out, x_next, numel, cfg_scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0, s); }
 extern "C" int lr_dpmpp_cfg_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* x0_prev, float* x0_out, float* x_next, int64_t numel, float cfg_scale, float sigma_s, float alpha_s, float ratio, float c, float c_half, float inv_r0, lr_stream_t s) { return lr_dpmpp_cfg_step_t<bf16>(x, eps, eps_is_f32, x0_prev, x0_out, x_next, numel, cfg_scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0, s); }
+extern "C" int lr_ddim_inv_cfg_step(const float* x, const void* eps, int eps_is_f32, float* x_next, int64_t numel, float cfg_scale, float c1, float c2, lr_stream_t s) { return lr_ddim_inv_cfg_step_t<f16>(x, eps, eps_is_f32, x_next, numel, cfg_scale, c1, c2, s); }
+extern "C" int lr_ddim_inv_cfg_step_bf16(const float* x, const void* eps, int eps_is_f32, float* x_next, int64_t numel, float cfg_scale, float c1, float c2, lr_stream_t s) { return lr_ddim_inv_cfg_step_t<bf16>(x, eps, eps_is_f32, x_next, numel, cfg_scale, c1, c2, s); }
+extern "C" int lr_ddim_cfg3_step(const float* x, const void* eps, int eps_is_f32, const float* noise, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float cond_weight, float one_minus_cond_weight, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, lr_stream_t s) { return lr_ddim_cfg3_step_t<f16>(x, eps, eps_is_f32, noise, x_prev, pred_x0, numel, cfg_scale, cond_weight, one_minus_cond_weight, a_t, a_prev, sigma_t, sqrt_one_minus_at, s); }
+extern "C" int lr_ddim_cfg3_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* noise, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float cond_weight, float one_minus_cond_weight, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, lr_stream_t s) { return lr_ddim_cfg3_step_t<bf16>(x, eps, eps_is_f32, noise, x_prev, pred_x0, numel, cfg_scale, cond_weight, one_minus_cond_weight, a_t, a_prev, sigma_t, sqrt_one_minus_at, s); }
 extern "C" int lr_geglu_fwd(const lr_half* pre, lr_half* out, int M, int H, lr_stream_t s) { return lr_geglu_fwd_t<f16>(pre, out, M, H, s); }
 extern "C" int lr_geglu_fwd_bf16(const lr_half* pre, lr_half* out, int M, int H, lr_stream_t s) { return lr_geglu_fwd_t<bf16>(pre, out, M, H, s); }
 extern "C" int lr_geglu_bwd(const lr_half* pre, const lr_half* dy, lr_half* dpre, int M, int H, lr_stream_t s) { return lr_geglu_bwd_t<f16>(pre, dy, dpre, M, H, s); }

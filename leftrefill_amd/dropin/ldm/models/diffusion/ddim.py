@@ -9,12 +9,33 @@ Differences by design (results identical):
     device tensors per step (ddim.py:359-362), i.e. four device->host syncs per step;
   * the CFG combine + x0 prediction + x_{t-1} update (ddim.py:343-381, ~15 elementwise kernels) is ONE HIP kernel
     (lr_ddim_cfg_step); the UNet step itself is one hipGraph replay.
+
+Also served: `encode` (DDIM inversion, one lr_ddim_inv_cfg_step per evaluation), `stochastic_encode` (lr_ddim_q_sample), `decode`
+(ddim.py:389-470) and LeftRefill's `StructureDDIMSampler` (ddim.py:474-647: three-way guidance over [uncond; cond; cond_simple]
+for index >= Tm, one lr_ddim_cfg3_step per evaluation, then two-way guidance with cond_simple).  All of them accept dict
+conditioning as well as tensors.
 """
 import numpy as np
 import torch
 
 from leftrefill_amd import ops
 from ldm.modules.diffusionmodules.util import make_ddim_sampling_parameters, make_ddim_timesteps, noise_like
+
+
+def _unsupported(who, what):
+    raise NotImplementedError(f"{who}: {what} is not supported by this build (eps-parameterisation, uniform DDIM steps, dict or "
+                              "tensor conditioning)")
+
+
+def _cat_cond(parts):
+    """torch.cat of conditionings along the batch, in order: dict (of tensors or lists of tensors) or tensor."""
+    c = parts[-1]
+    if isinstance(c, dict):
+        return {k: ([torch.cat([p[k][i] for p in parts]) for i in range(len(c[k]))] if isinstance(c[k], list)
+                    else torch.cat([p[k] for p in parts])) for k in c}
+    if isinstance(c, torch.Tensor):
+        return torch.cat(parts)
+    raise NotImplementedError(f"conditioning of type {type(c).__name__} is not supported by this build (dict or tensor)")
 
 
 class CFGModelEval(object):
@@ -88,6 +109,24 @@ class CFGModelEval(object):
             if shared:
                 unet.cfg_shared_prefix = False
         return eps.contiguous(), scale
+
+    # three-way guidance of StructureDDIMSampler: the [uncond; cond; cond_simple] batch, built once per sampling like the CFG pair
+    def _prepare_cfg3_inputs(self, c, c_simple, uc, scale):
+        self._cfg3_cache = None
+        if uc is None or scale == 1. or c_simple is None:
+            return
+        self._cfg3_cache = (id(c), id(c_simple), id(uc), _cat_cond([uc, c, c_simple]))
+
+    def _cfg3_eps(self, x, c, c_simple, t, uc):
+        """One model evaluation on the [uncond; cond; cond_simple] batch (one UNet call at 3B, ddim.py:587-604) -> eps [3B, ...]
+        contiguous.  No shared prefix: the three thirds are not two equal halves (the flag stays two-way only)."""
+        cache = getattr(self, "_cfg3_cache", None)
+        if cache is not None and cache[:3] == (id(c), id(c_simple), id(uc)):
+            c_in = cache[3]
+        else:
+            c_in = _cat_cond([uc, c, c_simple])
+        eps = self.model.apply_model(torch.cat([x] * 3), torch.cat([t] * 3), c_in)
+        return eps.contiguous()
 
 
 class DDIMSampler(CFGModelEval):
@@ -283,3 +322,258 @@ class DDIMSampler(CFGModelEval):
         x_prev, pred_x0 = ops.ddim_cfg_step(x, eps, noise, scale, self.ddim_alphas[index], self.ddim_alphas_prev[index],
                                             sigma * float(temperature), self.ddim_sqrt_one_minus_alphas[index])
         return x_prev, pred_x0
+
+    def _check_extras(self, who, use_original_steps=False, unconditional_conditioning=None, scale=1.):
+        if use_original_steps:
+            _unsupported(who, "use_original_steps")
+        if self.model.parameterization != "eps":
+            _unsupported(who, f"parameterization {self.model.parameterization!r}")
+        if unconditional_conditioning is not None and scale != 1.:
+            from leftrefill_amd import dist as lrd
+            if lrd.split_cfg_active():
+                _unsupported(who, "split classifier-free guidance across ranks")
+
+    def encode_coefficients(self, num_steps):
+        """(c1, c2) of the first num_steps inversion steps, float64: the reference's 0-dim results (ddim.py:398-400, 417-419), formed in
+        its dtype chain -- alphas_next = ddim_alphas (fp32), alphas = torch.tensor(ddim_alphas_prev) (float64).  The kernel applies
+        them to fp32 tensors, i.e. rounded to fp32."""
+        an = torch.from_numpy(np.asarray(self.ddim_alphas[:num_steps], dtype=np.float32))
+        a = torch.tensor(self.ddim_alphas_prev[:num_steps])
+        c1 = np.empty(num_steps, dtype=np.float64)
+        c2 = np.empty(num_steps, dtype=np.float64)
+        for i in range(num_steps):
+            c1[i] = (an[i] / a[i]).sqrt().item()
+            c2[i] = (an[i].sqrt() * ((1 / an[i] - 1).sqrt() - (1 / a[i] - 1).sqrt())).item()
+        return c1, c2
+
+    @torch.no_grad()
+    def encode(self, x0, c, t_enc, use_original_steps=False, return_intermediates=None, unconditional_guidance_scale=1.0,
+               unconditional_conditioning=None, callback=None):
+        """Deterministic DDIM inversion over the first t_enc DDIM steps (ddim.py:389-433): x_next = c1 x + c2 e per step, with
+        classifier-free guidance when unconditional_guidance_scale != 1.  Returns (x_next, {'x_encoded', 'intermediate_steps'
+        [, 'intermediates']}) with the reference's intermediate-selection rule.
+
+        The model is fed t = i, the LOOP INDEX 0..t_enc-1 (ddim.py:407), not ddim_timesteps[i]: an upstream quirk that this drop-in
+        reproduces so that it computes what the reference computes.  Each evaluation is one replay of the captured UNet step
+        (the graph DDIM captured, for the same batch and conditioning) and one lr_ddim_inv_cfg_step."""
+        scale = float(unconditional_guidance_scale)
+        self._check_extras("DDIMSampler.encode", use_original_steps, unconditional_conditioning, scale)
+        num_reference_steps = self.ddim_timesteps.shape[0]
+        assert t_enc <= num_reference_steps
+        num_steps = t_enc
+        c1, c2 = self.encode_coefficients(num_steps)
+        uc = None
+        if scale != 1.:
+            assert unconditional_conditioning is not None
+            uc = unconditional_conditioning
+        x_next = x0
+        intermediates = []
+        inter_steps = []
+        self._prepare_cfg_inputs(c, uc, scale)
+        self._prepare_timesteps(range(num_steps))
+        try:
+            for i in range(num_steps):
+                t = torch.full((x0.shape[0],), i, device=x0.device, dtype=torch.long)
+                x_in = x_next.float().contiguous()
+                self._step_hint(i)
+                try:
+                    eps, sc = self._cfg_eps(x_in, c, t, uc, scale)
+                finally:
+                    self._step_hint(None)
+                x_next = ops.ddim_inv_cfg_step(x_in, eps, sc, c1[i], c2[i])
+                if return_intermediates and i % (num_steps // return_intermediates) == 0 and i < num_steps - 1:
+                    intermediates.append(x_next)
+                    inter_steps.append(i)
+                elif return_intermediates and i >= num_steps - 2:
+                    intermediates.append(x_next)
+                    inter_steps.append(i)
+                if callback:
+                    callback(i)
+        finally:
+            self._cfg_cache = None
+        out = {'x_encoded': x_next, 'intermediate_steps': inter_steps}
+        if return_intermediates:
+            out.update({'intermediates': intermediates})
+        return x_next, out
+
+    def q_sample_coefficients(self, t):
+        """(sqrt(ddim_alphas)[t], ddim_sqrt_one_minus_alphas[t]) per sample as fp32 numpy -- what extract_into_tensor gathers in
+        stochastic_encode (ddim.py:444-449).  t: DDIM step indices (tensor or sequence); a device tensor is read back once."""
+        idx = np.asarray(t.tolist() if isinstance(t, torch.Tensor) else t, dtype=np.int64).reshape(-1)
+        sa = np.sqrt(np.asarray(self.ddim_alphas, dtype=np.float32))[idx]
+        s1ma = np.asarray(self.ddim_sqrt_one_minus_alphas, dtype=np.float32)[idx]
+        return sa, s1ma
+
+    @torch.no_grad()
+    def stochastic_encode(self, x0, t, use_original_steps=False, noise=None):
+        """Re-noise a clean latent to DDIM step t[b] of each sample (ddim.py:436-449): sqrt(a_t) x0 + sqrt(1 - a_t) noise, one
+        lr_ddim_q_sample launch.  noise=None draws randn_like(x0) like the reference."""
+        if use_original_steps:
+            _unsupported("DDIMSampler.stochastic_encode", "use_original_steps")
+        sa, s1ma = self.q_sample_coefficients(t)
+        assert sa.shape[0] == x0.shape[0], "one DDIM step index per sample"
+        if noise is None:
+            noise = torch.randn_like(x0)
+        return ops.ddim_q_sample(x0.float(), noise.float(), sa, s1ma)
+
+    @torch.no_grad()
+    def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
+               use_original_steps=False, callback=None):
+        """Denoise from DDIM step t_start (ddim.py:452-470): p_sample_ddim over ddim_timesteps[:t_start], newest first -- the same
+        per-step work as ddim_sampling (precomputed embedding rows, [uncond; cond] batch built once, one graph replay)."""
+        self._check_extras("DDIMSampler.decode", use_original_steps)
+        steps = self.ddim_timesteps[:t_start]
+        time_range = np.flip(steps)
+        total_steps = steps.shape[0]
+        x_dec = x_latent
+        self._prepare_cfg_inputs(cond, unconditional_conditioning, unconditional_guidance_scale)
+        self._prepare_timesteps(time_range)
+        try:
+            for i, step in enumerate(time_range):
+                index = total_steps - i - 1
+                ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)
+                x_dec, _ = self.p_sample_ddim(x_dec, cond, ts, index=index,
+                                              unconditional_guidance_scale=unconditional_guidance_scale,
+                                              unconditional_conditioning=unconditional_conditioning, t_host=int(step))
+                if callback:
+                    callback(i)
+        finally:
+            self._cfg_cache = None
+        return x_dec
+
+
+class StructureDDIMSampler(DDIMSampler):
+    """LeftRefill's guided sampler (reference ddim.py:474-647): for DDIM index >= Tm a three-way guidance over
+    [uncond; cond; cond_simple], e = e_u + s ((w e_c + (1 - w) e_s) - e_u) (ddim.py:607) -- one UNet call at batch 3B (its own
+    captured step) and one lr_ddim_cfg3_step; below Tm ordinary DDIM with cond_simple and a copy of the unconditional
+    conditioning.  `mask_dir` is accepted and unused, as in the reference (its only use is commented out)."""
+
+    def __init__(self, model, schedule="linear", **kwargs):
+        super().__init__(model, schedule, **kwargs)
+
+    @torch.no_grad()
+    def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
+               quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
+               corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
+               unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None, Tm=None, cond_simple=None,
+               cond_weight=None, mask_dir='right', **kwargs):
+        if isinstance(conditioning, list):       # the reference routes list conditioning to ddim_multi_sampling (no Tm)
+            return super().sample(S, batch_size, shape, conditioning=conditioning, callback=callback, img_callback=img_callback,
+                                  quantize_x0=quantize_x0, eta=eta, mask=mask, x0=x0, temperature=temperature,
+                                  noise_dropout=noise_dropout, score_corrector=score_corrector, verbose=verbose, x_T=x_T,
+                                  log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
+                                  unconditional_conditioning=unconditional_conditioning, dynamic_threshold=dynamic_threshold,
+                                  ucg_schedule=ucg_schedule)
+        if conditioning is not None and isinstance(conditioning, dict):
+            c0 = conditioning[list(conditioning.keys())[0]]
+            while isinstance(c0, list):
+                c0 = c0[0]
+            if c0.shape[0] != batch_size:
+                print(f"Warning: Got {c0.shape[0]} conditionings but batch-size is {batch_size}")
+        self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
+        C, H, W = shape
+        return self.ddim_sampling(conditioning, (batch_size, C, H, W), callback=callback, img_callback=img_callback,
+                                  quantize_denoised=quantize_x0, mask=mask, x0=x0, ddim_use_original_steps=False,
+                                  noise_dropout=noise_dropout, temperature=temperature, score_corrector=score_corrector,
+                                  corrector_kwargs=corrector_kwargs, x_T=x_T, log_every_t=log_every_t,
+                                  unconditional_guidance_scale=unconditional_guidance_scale,
+                                  unconditional_conditioning=unconditional_conditioning, dynamic_threshold=dynamic_threshold,
+                                  ucg_schedule=ucg_schedule, Tm=Tm, cond_simple=cond_simple, cond_weight=cond_weight,
+                                  mask_dir=mask_dir, **kwargs)
+
+    def _check_guide(self, use_original_steps=False, quantize_denoised=False, noise_dropout=0., score_corrector=None,
+                     dynamic_threshold=None, return_attn=False):
+        who = "StructureDDIMSampler"
+        if return_attn:
+            _unsupported(who, "return_attn (the reference's path reads an undefined att_score)")
+        if quantize_denoised or noise_dropout > 0. or score_corrector is not None or dynamic_threshold is not None:
+            _unsupported(who, "quantize_denoised / noise_dropout / score_corrector / dynamic_threshold")
+        self._check_extras(who, use_original_steps)
+
+    @torch.no_grad()
+    def ddim_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
+                      quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.,
+                      noise_dropout=0., score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.,
+                      unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None, Tm=None, cond_simple=None,
+                      cond_weight=None, mask_dir='right', **kwargs):
+        self._check_guide(ddim_use_original_steps, quantize_denoised, noise_dropout, score_corrector, dynamic_threshold,
+                          kwargs.get('return_attn', False))
+        if Tm is None or cond_simple is None or cond_weight is None:
+            raise ValueError("StructureDDIMSampler needs Tm, cond_simple and cond_weight")
+        import copy
+        device = self.model.betas.device
+        b = shape[0]
+        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
+        steps = self.ddim_timesteps
+        if timesteps is not None:
+            end = int(min(timesteps / steps.shape[0], 1) * steps.shape[0]) - 1
+            steps = steps[:end]
+        intermediates = {'x_inter': [img], 'pred_x0': [img]}
+        time_range = np.flip(steps)
+        total_steps = steps.shape[0]
+        # the second phase runs on its own copies of cond_simple and of the unconditional conditioning (ddim.py:517-518)
+        new_cond_simple = copy.deepcopy(cond_simple)
+        new_uc = copy.deepcopy(unconditional_conditioning)
+        scale = unconditional_guidance_scale
+        self._prepare_cfg3_inputs(cond, cond_simple, unconditional_conditioning, scale)
+        self._prepare_cfg_inputs(new_cond_simple, new_uc, scale)
+        self._prepare_timesteps(time_range)
+        try:
+            for i, step in enumerate(time_range):
+                index = total_steps - i - 1
+                ts = torch.full((b,), int(step), device=device, dtype=torch.long)
+                if mask is not None:
+                    assert x0 is not None
+                    img = self.model.q_sample(x0, ts) * mask + (1. - mask) * img
+                if ucg_schedule is not None:
+                    assert len(ucg_schedule) == len(time_range)
+                    scale = ucg_schedule[i]
+                if index >= Tm:
+                    img, pred_x0 = self.p_sample_ddim_guide(img, cond, cond_simple, cond_weight, ts, index=index,
+                                                            temperature=temperature, unconditional_guidance_scale=scale,
+                                                            unconditional_conditioning=unconditional_conditioning,
+                                                            t_host=int(step))
+                else:
+                    img, pred_x0 = self.p_sample_ddim(img, new_cond_simple, ts, index=index, temperature=temperature,
+                                                      unconditional_guidance_scale=scale, unconditional_conditioning=new_uc,
+                                                      t_host=int(step))
+                if callback:
+                    callback(i)
+                if img_callback:
+                    img_callback(pred_x0, i)
+                if index % log_every_t == 0 or index == total_steps - 1:
+                    intermediates['x_inter'].append(img)
+                    intermediates['pred_x0'].append(pred_x0)
+        finally:
+            self._cfg_cache = None
+            self._cfg3_cache = None
+        return img, intermediates
+
+    @torch.no_grad()
+    def p_sample_ddim_guide(self, x, c, c_simple, c_weight, t, index, repeat_noise=False, use_original_steps=False,
+                            quantize_denoised=False, temperature=1., noise_dropout=0., score_corrector=None,
+                            corrector_kwargs=None, unconditional_guidance_scale=1., unconditional_conditioning=None,
+                            dynamic_threshold=None, t_host=None, **kwargs):
+        """One three-way guided DDIM step (ddim.py:579-647).  Without an unconditional pass (or at scale 1) the model sees c alone
+        (ddim.py:585-586) and the step is lr_ddim_cfg_step's.  t_host: as in p_sample_ddim."""
+        self._check_guide(use_original_steps, quantize_denoised, noise_dropout, score_corrector, dynamic_threshold,
+                          kwargs.get('return_attn', False))
+        x = x.float().contiguous()
+        scale = float(unconditional_guidance_scale)
+        three = unconditional_conditioning is not None and scale != 1.
+        if three:
+            self._check_extras("StructureDDIMSampler", False, unconditional_conditioning, scale)
+        self._step_hint(t_host)
+        try:
+            if three:
+                eps = self._cfg3_eps(x, c, c_simple, t, unconditional_conditioning)
+            else:
+                eps, _ = self._cfg_eps(x, c, t, None, 1.)
+        finally:
+            self._step_hint(None)
+        noise = noise_like(x.shape, x.device, repeat_noise)      # drawn every step like the reference (ddim.py:643)
+        sigma = float(self.ddim_sigmas[index]) * float(temperature)
+        a_t, a_prev, s1 = self.ddim_alphas[index], self.ddim_alphas_prev[index], self.ddim_sqrt_one_minus_alphas[index]
+        if not three:
+            return ops.ddim_cfg_step(x, eps, noise, 1.0, a_t, a_prev, sigma, s1)
+        return ops.ddim_cfg3_step(x, eps, noise, scale, c_weight, a_t, a_prev, sigma, s1)

@@ -899,3 +899,58 @@ def dpmpp_cfg_step(x, eps, x0_prev, cfg_scale, sigma_s, alpha_s, ratio, c, c_hal
                                                           float(ratio), float(c), float(c_half), float(inv_r0), _stream()),
                "dpmpp_cfg_step")
     return x_next, x0
+
+
+def ddim_inv_cfg_step(x, eps, cfg_scale, c1, c2):
+    """One DDIM inversion step (DDIMSampler.encode): x_next = c1 x + c2 e with e = e_u + s (e_c - e_u).  x [B,...] fp32;
+    eps [2B,...] fp16|bf16|fp32 (uncond first); c1, c2: the host coefficients (python / float64 values).  Returns x_next fp32."""
+    lib = _lib.load()
+    assert x.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous()
+    assert eps.numel() == 2 * x.numel() and eps.dtype in (torch.float16, torch.bfloat16, torch.float32)
+    if eps.dtype != torch.float32:      # the reference casts the 0-dim float64 c2 to eps's dtype: round once, from float64
+        c2 = torch.tensor(float(c2), dtype=torch.float64).to(eps.dtype).item()
+    x_next = torch.empty_like(x)
+    _lib.check(_fn(lib, "lr_ddim_inv_cfg_step", _eps16(eps))(_p(x), _p(eps), int(eps.dtype == torch.float32), _p(x_next), x.numel(),
+                                                             float(cfg_scale), float(c1), float(c2), _stream()),
+               "ddim_inv_cfg_step")
+    return x_next
+
+
+def ddim_cfg3_step(x, eps, noise, cfg_scale, cond_weight, a_t, a_prev, sigma_t, sqrt_one_minus_at):
+    """Three-way guidance + DDIM update (StructureDDIMSampler.p_sample_ddim_guide).  x [B,...] fp32; eps [3B,...] fp16|bf16|fp32
+    in the order uncond, cond, cond_simple; noise fp32 like x or None.  Returns (x_prev, pred_x0) fp32."""
+    lib = _lib.load()
+    assert x.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous()
+    assert eps.numel() == 3 * x.numel() and eps.dtype in (torch.float16, torch.bfloat16, torch.float32)
+    if noise is not None:
+        noise = noise.float().contiguous()
+    x_prev = torch.empty_like(x)
+    pred = torch.empty_like(x)
+    w = float(cond_weight)
+    _lib.check(_fn(lib, "lr_ddim_cfg3_step", _eps16(eps))(_p(x), _p(eps), int(eps.dtype == torch.float32), _p(noise), _p(x_prev),
+                                                          _p(pred), x.numel(), float(cfg_scale), w, 1 - w, float(a_t),
+                                                          float(a_prev), float(sigma_t), float(sqrt_one_minus_at), _stream()),
+               "ddim_cfg3_step")
+    return x_prev, pred
+
+
+Q_SAMPLE_MAX_B = 32          # LR_Q_SAMPLE_MAX_B: coefficient pairs per launch (kernel arguments)
+
+
+def ddim_q_sample(x0, noise, sa, s1ma):
+    """out[b] = sa[b] x0[b] + s1ma[b] noise[b] (DDIMSampler.stochastic_encode).  x0, noise [B,...] fp32; sa, s1ma: B host floats
+    (the fp32 values).  One launch per Q_SAMPLE_MAX_B samples."""
+    lib = _lib.load()
+    assert x0.dtype == torch.float32 and noise.dtype == torch.float32 and x0.shape == noise.shape
+    x0, noise = x0.contiguous(), noise.contiguous()
+    B = x0.shape[0]
+    assert len(sa) == len(s1ma) == B
+    per = x0.numel() // B
+    out = torch.empty_like(x0)
+    for b0 in range(0, B, Q_SAMPLE_MAX_B):
+        n = min(Q_SAMPLE_MAX_B, B - b0)
+        a = (ctypes.c_float * n)(*[float(v) for v in sa[b0:b0 + n]])
+        s = (ctypes.c_float * n)(*[float(v) for v in s1ma[b0:b0 + n]])
+        _lib.check(lib.lr_ddim_q_sample(_p(x0[b0:b0 + n]), _p(noise[b0:b0 + n]), _p(out[b0:b0 + n]), n, per, ctypes.addressof(a),
+                                        ctypes.addressof(s), _stream()), "ddim_q_sample")
+    return out

@@ -1,4 +1,6 @@
-"""Sampler throughput at BASELINE configs[1] shapes: DDIM-50 (the bench.py metric's sampler), PLMS-50 and DPM-Solver++(2M)-20.
+"""Sampler throughput at BASELINE configs[1] shapes: DDIM-50 (the bench.py metric's sampler), PLMS-50, DPM-Solver++(2M)-20,
+StructureDDIMSampler-50 (Tm = 25: 25 three-way evaluations at batch 3B, then 25 two-way at 2B; Tm = 0: three-way throughout, the
+cost of one batch-3B evaluation) and DDIM encode-25 + decode-25 (an inversion round trip at S = 50).
 
     python tools/bench_samplers.py [--reps 3] [--out FILE]
 
@@ -21,7 +23,10 @@ if ROOT not in sys.path:
 
 import bench  # noqa: E402
 
-SAMPLERS = [("ddim", 50, 50), ("plms", 50, 51), ("dpm_solver", 20, 20)]      # (sampler, steps, UNet evaluations)
+# (sampler, steps, UNet evaluations); structure-N: StructureDDIMSampler with Tm = N, encode+decode: N steps each way at S = 50
+SAMPLERS = [("ddim", 50, 50), ("plms", 50, 51), ("dpm_solver", 20, 20), ("structure-25", 50, 50), ("structure-0", 50, 50),
+            ("encode+decode", 25, 50)]
+COND_WEIGHT = 0.7
 
 
 def run(model, batch, B, sampler, steps):
@@ -30,8 +35,22 @@ def run(model, batch, B, sampler, steps):
     uc = {"c_concat": [c_concat], "c_crossattn": [uc_cross]}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    out, _ = model.sample_log(cond=cond, batch_size=B, ddim=True, ddim_steps=steps, eta=0.0, unconditional_guidance_scale=bench.CFG,
-                              unconditional_conditioning=uc, x_T=x_T, sampler=sampler)
+    if sampler.startswith("structure-"):
+        from ldm.models.diffusion.ddim import StructureDDIMSampler
+        cs = {"c_concat": [c_concat], "c_crossattn": [c_cross.flip(0).contiguous()]}     # a context that differs from cond's
+        out, _ = StructureDDIMSampler(model).sample(steps, B, tuple(x_T.shape[1:]), cond, verbose=False, eta=0.0, x_T=x_T,
+                                                    unconditional_guidance_scale=bench.CFG, unconditional_conditioning=uc,
+                                                    Tm=int(sampler.split("-")[1]) * steps // 50, cond_simple=cs,
+                                                    cond_weight=COND_WEIGHT)
+    elif sampler == "encode+decode":
+        from ldm.models.diffusion.ddim import DDIMSampler
+        s = DDIMSampler(model)
+        s.make_schedule(2 * steps, ddim_eta=0.0, verbose=False)
+        z, _ = s.encode(x_T, cond, steps, unconditional_guidance_scale=bench.CFG, unconditional_conditioning=uc)
+        out = s.decode(z, cond, steps, unconditional_guidance_scale=bench.CFG, unconditional_conditioning=uc)
+    else:
+        out, _ = model.sample_log(cond=cond, batch_size=B, ddim=True, ddim_steps=steps, eta=0.0,
+                                  unconditional_guidance_scale=bench.CFG, unconditional_conditioning=uc, x_T=x_T, sampler=sampler)
     torch.cuda.synchronize()
     return time.perf_counter() - t0, out
 
@@ -57,7 +76,7 @@ def main():
                 times[s].append(run(model, batch, B, s, n)[0])
     res = {}
     for s, n, _ in todo:
-        evals = n + 1 if s == "plms" else n
+        evals = n + 1 if s == "plms" else (2 * n if s == "encode+decode" else n)
         sec = statistics.median(times[s])
         res[s] = {"steps": n, "unet_evals": evals, "s_per_batch": round(sec, 4), "images_per_s": round(B / sec, 3),
                   "ms_per_eval": round(1e3 * sec / evals, 3), "all_s": [round(t, 4) for t in times[s]]}
@@ -65,8 +84,12 @@ def main():
         for s in res:
             res[s]["ms_per_eval_vs_ddim"] = round(res[s]["ms_per_eval"] / res["ddim"]["ms_per_eval"], 4)
             res[s]["images_per_s_vs_ddim"] = round(res[s]["images_per_s"] / res["ddim"]["images_per_s"], 3)
+    # every structure-0 evaluation is one batch-3B UNet call (no shared prefix), every DDIM one a batch-2B call (shared prefix on)
+    ratio3 = (round(res["structure-0"]["ms_per_eval"] / res["ddim"]["ms_per_eval"], 4) if "ddim" in res and "structure-0" in res
+              else None)
     line = json.dumps({"config": "configs[1]: B=4, latent 64x128, cfg 2.5, full UNet (bench.py weights)", "reps": a.reps,
-                       "gpu": torch.cuda.get_device_name(0), "samplers": res})
+                       "gpu": torch.cuda.get_device_name(0), "samplers": res,
+                       "eval_3B_vs_2B": ratio3})
     print(line)
     if a.out:
         with open(a.out, "w") as f:
