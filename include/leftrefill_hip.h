@@ -484,6 +484,20 @@ typedef struct lr_attn_bwd_args {
   float scale;
 } lr_attn_bwd_args;
 int lr_attention_bwd_f16(const lr_attn_bwd_args* args, lr_stream_t s);
+/* ---- training of the prompt tokens through the text tower (ABI 29) -------------------------------------------------
+ * Causal self-attention (key j visible to query i iff j <= i, the tower's attn_mask): lr_attention_causal_lse_f16 is
+ * lr_attention_causal_f16 that also writes the log2-domain log-sum-exp lse [B][heads][N] fp32 (the convention of
+ * lr_attention_lse_f16); lr_attention_causal_bwd_f16 is lr_attention_bwd_f16 under the same mask (P = 0 above the diagonal, tiles
+ * wholly above it skipped).  Same argument struct; requires Nq == Nkv (else LR_E_ARG) and ld_qt == 0 (else LR_E_UNSUPPORTED, before any
+ * launch): the causal dK / dV kernel takes no query split. */
+int lr_attention_causal_lse_f16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o,
+                                int ldo, float* lse, int B, int heads, int N, float scale, lr_stream_t s);
+int lr_attention_causal_bwd_f16(const lr_attn_bwd_args* args, lr_stream_t s);
+/* plain erf-GELU (the tower's MLP, nn.GELU) over n contiguous elements, n % 8 == 0, 16-byte aligned: y = gelu(pre) with the
+ * formula of the lr_gemm_args.geglu == 2 epilogue, and dpre = dy * gelu'(pre), gelu'(x) = Phi(x) + x phi(x).  Training runs c_fc as a
+ * plain GEMM and keeps pre for the backward; inference keeps the fused epilogue. */
+int lr_gelu_fwd_f16(const lr_half* pre, lr_half* y, int64_t n, lr_stream_t s);
+int lr_gelu_bwd_f16(const lr_half* pre, const lr_half* dy, lr_half* dpre, int64_t n, lr_stream_t s);
 
 /* multi-view re-arrangement: gradient of lr_mv_gather (dseq -> dx: canvases other than 0 get zero in their right half) and
  * of lr_mv_scatter (dx -> dseq: the target slot sums the right halves of all canvases). */
@@ -551,6 +565,11 @@ int lr_attention_vt_bf16(const lr_half* q, int ldq, const lr_half* k, int ldk, c
     o, int ldo, int B, int heads, int Nq, int Nkv, float scale, lr_stream_t s);
 int lr_transpose_v_bf16(const lr_half* v, int ldv, lr_half* vt, int ld_vt, int B, int heads, int Nkv, lr_stream_t s);
 int lr_attention_bwd_bf16(const lr_attn_bwd_args* a, lr_stream_t s);
+int lr_attention_causal_lse_bf16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o,
+    int ldo, float* lse, int B, int heads, int N, float scale, lr_stream_t s);
+int lr_attention_causal_bwd_bf16(const lr_attn_bwd_args* a, lr_stream_t s);
+int lr_gelu_fwd_bf16(const lr_half* pre, lr_half* y, int64_t n, lr_stream_t s);
+int lr_gelu_bwd_bf16(const lr_half* pre, const lr_half* dy, lr_half* dpre, int64_t n, lr_stream_t s);
 int lr_xattn_block_bf16(const lr_xattn_args* args, lr_stream_t s);
 int lr_ffn_block_bf16(const lr_ffn_args* args, lr_stream_t s);
 int lr_stin_block_bf16(const lr_stin_args* args, lr_stream_t s);

@@ -9,7 +9,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 # LEFTREFILL_LIB_PATH: developer override (same-box A/B of two builds of the library)
 LIB_PATH = os.environ.get("LEFTREFILL_LIB_PATH") or os.path.join(HERE, "lib", "libleftrefill_hip.so")
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 c_void_p, c_int, c_float, c_int64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64
 
@@ -138,6 +138,11 @@ SIGNATURES = {
     "lr_attention_lse_f16": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                              c_int, c_float, c_void_p],
     "lr_attention_bwd_f16": [ctypes.POINTER(AttnBwdArgs), c_void_p],
+    "lr_attention_causal_lse_f16": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+                                    c_float, c_void_p],
+    "lr_attention_causal_bwd_f16": [ctypes.POINTER(AttnBwdArgs), c_void_p],
+    "lr_gelu_fwd_f16": [c_void_p, c_void_p, c_int64, c_void_p],
+    "lr_gelu_bwd_f16": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p],
     "lr_transpose_v_f16": [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "lr_xattn_block_f16": [ctypes.POINTER(XattnArgs), c_void_p],
     "lr_xattn_pack_vt_f16": [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p],
@@ -168,7 +173,8 @@ BF16_TWINS = ["lr_groupnorm_stats", "lr_groupnorm_apply", "lr_groupnorm_apply_n"
               "lr_dpmpp_cfg_step", "lr_ddim_inv_cfg_step", "lr_ddim_cfg3_step", "lr_geglu_fwd", "lr_geglu_bwd", "lr_sumpool2x2",
               "lr_mv_gather_bwd", "lr_mv_scatter_bwd", "lr_attention_f16", "lr_attention_causal_f16", "lr_attention_lse_f16",
               "lr_attention_vt_f16", "lr_transpose_v_f16", "lr_attention_bwd_f16", "lr_xattn_block_f16",
-              "lr_xattn_pack_vt_f16", "lr_ffn_block_f16", "lr_stin_block_f16", "lr_rowlin_f16", "lr_gn_conv_out_f16"]
+              "lr_xattn_pack_vt_f16", "lr_ffn_block_f16", "lr_stin_block_f16", "lr_rowlin_f16", "lr_gn_conv_out_f16",
+              "lr_attention_causal_lse_f16", "lr_attention_causal_bwd_f16", "lr_gelu_fwd_f16", "lr_gelu_bwd_f16"]
 
 
 def twin(name):

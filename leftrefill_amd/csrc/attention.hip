@@ -725,7 +725,8 @@ static int lr_attention_t(const lr_half* q, int ldq, const lr_half* k, int ldk, 
 
 template <typename T>
 static int lr_attention_causal_t(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv,
-                                       lr_half* o, int ldo, int B, int heads, int N, float scale, lr_stream_t s) {
+                                       lr_half* o, int ldo, int B, int heads, int N, float scale, lr_stream_t s,
+                                       float* lse = nullptr) {
   if (!q || !k || !v || !o || B <= 0 || heads <= 0 || N <= 0) return LR_E_ARG;
   if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8) return LR_E_ALIGN;
   if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) & 15) return LR_E_ALIGN;
@@ -736,7 +737,7 @@ static int lr_attention_causal_t(const lr_half* q, int ldq, const lr_half* k, in
   P.nqt = (N + ATT_QB - 1) / ATT_QB;
   P.nblocks = P.nqt * heads * B;
   P.c = scale * 1.44269504088896340736f;
-  P.lse = nullptr;
+  P.lse = lse;      // the causal instance is exact (FOLD = false) already: its log-sum-exp is what lr_attention_causal_bwd rebuilds P from
   hipLaunchKernelGGL((attention_kernel<T, 2, true>), dim3(P.nblocks), dim3(ATT_THREADS), 0, (hipStream_t)s, P);
   return lr_launch_status();
 }
@@ -747,6 +748,13 @@ static int lr_attention_lse_t(const lr_half* q, int ldq, const lr_half* k, int l
                                     lr_stream_t s) {
   if (!lse) return LR_E_ARG;
   return launch_attention<T>(q, ldq, k, ldk, v, ldv, o, ldo, B, heads, Nq, Nkv, scale, s, false, lse);
+}
+
+template <typename T>
+static int lr_attention_causal_lse_t(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv,
+                                     lr_half* o, int ldo, float* lse, int B, int heads, int N, float scale, lr_stream_t s) {
+  if (!lse) return LR_E_ARG;
+  return lr_attention_causal_t<T>(q, ldq, k, ldk, v, ldv, o, ldo, B, heads, N, scale, s, lse);
 }
 
 template <typename T>
@@ -804,6 +812,8 @@ extern "C" int lr_attention_f16(const lr_half* q, int ldq, const lr_half* k, int
 extern "C" int lr_attention_bf16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o, int ldo, int B, int heads, int Nq, int Nkv, float scale, lr_stream_t s) { return lr_attention_t<bf16>(q, ldq, k, ldk, v, ldv, o, ldo, B, heads, Nq, Nkv, scale, s); }
 extern "C" int lr_attention_causal_f16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o, int ldo, int B, int heads, int N, float scale, lr_stream_t s) { return lr_attention_causal_t<f16>(q, ldq, k, ldk, v, ldv, o, ldo, B, heads, N, scale, s); }
 extern "C" int lr_attention_causal_bf16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o, int ldo, int B, int heads, int N, float scale, lr_stream_t s) { return lr_attention_causal_t<bf16>(q, ldq, k, ldk, v, ldv, o, ldo, B, heads, N, scale, s); }
+extern "C" int lr_attention_causal_lse_f16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o, int ldo, float* lse, int B, int heads, int N, float scale, lr_stream_t s) { return lr_attention_causal_lse_t<f16>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, heads, N, scale, s); }
+extern "C" int lr_attention_causal_lse_bf16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o, int ldo, float* lse, int B, int heads, int N, float scale, lr_stream_t s) { return lr_attention_causal_lse_t<bf16>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, heads, N, scale, s); }
 extern "C" int lr_attention_lse_f16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o, int ldo, float* lse, int B, int heads, int Nq, int Nkv, float scale, lr_stream_t s) { return lr_attention_lse_t<f16>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nkv, scale, s); }
 extern "C" int lr_attention_lse_bf16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o, int ldo, float* lse, int B, int heads, int Nq, int Nkv, float scale, lr_stream_t s) { return lr_attention_lse_t<bf16>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nkv, scale, s); }
 extern "C" int lr_attention_vt_f16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* vt, int ld_vt, lr_half* o, int ldo, int B, int heads, int Nq, int Nkv, float scale, lr_stream_t s) { return lr_attention_vt_t<f16>(q, ldq, k, ldk, vt, ld_vt, o, ldo, B, heads, Nq, Nkv, scale, s); }

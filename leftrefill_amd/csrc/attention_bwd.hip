@@ -14,6 +14,10 @@
 //
 //   attn_bwd_dq_kernel : block = 4 waves x 32 queries, loops over 64-key tiles.      12 of the 28 MFMA groups
 //   attn_bwd_dkv_kernel: block = 4 waves x 32 keys,    loops over 64-query tiles.    16 of the 28 MFMA groups
+//
+// CAUSAL = true (lr_attention_causal_bwd, the text tower's attn_mask: key j visible to query i iff j <= i): P = 0 above the diagonal;
+// the dQ kernel stops after the key tile of its block's last query, the dK / dV kernel starts at the query tile of its block's first
+// key.  CAUSAL = false compiles to the code of the unmasked kernels.
 #include "common.h"
 
 #include <type_traits>
@@ -94,7 +98,7 @@ __device__ __forceinline__ vec8<T> ab_frag(const char* tile, int row, int chunk)
 // ---------------------------------------------------------------------------------------------------------------------
 // dQ: one query per lane (ql), the wave's 32 queries against every key tile.
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool CAUSAL = false>
 __global__ __launch_bounds__(AB_THREADS) void attn_bwd_dq_kernel(const AttnBwdParams<T> P) {
   __shared__ __attribute__((aligned(16))) char smem[2 * 3 * AB_TILE * 128];   // {K, V, K in the transpose-read swizzle} x 2 buffers
   const int t = threadIdx.x, lane = t & 63;
@@ -139,6 +143,8 @@ __global__ __launch_bounds__(AB_THREADS) void attn_bwd_dq_kernel(const AttnBwdPa
   const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
   const int ntiles = (P.Nkv + AB_TILE - 1) / AB_TILE;
+  // causal: key tiles past the block's last query are wholly masked -- neither run nor prefetched
+  const int tend = CAUSAL ? min(ntiles, min(qblk * 128 + 127, P.Nq - 1) / AB_TILE + 1) : ntiles;
   auto stage = [&](int buf, int tile) {
     char* base = smem + buf * (3 * AB_TILE * 128);
     ab_stage_rows(base, kp, P.ldk, tile * AB_TILE, P.Nkv, w, lane, zero);
@@ -151,7 +157,7 @@ __global__ __launch_bounds__(AB_THREADS) void attn_bwd_dq_kernel(const AttnBwdPa
   auto process = [&](int tile, auto tail_tag) {
     constexpr bool TAIL = decltype(tail_tag)::value;
     const int cur = tile & 1;
-    if (tile + 1 < ntiles) stage(cur ^ 1, tile + 1);
+    if (tile + 1 < tend) stage(cur ^ 1, tile + 1);
     const char* Ks = smem + cur * (3 * AB_TILE * 128);
     const char* Vs = Ks + AB_TILE * 128;
     const char* Kt = Ks + 2 * AB_TILE * 128;
@@ -172,7 +178,7 @@ __global__ __launch_bounds__(AB_THREADS) void attn_bwd_dq_kernel(const AttnBwdPa
         float p = __builtin_amdgcn_exp2f(fmaf(sacc[kb][r], P.c, -lse));
         if constexpr (TAIL) {
           const int key = tile * AB_TILE + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          if (key >= P.Nkv) p = 0.f;
+          if (key >= P.Nkv || (CAUSAL && key > qrow)) p = 0.f;
         }
         dsf[kb][r >> 3][r & 7] = (T)(p * (pacc[kb][r] - dsum));
       }
@@ -185,9 +191,14 @@ __global__ __launch_bounds__(AB_THREADS) void attn_bwd_dq_kernel(const AttnBwdPa
           dq[db] = lr_mfma32(ab_frag_tr<T>(Kt, tr, kb, tt, db), dsf[kb][tt], dq[db]);
     __syncthreads();
   };
-  const int nfull = P.Nkv / AB_TILE;
-  for (int tile = 0; tile < nfull; ++tile) process(tile, std::false_type{});
-  if (nfull < ntiles) process(nfull, std::true_type{});
+  if constexpr (CAUSAL) {
+    // every tile that runs takes the masked path (the text tower's N = 77 is two tiles, both on the diagonal)
+    for (int tile = 0; tile < tend; ++tile) process(tile, std::true_type{});
+  } else {
+    const int nfull = P.Nkv / AB_TILE;
+    for (int tile = 0; tile < nfull; ++tile) process(tile, std::false_type{});
+    if (nfull < ntiles) process(nfull, std::true_type{});
+  }
 
   if (qrow < P.Nq) {
     T* dst = P.dq + ((size_t)b * P.Nq + qrow) * P.lddq + h * 64;
@@ -206,7 +217,7 @@ __global__ __launch_bounds__(AB_THREADS) void attn_bwd_dq_kernel(const AttnBwdPa
 // ---------------------------------------------------------------------------------------------------------------------
 // dK, dV: one key per lane (ql), the wave's 32 keys against every query tile.
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool CAUSAL = false>
 __global__ __launch_bounds__(AB_THREADS) void attn_bwd_dkv_kernel(const AttnBwdParams<T> P) {
   extern __shared__ __attribute__((aligned(16))) char smem[];   // {Q, dO, and both again in the transpose-read swizzle} x 2 buffers (64 KB) + lse, D (1 KB)
   float (*s_lse)[AB_TILE] = reinterpret_cast<float (*)[AB_TILE]>(smem + 2 * 4 * AB_TILE * 128);
@@ -243,7 +254,8 @@ __global__ __launch_bounds__(AB_THREADS) void attn_bwd_dkv_kernel(const AttnBwdP
 
   const int ntiles_all = (P.Nq + AB_TILE - 1) / AB_TILE;
   const int t_per = (ntiles_all + P.q_splits - 1) / P.q_splits;
-  const int t0 = sp * t_per, ntiles = min(ntiles_all, t0 + t_per);      // this block runs query tiles [t0, ntiles)
+  // this block runs query tiles [t0, ntiles); causal (q_splits == 1): the query tiles before the block's first key are wholly masked
+  const int t0 = CAUSAL ? kblk * (128 / AB_TILE) : sp * t_per, ntiles = min(ntiles_all, t0 + t_per);
   auto stage = [&](int buf, int tile) {
     char* base = smem + buf * (4 * AB_TILE * 128);
     ab_stage_rows(base, qp, P.ldq, tile * AB_TILE, P.Nq, w, lane, zero);
@@ -287,7 +299,10 @@ __global__ __launch_bounds__(AB_THREADS) void attn_bwd_dkv_kernel(const AttnBwdP
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int r = g * 4 + i;
-          const float p = __builtin_amdgcn_exp2f(fmaf(sacc[qb][r], P.c, -l4[i]));
+          float p = __builtin_amdgcn_exp2f(fmaf(sacc[qb][r], P.c, -l4[i]));
+          if constexpr (CAUSAL) {
+            if (tile * AB_TILE + qb * 32 + 8 * g + 4 * hi + i < krow) p = 0.f;      // key krow is visible to queries >= krow
+          }
           pf[qb][r >> 3][r & 7] = (T)p;
           dsf[qb][r >> 3][r & 7] = (T)(p * (pacc[qb][r] - d4[i]));
         }
@@ -363,13 +378,15 @@ __global__ void attn_bwd_kv_reduce_kernel(const AttnBwdParams<T> P, int nbh) {
   *reinterpret_cast<vec4<T>*>(P.dv + ((size_t)b * P.Nkv + krow) * P.lddv + h * 64 + d4) = va;
 }
 
-template <typename T>
+template <typename T, bool CAUSAL = false>
 static int lr_attention_bwd_t(const lr_attn_bwd_args* a, lr_stream_t s) {
   if (!a || !a->q || !a->k || !a->v || !a->o || !a->dout || !a->lse || !a->dsum || !a->dq || !a->dk || !a->dv)
     return LR_E_ARG;
   if (a->B <= 0 || a->heads <= 0 || a->Nq <= 0 || a->Nkv <= 0) return LR_E_ARG;
   if ((a->ldq | a->ldk | a->ldv | a->ldo | a->lddo) % 8 || (a->lddq | a->lddk | a->lddv) % 4) return LR_E_ALIGN;
   if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o | (uintptr_t)a->dout) & 15) return LR_E_ALIGN;
+  if (CAUSAL && a->Nq != a->Nkv) return LR_E_ARG;
+  if (CAUSAL && a->ld_qt != 0) return LR_E_UNSUPPORTED;      // the causal dK / dV kernel walks every query tile of a key block itself
   AttnBwdParams<T> P;
   P.q = (const T*)a->q; P.k = (const T*)a->k; P.v = (const T*)a->v; P.o = (const T*)a->o;
   P.dout = (const T*)a->dout;
@@ -385,14 +402,14 @@ static int lr_attention_bwd_t(const lr_attn_bwd_args* a, lr_stream_t s) {
   hipStream_t st = (hipStream_t)s;
   int rc;
   P.ntile_blocks = (a->Nq + 127) / 128;
-  hipLaunchKernelGGL(attn_bwd_dq_kernel<T>, dim3(P.ntile_blocks * a->heads * a->B), dim3(AB_THREADS), 0, st, P);
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, CAUSAL>), dim3(P.ntile_blocks * a->heads * a->B), dim3(AB_THREADS), 0, st, P);
   rc = lr_launch_status();
   if (rc) return rc;
   P.ntile_blocks = (a->Nkv + 127) / 128;
   const int dkv_smem = 2 * 4 * AB_TILE * 128 + 4 * AB_TILE * (int)sizeof(float);
   static unsigned long long attr_done = 0;
   if (lr_attr_needed(&attr_done)) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, dkv_smem);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_kernel<T, CAUSAL>), hipFuncAttributeMaxDynamicSharedMemorySize, dkv_smem);
   }
   // ABI 26: `qt` / `ld_qt` of the argument struct carry the query split of this kernel (few key blocks against many queries -- the 77-key
   // cross-attention of the 64 x 128 level is 1 key block per (batch, head): 80 blocks for 256 CUs): ld_qt = number of query slices (0 / 1 =
@@ -400,7 +417,7 @@ static int lr_attention_bwd_t(const lr_attn_bwd_args* a, lr_stream_t s) {
   P.q_splits = a->ld_qt > 1 && a->qt ? a->ld_qt : 1;
   P.kv_ws = P.q_splits > 1 ? (float*)const_cast<lr_half*>(a->qt) : nullptr;
   if (P.q_splits > 64 || (P.kv_ws && ((uintptr_t)P.kv_ws & 15))) return LR_E_ARG;
-  hipLaunchKernelGGL(attn_bwd_dkv_kernel<T>, dim3(P.ntile_blocks * P.q_splits * a->heads * a->B), dim3(AB_THREADS), dkv_smem, st, P);
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, CAUSAL>), dim3(P.ntile_blocks * P.q_splits * a->heads * a->B), dim3(AB_THREADS), dkv_smem, st, P);
   rc = lr_launch_status();
   if (rc || P.q_splits == 1) return rc;
   const int nbh = a->heads * a->B;
@@ -412,3 +429,5 @@ static int lr_attention_bwd_t(const lr_attn_bwd_args* a, lr_stream_t s) {
 // ---- C ABI: every entry point in its fp16 and bf16 form -------------------------------------------------------------
 extern "C" int lr_attention_bwd_f16(const lr_attn_bwd_args* a, lr_stream_t s) { return lr_attention_bwd_t<f16>(a, s); }
 extern "C" int lr_attention_bwd_bf16(const lr_attn_bwd_args* a, lr_stream_t s) { return lr_attention_bwd_t<bf16>(a, s); }
+extern "C" int lr_attention_causal_bwd_f16(const lr_attn_bwd_args* a, lr_stream_t s) { return lr_attention_bwd_t<f16, true>(a, s); }
+extern "C" int lr_attention_causal_bwd_bf16(const lr_attn_bwd_args* a, lr_stream_t s) { return lr_attention_bwd_t<bf16, true>(a, s); }

@@ -462,7 +462,7 @@ static inline int grid_for(long long total, int block, int cap = 4096) {
   return (int)g;
 }
 
-extern "C" int lr_abi_version(void) { return 28; }
+extern "C" int lr_abi_version(void) { return 29; }
 
 #ifdef LR_DEV_VARIANTS
 // developer build only: name -> value table behind LR_DEV (common.h); set through lr_dev_set by the Python front end
@@ -806,6 +806,47 @@ static int lr_geglu_bwd_t(const lr_half* pre, const lr_half* dy, lr_half* dpre, 
   return lr_launch_status();
 }
 
+// Plain erf-GELU (the text tower's MLP, nn.GELU) for training: the GEMM runs without its GELU epilogue and keeps `pre` for the
+// backward.  pre / y / dy / dpre are n contiguous elements, n % 8 == 0; one thread per 8 of them.
+//   fwd: y = gelu(pre)                         (lr_gelu_erf2: the fused epilogue's formula, same bits)
+//   bwd: dpre = dy * (Phi(pre) + pre phi(pre))  (Phi from the forward's own formula, as in geglu_bwd_kernel)
+template <typename T, bool BWD>
+__global__ void gelu_kernel(const T* __restrict__ pre, const T* __restrict__ dy, T* __restrict__ out, long long total) {
+  for (long long id = blockIdx.x * (long long)blockDim.x + threadIdx.x; id < total; id += (long long)gridDim.x * blockDim.x) {
+    float x[8], d[8], o[8];
+    lr_unpack8<T>(*reinterpret_cast<const uint4*>(pre + id * 8), x);
+    if constexpr (BWD) lr_unpack8<T>(*reinterpret_cast<const uint4*>(dy + id * 8), d);
+#pragma unroll
+    for (int i = 0; i < 8; i += 2) {
+      const f32x2_t xx = {x[i], x[i + 1]};
+      f32x2_t r;
+      if constexpr (BWD) {
+        const f32x2_t ph = lr_phi_mhalf2(xx);                                                   // Phi(x) - 0.5
+        const f32x2_t q = xx * xx * -0.72134752044448170368f;                                   // -x^2 / 2 in log2 units
+        const f32x2_t pdf = (f32x2_t){__builtin_amdgcn_exp2f(q[0]), __builtin_amdgcn_exp2f(q[1])} * 0.3989422804014327f;
+        r = (f32x2_t){d[i], d[i + 1]} * __builtin_elementwise_fma(xx, pdf, ph + 0.5f);        // dy (Phi + x phi)
+      } else {
+        r = lr_gelu_erf2(xx);
+      }
+      o[i] = r[0];
+      o[i + 1] = r[1];
+    }
+    *reinterpret_cast<uint4*>(out + id * 8) = lr_pack8<T>(o);
+  }
+}
+
+template <typename T, bool BWD>
+static int lr_gelu_t(const lr_half* pre, const lr_half* dy, lr_half* out, long long n, lr_stream_t s) {
+  if (!pre || !out || (BWD && !dy) || n <= 0) return LR_E_ARG;
+  if (n % 8 || (((uintptr_t)pre | (uintptr_t)dy | (uintptr_t)out) & 15)) return LR_E_ALIGN;
+  const long long total = n / 8;
+  long long blocks = (total + 255) / 256;
+  if (blocks > 65536) blocks = 65536;
+  hipLaunchKernelGGL((gelu_kernel<T, BWD>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)s, (const T*)pre, (const T*)dy, (T*)out,
+                     total);
+  return lr_launch_status();
+}
+
 // Backward of the nearest-2x upsample in front of a conv (Upsample.forward, openaimodel.py:115): the four fine pixels
 // of a coarse pixel add up.  x [N][2H][2W][C] -> y [N][H][W][C].
 template <typename T>
@@ -895,6 +936,10 @@ extern "C" int lr_geglu_fwd(const lr_half* pre, lr_half* out, int M, int H, lr_s
 extern "C" int lr_geglu_fwd_bf16(const lr_half* pre, lr_half* out, int M, int H, lr_stream_t s) { return lr_geglu_fwd_t<bf16>(pre, out, M, H, s); }
 extern "C" int lr_geglu_bwd(const lr_half* pre, const lr_half* dy, lr_half* dpre, int M, int H, lr_stream_t s) { return lr_geglu_bwd_t<f16>(pre, dy, dpre, M, H, s); }
 extern "C" int lr_geglu_bwd_bf16(const lr_half* pre, const lr_half* dy, lr_half* dpre, int M, int H, lr_stream_t s) { return lr_geglu_bwd_t<bf16>(pre, dy, dpre, M, H, s); }
+extern "C" int lr_gelu_fwd_f16(const lr_half* pre, lr_half* y, int64_t n, lr_stream_t s) { return lr_gelu_t<f16, false>(pre, nullptr, y, n, s); }
+extern "C" int lr_gelu_fwd_bf16(const lr_half* pre, lr_half* y, int64_t n, lr_stream_t s) { return lr_gelu_t<bf16, false>(pre, nullptr, y, n, s); }
+extern "C" int lr_gelu_bwd_f16(const lr_half* pre, const lr_half* dy, lr_half* dpre, int64_t n, lr_stream_t s) { return lr_gelu_t<f16, true>(pre, dy, dpre, n, s); }
+extern "C" int lr_gelu_bwd_bf16(const lr_half* pre, const lr_half* dy, lr_half* dpre, int64_t n, lr_stream_t s) { return lr_gelu_t<bf16, true>(pre, dy, dpre, n, s); }
 extern "C" int lr_sumpool2x2(const lr_half* x, lr_half* y, int N, int H, int W, int C, lr_stream_t s) { return lr_sumpool2x2_t<f16>(x, y, N, H, W, C, s); }
 extern "C" int lr_sumpool2x2_bf16(const lr_half* x, lr_half* y, int N, int H, int W, int C, lr_stream_t s) { return lr_sumpool2x2_t<bf16>(x, y, N, H, W, C, s); }
 extern "C" int lr_mv_gather_bwd(const lr_half* dseq, lr_half* dx, int b, int v, int s, int C, lr_stream_t st) { return lr_mv_gather_bwd_t<f16>(dseq, dx, b, v, s, C, st); }

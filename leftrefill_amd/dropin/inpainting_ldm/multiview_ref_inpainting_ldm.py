@@ -6,11 +6,13 @@ to `(b v)` canvases (99-111) and `log_images` (113-180), which samples all `(b v
 MultiViewUnetModel's re-arranged self-attention) and returns the target view plus the references:
   concat_target: canvases are [ref_i | target]; pred / origin / masked = right half of canvas 0, reference = left halves;
   otherwise    : view 0 is the target, views 1.. are the references.
-Training (`p_losses`, 38-91) is out of scope.
+Training objective `p_losses` (38-91): the single-reference objective per canvas, of which only view 0 of every sample counts.
 """
 import torch
 
 from inpainting_ldm.ref_inpainting_ldm import RefInpaintLDM as _SingleViewLDM
+from ldm.modules.diffusionmodules.util import extract_into_tensor
+from ldm.util import default
 
 
 class RefInpaintLDM(_SingleViewLDM):
@@ -20,8 +22,38 @@ class RefInpaintLDM(_SingleViewLDM):
         super().__init__(*args, **kwargs)       # DDPM.__init__ swallows the extra keys, as in the reference
         self.view_mode, self.view_num, self.concat_target, self.reduced_loss = mv
 
-    def p_losses(self, *args, **kwargs):
-        raise NotImplementedError("training is outside the MI355X sampling path")
+    def p_losses(self, x_start, cond, t, noise=None):
+        """reference 38-91: per-canvas MSE, logvar[t] weighting and the vlb term, then '(b v) -> b v' and view 0 only."""
+        noise = default(noise, lambda: torch.randn_like(x_start))
+        x_noisy = self.q_sample(x_start=x_start, t=t, noise=noise)
+        model_output = self.apply_model(x_noisy, t, cond)
+        prefix = 'train' if self.training else 'val'
+        if self.parameterization == "x0":
+            target = x_start
+        elif self.parameterization == "eps":
+            target = noise
+        else:      # "v" (DDPM.get_v of the reference): sqrt(a_t) noise - sqrt(1 - a_t) x0
+            target = (extract_into_tensor(self.sqrt_alphas_cumprod, t, x_start.shape) * noise -
+                      extract_into_tensor(self.sqrt_one_minus_alphas_cumprod, t, x_start.shape) * x_start)
+        v = self.view_num - 1 if self.concat_target else self.view_num
+
+        def view0(per_canvas):      # '(b v) -> b v', [:, 0]
+            return per_canvas.reshape(-1, v)[:, 0]
+
+        loss_dict = {}
+        loss_simple = self.get_loss(model_output, target, mean=False).mean([1, 2, 3])
+        loss_dict[f'{prefix}/loss_simple'] = view0(loss_simple).mean()
+        logvar_t = self.logvar[t].to(self.device)
+        loss = loss_simple / torch.exp(logvar_t) + logvar_t
+        if self.learn_logvar:
+            raise NotImplementedError("learn_logvar is not supported by the multi-view objective (as in the reference)")
+        loss = self.l_simple_weight * view0(loss).mean()
+        loss_vlb = self.get_loss(model_output, target, mean=False).mean(dim=(1, 2, 3))
+        loss_vlb = view0(self.lvlb_weights[t] * loss_vlb).mean()
+        loss_dict[f'{prefix}/loss_vlb'] = loss_vlb
+        loss = loss + self.original_elbo_weight * loss_vlb
+        loss_dict[f'{prefix}/loss'] = loss
+        return loss, loss_dict
 
     def get_input(self, batch, k, cond_key=None, bs=None, return_first_stage_outputs=False, force_c_encode=True):
         if batch['image'].dim() == 5:            # [b, v, h, w, c] -> (b v) canvases, in place like the reference (100-104)

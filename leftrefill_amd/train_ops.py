@@ -5,10 +5,12 @@ and an input requires grad, in which case it runs as a `torch.autograd.Function`
 
   conv / linear    dX = lr_gemm_conv_f16 on flipped, transposed weights (stride 2: zero-insertion gather, `up = 2`;
                    nearest-up conv: dgrad at the fine resolution + lr_sumpool2x2); GEGLU: the training forward keeps the
-                   projection (lr_geglu_fwd applies the gate), lr_geglu_bwd, then the same dgrad GEMM
+                   projection (lr_geglu_fwd applies the gate), lr_geglu_bwd, then the same dgrad GEMM; plain GELU (text tower):
+                   the same with lr_gelu_fwd_f16 / lr_gelu_bwd_f16
   GroupNorm(+SiLU) lr_groupnorm_stats (recomputed) + lr_groupnorm_bwd
   LayerNorm        lr_layernorm_bwd
-  attention        lr_attention_bwd_f16 (flash-style recomputation from the saved log-sum-exp)
+  attention        lr_attention_bwd_f16 (flash-style recomputation from the saved log-sum-exp); causal (text tower):
+                   lr_attention_causal_lse_f16 + lr_attention_causal_bwd_f16
 
 torch.autograd only orchestrates (graph, fan-in sums of residual branches, `torch.utils.checkpoint` recomputation like
 the reference's CheckpointFunction, ldm/modules/diffusionmodules/util.py:102-151); weights never receive gradients --
@@ -177,7 +179,11 @@ def gemm_conv(x1, wt, *, x2=None, bias=None, rowvec=None, resid=None, skip_parts
     if kw.get("out") is not None:
         raise ValueError("out= is not supported while autograd is recording")
     if kw.get("gelu"):
-        raise NotImplementedError("the plain-GELU epilogue (text tower) has no backward; differentiate the PyTorch module instead")
+        # training: the GEMM without its GELU epilogue, `pre` kept for lr_gelu_bwd (as the GEGLU projection keeps its own)
+        if rowvec is not None or resid is not None or kw.get("want_gn_stats"):
+            raise NotImplementedError("the differentiable GELU GEMM takes no rowvec / resid / statistics outputs")
+        kw = {k: v for k, v in kw.items() if k != "gelu"}
+        return _Gelu.apply(_GemmConv.apply(x1, x2, None, wt, bias, None, kw))
     if kw.get("want_gn_stats"):
         meta = kw["_gs_meta"] = []
         y, part, gp = _GemmConv.apply(x1, x2, resid, wt, bias, rowvec, kw)
@@ -201,6 +207,35 @@ def geglu_bwd(pre, dy):
     dpre = torch.empty_like(pre)
     _lib.check(_lib.fn(lib, "lr_geglu_bwd", pre.dtype)(_p(pre), _p(dy), _p(dpre), M, H, _stream()), "geglu_bwd")
     return dpre
+
+
+def gelu_fwd(pre):
+    """y = gelu(pre): the erf-GELU of the fused epilogue as its own pass (lr_gelu_fwd_f16)."""
+    lib = _lib.load()
+    assert pre.is_contiguous()
+    y = torch.empty_like(pre)
+    _lib.check(_lib.fn(lib, "lr_gelu_fwd_f16", pre.dtype)(_p(pre), _p(y), pre.numel(), _stream()), "gelu_fwd")
+    return y
+
+
+def gelu_bwd(pre, dy):
+    """dpre = dy * gelu'(pre) (lr_gelu_bwd_f16)."""
+    lib = _lib.load()
+    assert pre.is_contiguous() and dy.is_contiguous() and dy.shape == pre.shape and dy.dtype == pre.dtype
+    dpre = torch.empty_like(pre)
+    _lib.check(_lib.fn(lib, "lr_gelu_bwd_f16", pre.dtype)(_p(pre), _p(dy), _p(dpre), pre.numel(), _stream()), "gelu_bwd")
+    return dpre
+
+
+class _Gelu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pre):
+        ctx.save_for_backward(pre)
+        return gelu_fwd(pre)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return gelu_bwd(ctx.saved_tensors[0], dy.contiguous())
 
 
 def sumpool2x2(x, N, H, W):
@@ -362,8 +397,8 @@ def attn_bwd_q_splits(B, heads, Nq, Nkv):
     return max(1, min(256 // blocks, tiles // 4, 64))
 
 
-def _attention_backward(q, k, v, out, lse, dout, meta, dq, dk, dv):
-    """dq / dk / dv: pre-allocated (possibly strided column-slice) outputs."""
+def _attention_backward(q, k, v, out, lse, dout, meta, dq, dk, dv, causal=False):
+    """dq / dk / dv: pre-allocated (possibly strided column-slice) outputs.  causal: lr_attention_causal_bwd_f16 (no query split)."""
     lib = _lib.load()
     B, heads, Nq, Nkv, scale = meta
     dout = dout.contiguous()
@@ -371,7 +406,7 @@ def _attention_backward(q, k, v, out, lse, dout, meta, dq, dk, dv):
     a = AttnBwdArgs()
     a.q, a.k, a.v, a.o, a.dout = _p(q), _p(k), _p(v), _p(out), _p(dout)
     a.qt, a.kt, a.dot, a.lse, a.dsum = 0, 0, 0, _p(lse), _p(dsum)       # (no transposed copies since ABI 25: LDS transpose reads)
-    qs, ws = attn_bwd_q_splits(B, heads, Nq, Nkv), None
+    qs, ws = (1 if causal else attn_bwd_q_splits(B, heads, Nq, Nkv)), None
     if qs > 1:      # few key blocks against many queries (the level-0 cross-attention): the dK / dV kernel's query tiles split over more blocks
         ws = torch.empty(qs * B * heads * ((Nkv + 127) // 128) * 2 * 128 * 64, device=q.device, dtype=torch.float32)
         a.qt = _p(ws)
@@ -380,7 +415,8 @@ def _attention_backward(q, k, v, out, lse, dout, meta, dq, dk, dv):
     a.ld_qt, a.ld_kt = (qs if qs > 1 else 0), 0
     a.lddq, a.lddk, a.lddv = dq.stride(0), dk.stride(0), dv.stride(0)
     a.B, a.heads, a.Nq, a.Nkv, a.scale = B, heads, Nq, Nkv, scale
-    _lib.check(_lib.fn(lib, "lr_attention_bwd_f16", q.dtype)(a, _stream()), "attention_bwd")
+    name = "lr_attention_causal_bwd_f16" if causal else "lr_attention_bwd_f16"
+    _lib.check(_lib.fn(lib, name, q.dtype)(a, _stream()), "attention_bwd")
 
 
 def _attention_forward(q, k, v, B, heads, Nq, Nkv, scale):
@@ -507,6 +543,58 @@ def attention_q_kv(q, kv, B, heads, Nq, Nkv, scale, vt=None):
     if not _needs_grad(q, kv):
         return ops.attention_q_kv(q, kv, B, heads, Nq, Nkv, scale, vt=vt)
     return _AttentionQ_KV.apply(q.contiguous(), kv if _rows_ok(kv) else kv.contiguous(), B, heads, Nq, Nkv, scale)
+
+
+class _AttentionCausal(torch.autograd.Function):
+    """Causal self-attention of the text tower (query i sees keys <= i) on the fused in_proj output qkv [M, 3C] (q | k | v column blocks):
+    the three gradients land in ONE [M, 3C] buffer."""
+
+    @staticmethod
+    def forward(ctx, qkv, B, heads, N, scale):
+        lib = _lib.load()
+        C = heads * 64
+        q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
+        out = torch.empty(B * N, C, device=q.device, dtype=q.dtype)
+        lse = torch.empty(B * heads * N, device=q.device, dtype=torch.float32)
+        _lib.check(_lib.fn(lib, "lr_attention_causal_lse_f16", q.dtype)(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(out),
+                                                                       out.stride(0), _p(lse), B, heads, N, float(scale), _stream()),
+                   "attention_causal_lse")
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.meta = (B, heads, N, N, float(scale))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        C = ctx.meta[1] * 64
+        d = torch.empty_like(qkv)
+        _attention_backward(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], out, lse, dout, ctx.meta, d[:, :C], d[:, C:2 * C],
+                            d[:, 2 * C:], causal=True)
+        return d, None, None, None, None
+
+
+def _fused_qkv(q, k, v, C):
+    """The [M, 3C] tensor q / k / v are the three column blocks of, or None."""
+    base = q._base
+    if base is None or k._base is not base or v._base is not base or base.dim() != 2 or base.shape[1] != 3 * C:
+        return None
+    if not base.is_contiguous() or q.shape != (base.shape[0], C) or k.shape != q.shape or v.shape != q.shape:
+        return None
+    e = base.element_size()
+    p0 = base.data_ptr()
+    return base if (q.data_ptr(), k.data_ptr(), v.data_ptr()) == (p0, p0 + C * e, p0 + 2 * C * e) else None
+
+
+def attention_causal(q, k, v, B, heads, N, scale):
+    """Causal self-attention on [B*N, heads*64] column slices (ops.attention_causal); differentiable when an input requires grad.  The text
+    tower passes the three column blocks of its fused in_proj output: the backward then writes one [M, 3C] gradient."""
+    if not _needs_grad(q, k, v):
+        return ops.attention_causal(q, k, v, B, heads, N, scale)
+    C = heads * 64
+    qkv = _fused_qkv(q, k, v, C)
+    if qkv is None:
+        qkv = torch.cat([q, k, v], dim=1)
+    return _AttentionCausal.apply(qkv, B, heads, N, scale)
 
 
 class _MvGather(torch.autograd.Function):
