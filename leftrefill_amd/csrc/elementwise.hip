@@ -2,6 +2,7 @@
 // (small-M linear), the re-arranged multi-view token gather/scatter and the fused CFG + DDIM update.
 // All are HBM/launch bound; every global access is vectorised and coalesced.
 #include "common.h"
+#include <type_traits>
 
 // ---------------------------------------------------------------------------------------------------------------
 // NCHW fp32 -> NHWC fp16 (channel-padded).  One thread per (pixel, octet of output channels): the reads of one
@@ -204,40 +205,12 @@ __global__ void row_copy_kernel(const RowCopyJobs J) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// CFG combine + DDIM update (ddim.py:343-381), fp32 state, 4 elements per thread.
-// ---------------------------------------------------------------------------------------------------------------
-template <typename EpsT, typename T>
-__global__ void ddim_cfg_step_kernel(const float* __restrict__ x, const EpsT* __restrict__ eps,
-                                     const float* __restrict__ noise, float* __restrict__ x_prev,
-                                     float* __restrict__ pred_x0, long long numel, float scale, float sqrt_at,
-                                     float sqrt_1m_at, float sqrt_aprev, float dir_coef, float sigma) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < numel;
-       i += (long long)gridDim.x * blockDim.x) {
-    const float eu = (float)eps[i];
-    const float ec = (float)eps[numel + i];
-    float e;
-    if (sizeof(EpsT) == 2) {
-      // the reference's CFG combine runs in fp16 (model output dtype under autocast, ddim.py:343)
-      const T d = (T)(ec - eu);
-      const T sd = (T)(scale * (float)d);
-      e = (float)(T)(eu + (float)sd);
-    } else {
-      e = eu + scale * (ec - eu);
-    }
-    const float xv = x[i];
-    const float p0 = (xv - sqrt_1m_at * e) / sqrt_at;
-    float xp = sqrt_aprev * p0 + dir_coef * e;
-    if (noise) xp += sigma * noise[i];
-    pred_x0[i] = p0;
-    x_prev[i] = xp;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Fused sampler updates of the PLMS and DPM-Solver++ samplers: CFG combine + multistep combination + update, one pass.
-// The element arithmetic keeps the reference's order of operations op by op (no contraction into fma), so the fp32 result
-// matches torch's eager evaluation of the same expression.  V = 4: 16-byte fp32 / 8-byte 16-bit accesses (numel % 4 == 0
-// and aligned buffers), V = 1: scalar.
+// Fused sampler updates (DDIM, PLMS, DPM-Solver++, DDIM inversion, three-way DDIM): CFG combine + update of the fp32 state, one pass.
+// sampler_step_kernel owns the grid-stride loop and the loads of the eps slabs; a Step (below) holds its fp32 streams and scalars
+// and loads, updates and stores the V elements of one thread (an optional stream is loaded where it is used, so each Step compiles
+// to the code of a hand-written kernel).  V = 4: 16-byte fp32 / 8-byte 16-bit accesses (numel % 4 == 0, aligned buffers), V = 1: scalar.
+// Every Step but DdimStep keeps the reference's order of operations op by op (no contraction into fma), so the fp32 result
+// matches torch's eager evaluation of the same expression.
 // ---------------------------------------------------------------------------------------------------------------
 template <int V>
 __device__ __forceinline__ void ld_f32(const float* __restrict__ p, long long i, float (&v)[V]) {
@@ -269,7 +242,65 @@ __device__ __forceinline__ void ld_eps(const EpsT* __restrict__ p, long long i, 
   }
 }
 
-// e = e_u + s (e_c - e_u), rounded in the eps dtype exactly as ddim_cfg_step_kernel does
+// A Step has NE eps slabs (eps [NE numel]: uncond, cond, ...), its fp32 streams of numel elements each -- in[] (in[0] = x) and
+// out[]; a null pointer is an absent optional stream --, MAX_V (4, or 1 for a step that stays one element per thread) and
+// apply<EpsT, T>(i, e): load the V elements at i of its inputs, map them and e to the outputs, store those.
+template <int V, typename EpsT, typename T, typename Step>
+__global__ void sampler_step_kernel(long long numel, const EpsT* __restrict__ eps, const Step s) {
+  const long long groups = numel / V;
+  for (long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
+    const long long i = g * V;
+    float e[Step::NE][V];
+#pragma unroll
+    for (int j = 0; j < Step::NE; ++j) ld_eps<V, EpsT>(eps, j * numel + i, e[j]);
+    s.template apply<EpsT, T>(i, e);
+  }
+}
+
+// pred_x0 = (x - sqrt_1m_at e) / sqrt_at, x_prev = sqrt_aprev pred_x0 + dir_coef e + sigma noise: the coefficients of the DDIM
+// update, formed in fp32 with sqrtf in the reference's order -- its schedule values are 0-dim / [b,1,1,1] fp32 tensors
+// (ddim.py:359-381, :623-645; plms.py:204-223 with sigma = 0).
+struct DdimCoefs { float sqrt_at, sqrt_1m_at, sqrt_aprev, dir_coef, sigma; };
+
+static inline DdimCoefs ddim_coefs(float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at) {
+  return {sqrtf(a_t), sqrt_one_minus_at, sqrtf(a_prev), sqrtf(1.0f - a_prev - sigma_t * sigma_t), sigma_t};
+}
+
+// CFG combine + DDIM update (ddim.py:343-381), fp32 state, one element per thread.
+// This step is deliberately compiled with the default floating-point contraction ON, while the steps after it are contract(off):
+// x - sqrt_1m_at e, sqrt_aprev p0 + dir_coef e and + sigma noise are fused multiply-adds here (and so is the fp32-eps combine,
+// which is why this step does not call cfg_combine), and they round differently from the separate multiply and add.  Every
+// sample the default DDIM sampler has produced so far carries this rounding; the golden test of this step allows 2e-6, so it
+// would NOT notice a switch to contract(off), a reordered expression or a call to cfg_combine.  Keep all three as they are.
+struct DdimStep {
+  static constexpr int NE = 2, MAX_V = 1;
+  const float* in[2];      // x, noise (optional)
+  float* out[2];           // x_prev, pred_x0
+  float scale;
+  DdimCoefs c;
+  template <typename EpsT, typename T, int V>
+  __device__ __forceinline__ void apply(long long i, const float (&e)[NE][V]) const {
+    static_assert(V == 1);
+    const float eu = e[0][0], ec = e[1][0];
+    float ee;
+    if constexpr (sizeof(EpsT) == 2) {
+      // the reference's CFG combine runs in fp16 (model output dtype under autocast, ddim.py:343)
+      const T d = (T)(ec - eu);
+      const T sd = (T)(scale * (float)d);
+      ee = (float)(T)(eu + (float)sd);
+    } else {
+      ee = eu + scale * (ec - eu);
+    }
+    const float xv = in[0][i];
+    const float p0 = (xv - c.sqrt_1m_at * ee) / c.sqrt_at;
+    float xp = c.sqrt_aprev * p0 + c.dir_coef * ee;
+    if (in[1]) xp += c.sigma * in[1][i];
+    out[1][i] = p0;
+    out[0][i] = xp;
+  }
+};
+
+// e = e_u + s (e_c - e_u), rounded in the eps dtype exactly as DdimStep does
 template <typename EpsT, typename T>
 __device__ __forceinline__ float cfg_combine(float eu, float ec, float scale) {
 #pragma clang fp contract(off)
@@ -284,98 +315,93 @@ __device__ __forceinline__ float cfg_combine(float eu, float ec, float scale) {
 
 // PLMS (pseudo linear multistep, sigma = 0): e' = (w0 e + w1 h1 + w2 h2 + w3 h3) / div over the n_hist newest history
 // entries, then pred_x0 = (x - sqrt(1 - a_t) e') / sqrt(a_t), x_prev = sqrt(a_prev) pred_x0 + sqrt(1 - a_prev) e'.
-template <int V, typename EpsT, typename T>
-__global__ void plms_cfg_step_kernel(const float* __restrict__ x, const EpsT* __restrict__ eps, const float* __restrict__ h1,
-                                     const float* __restrict__ h2, const float* __restrict__ h3, float* __restrict__ e_out,
-                                     float* __restrict__ x_prev, float* __restrict__ pred_x0, long long numel, int n_hist,
-                                     float scale, float w0, float w1, float w2, float w3, float div, float sqrt_at,
-                                     float sqrt_1m_at, float sqrt_aprev, float dir_coef) {
+struct PlmsStep {
+  static constexpr int NE = 2, MAX_V = 4;
+  const float* in[4];      // x, then the n_hist newest history entries (the rest null)
+  float* out[3];           // e (optional): this evaluation's combined eps; x_prev; pred_x0
+  int n_hist;
+  float scale, w[4], div;
+  DdimCoefs c;
+  template <typename EpsT, typename T, int V>
+  __device__ __forceinline__ void apply(long long i, const float (&e)[NE][V]) const {
 #pragma clang fp contract(off)
-  const long long groups = numel / V;
-  for (long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
-    const long long i = g * V;
-    float eu[V], ec[V], xv[V], a[V], b[V], c[V], e[V], p0[V], xp[V];
-    ld_eps<V, EpsT>(eps, i, eu);
-    ld_eps<V, EpsT>(eps, numel + i, ec);
-    ld_f32<V>(x, i, xv);
-    if (n_hist > 0) ld_f32<V>(h1, i, a);
-    if (n_hist > 1) ld_f32<V>(h2, i, b);
-    if (n_hist > 2) ld_f32<V>(h3, i, c);
+    float xv[V], h1[V], h2[V], h3[V], ee[V], p0[V], xp[V];
+    ld_f32<V>(in[0], i, xv);
+    if (n_hist > 0) ld_f32<V>(in[1], i, h1);
+    if (n_hist > 1) ld_f32<V>(in[2], i, h2);
+    if (n_hist > 2) ld_f32<V>(in[3], i, h3);
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      e[k] = cfg_combine<EpsT, T>(eu[k], ec[k], scale);
-      float acc = w0 * e[k];                         // integer weights, left to right, then ONE division (plms.py:225-241)
-      if (n_hist > 0) acc = acc + w1 * a[k];
-      if (n_hist > 1) acc = acc + w2 * b[k];
-      if (n_hist > 2) acc = acc + w3 * c[k];
+      ee[k] = cfg_combine<EpsT, T>(e[0][k], e[1][k], scale);
+      float acc = w[0] * ee[k];                         // integer weights, left to right, then ONE division (plms.py:225-241)
+      if (n_hist > 0) acc = acc + w[1] * h1[k];
+      if (n_hist > 1) acc = acc + w[2] * h2[k];
+      if (n_hist > 2) acc = acc + w[3] * h3[k];
       const float ep = acc / div;
-      p0[k] = (xv[k] - sqrt_1m_at * ep) / sqrt_at;
-      xp[k] = sqrt_aprev * p0[k] + dir_coef * ep;
+      p0[k] = (xv[k] - c.sqrt_1m_at * ep) / c.sqrt_at;
+      xp[k] = c.sqrt_aprev * p0[k] + c.dir_coef * ep;
     }
-    if (e_out) st_f32<V>(e_out, i, e);
-    st_f32<V>(pred_x0, i, p0);
-    st_f32<V>(x_prev, i, xp);
+    if (out[0]) st_f32<V>(out[0], i, ee);
+    st_f32<V>(out[2], i, p0);
+    st_f32<V>(out[1], i, xp);
   }
-}
+};
 
 // DPM-Solver++ multistep (data prediction, solver_type 'dpm_solver'): m0 = (x - sigma_s e) / alpha_s, then
 //   order 1: x_t = ratio x - c m0,                     c = alpha_t expm1(-h)
 //   order 2: x_t = ratio x - c m0 - c_half D,          c = alpha_t (e^-h - 1), c_half = 0.5 c, D = inv_r0 (m0 - m1)
-template <int V, typename EpsT, typename T>
-__global__ void dpmpp_cfg_step_kernel(const float* __restrict__ x, const EpsT* __restrict__ eps, const float* __restrict__ x0_prev,
-                                      float* __restrict__ x0_out, float* __restrict__ x_next, long long numel, float scale,
-                                      float sigma_s, float alpha_s, float ratio, float c, float c_half, float inv_r0) {
+struct DpmppStep {
+  static constexpr int NE = 2, MAX_V = 4;
+  const float* in[2];      // x, m1 = the previous step's x0 (null: order 1)
+  float* out[2];           // m0 = this step's x0, x_t
+  float scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0;
+  template <typename EpsT, typename T, int V>
+  __device__ __forceinline__ void apply(long long i, const float (&e)[NE][V]) const {
 #pragma clang fp contract(off)
-  const long long groups = numel / V;
-  for (long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
-    const long long i = g * V;
-    float eu[V], ec[V], xv[V], m1[V], m0[V], xt[V];
-    ld_eps<V, EpsT>(eps, i, eu);
-    ld_eps<V, EpsT>(eps, numel + i, ec);
-    ld_f32<V>(x, i, xv);
-    if (x0_prev) ld_f32<V>(x0_prev, i, m1);
+    float xv[V], m1[V], m0[V], xt[V];
+    ld_f32<V>(in[0], i, xv);
+    if (in[1]) ld_f32<V>(in[1], i, m1);
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      const float e = cfg_combine<EpsT, T>(eu[k], ec[k], scale);
-      m0[k] = (xv[k] - sigma_s * e) / alpha_s;
+      const float ee = cfg_combine<EpsT, T>(e[0][k], e[1][k], scale);
+      m0[k] = (xv[k] - sigma_s * ee) / alpha_s;
       float v = ratio * xv[k] - c * m0[k];
-      if (x0_prev) {
+      if (in[1]) {
         const float D = inv_r0 * (m0[k] - m1[k]);
         v = v - c_half * D;
       }
       xt[k] = v;
     }
-    st_f32<V>(x0_out, i, m0);
-    st_f32<V>(x_next, i, xt);
+    st_f32<V>(out[0], i, m0);
+    st_f32<V>(out[1], i, xt);
   }
-}
+};
 
 // DDIM inversion (DDIMSampler.encode, ddim.py:411-421): x_next = c1 x + c2 e.  c1, c2 are 0-dim float64 tensors in the
 // reference, cast to the dtype of the tensor they multiply: with fp16 / bf16 eps, c2 is rounded to that dtype and so is the
 // product c2 e; c1 x and the sum are fp32.
-template <int V, typename EpsT, typename T>
-__global__ void ddim_inv_cfg_step_kernel(const float* __restrict__ x, const EpsT* __restrict__ eps, float* __restrict__ x_next,
-                                         long long numel, float scale, float c1, float c2) {
+struct DdimInvStep {
+  static constexpr int NE = 2, MAX_V = 4;
+  const float* in[1];      // x
+  float* out[1];           // x_next
+  float scale, c1, c2;
+  template <typename EpsT, typename T, int V>
+  __device__ __forceinline__ void apply(long long i, const float (&e)[NE][V]) const {
 #pragma clang fp contract(off)
-  const long long groups = numel / V;
-  for (long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
-    const long long i = g * V;
-    float eu[V], ec[V], xv[V], xn[V];
-    ld_eps<V, EpsT>(eps, i, eu);
-    ld_eps<V, EpsT>(eps, numel + i, ec);
-    ld_f32<V>(x, i, xv);
+    float xv[V], xn[V];
+    ld_f32<V>(in[0], i, xv);
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      const float e = cfg_combine<EpsT, T>(eu[k], ec[k], scale);
+      const float ee = cfg_combine<EpsT, T>(e[0][k], e[1][k], scale);
       const float a = c1 * xv[k];
       float b;
-      if constexpr (sizeof(EpsT) == 2) b = (float)(T)((float)(T)c2 * e);
-      else b = c2 * e;
+      if constexpr (sizeof(EpsT) == 2) b = (float)(T)((float)(T)c2 * ee);
+      else b = c2 * ee;
       xn[k] = a + b;
     }
-    st_f32<V>(x_next, i, xn);
+    st_f32<V>(out[0], i, xn);
   }
-}
+};
 
 // Three-way guidance of StructureDDIMSampler.p_sample_ddim_guide (ddim.py:605-607), eps [3 numel] = uncond, cond, cond_simple:
 // e = e_u + s ((w e_c + (1 - w) e_s) - e_u), every operation rounded in the eps dtype; then the DDIM update of ddim.py:623-647
@@ -403,33 +429,30 @@ __device__ __forceinline__ float cfg3_combine(float eu, float ec, float es, floa
   }
 }
 
-template <int V, typename EpsT, typename T>
-__global__ void ddim_cfg3_step_kernel(const float* __restrict__ x, const EpsT* __restrict__ eps, const float* __restrict__ noise,
-                                      float* __restrict__ x_prev, float* __restrict__ pred_x0, long long numel, float scale,
-                                      float w, float w1m, float sqrt_at, float sqrt_1m_at, float sqrt_aprev, float dir_coef,
-                                      float sigma) {
+struct DdimCfg3Step {
+  static constexpr int NE = 3, MAX_V = 4;
+  const float* in[2];      // x, noise (optional)
+  float* out[2];           // x_prev, pred_x0
+  float scale, w, w1m;
+  DdimCoefs c;
+  template <typename EpsT, typename T, int V>
+  __device__ __forceinline__ void apply(long long i, const float (&e)[NE][V]) const {
 #pragma clang fp contract(off)
-  const long long groups = numel / V;
-  for (long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
-    const long long i = g * V;
-    float eu[V], ec[V], es[V], xv[V], nz[V], p0[V], xp[V];
-    ld_eps<V, EpsT>(eps, i, eu);
-    ld_eps<V, EpsT>(eps, numel + i, ec);
-    ld_eps<V, EpsT>(eps, 2 * numel + i, es);
-    ld_f32<V>(x, i, xv);
-    if (noise) ld_f32<V>(noise, i, nz);
+    float xv[V], nz[V], p0[V], xp[V];
+    ld_f32<V>(in[0], i, xv);
+    if (in[1]) ld_f32<V>(in[1], i, nz);
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      const float e = cfg3_combine<EpsT, T>(eu[k], ec[k], es[k], scale, w, w1m);
-      p0[k] = (xv[k] - sqrt_1m_at * e) / sqrt_at;
-      float v = sqrt_aprev * p0[k] + dir_coef * e;
-      if (noise) v = v + sigma * nz[k];
+      const float ee = cfg3_combine<EpsT, T>(e[0][k], e[1][k], e[2][k], scale, w, w1m);
+      p0[k] = (xv[k] - c.sqrt_1m_at * ee) / c.sqrt_at;
+      float v = c.sqrt_aprev * p0[k] + c.dir_coef * ee;
+      if (in[1]) v = v + c.sigma * nz[k];
       xp[k] = v;
     }
-    st_f32<V>(pred_x0, i, p0);
-    st_f32<V>(x_prev, i, xp);
+    st_f32<V>(out[1], i, p0);
+    st_f32<V>(out[0], i, xp);
   }
-}
+};
 
 // DDIMSampler.stochastic_encode (ddim.py:436-449): out = sa[b] x0 + s1ma[b] noise, sample b = blockIdx.y; the coefficient pairs
 // are kernel arguments (at most LR_Q_SAMPLE_MAX_B samples per launch).
@@ -454,6 +477,13 @@ __global__ void ddim_q_sample_kernel(const float* __restrict__ x0, const float* 
 }
 
 static inline bool aligned16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
+
+template <typename P, size_t N>
+static inline bool aligned16(P* const (&ptrs)[N]) {      // every pointer of a list (null: an absent stream)
+  for (P* p : ptrs)
+    if (!aligned16(p)) return false;
+  return true;
+}
 
 static inline int grid_for(long long total, int block, int cap = 4096) {
   long long g = (total + block - 1) / block;
@@ -571,34 +601,36 @@ static int lr_mv_scatter_t(const lr_half* seq, lr_half* x, int b, int v, int s, 
   return lr_launch_status();
 }
 
+// The one launch of the sampler steps: V = 4 where the step allows it, numel % 4 == 0, every fp32 stream is 16-byte aligned and
+// eps 16-byte (fp32) / 8-byte (16-bit) aligned, else V = 1; EpsT = float or the 16-bit type T of the entry point.
+template <typename T, typename Step>
+static int launch_sampler_step(const Step& st, const void* eps, int eps_is_f32, int64_t numel, lr_stream_t s) {
+  const bool vec = Step::MAX_V == 4 && numel % 4 == 0 && aligned16(st.in) && aligned16(st.out) &&
+                   ((uintptr_t)eps & (eps_is_f32 ? 15 : 7)) == 0;
+  auto launch = [&](auto v, auto* e) {      // v: std::integral_constant<int, V>, e: const EpsT*
+    constexpr int V = decltype(v)::value;
+    using EpsT = std::remove_cv_t<std::remove_pointer_t<decltype(e)>>;
+    hipLaunchKernelGGL((sampler_step_kernel<V, EpsT, T, Step>), dim3(grid_for(numel / V, 256)), dim3(256), 0, (hipStream_t)s,
+                       (long long)numel, e, st);
+  };
+  auto with_eps = [&](auto* e) {
+    if constexpr (Step::MAX_V == 4) {
+      if (vec) return launch(std::integral_constant<int, 4>{}, e);
+    }
+    launch(std::integral_constant<int, 1>{}, e);
+  };
+  if (eps_is_f32) with_eps((const float*)eps);
+  else with_eps((const T*)eps);
+  return lr_launch_status();
+}
+
 template <typename T>
 static int lr_ddim_cfg_step_t(const float* x, const void* eps, int eps_is_f32, const float* noise, float* x_prev,
                                 float* pred_x0, int64_t numel, float cfg_scale, float a_t, float a_prev, float sigma_t,
                                 float sqrt_one_minus_at, lr_stream_t s) {
   if (!x || !eps || !x_prev || !pred_x0 || numel <= 0) return LR_E_ARG;
-  // same fp32 scalar arithmetic as the reference's 0-dim fp32 tensors (ddim.py:359-381)
-  const float sqrt_at = sqrtf(a_t);
-  const float sqrt_aprev = sqrtf(a_prev);
-  const float dir_coef = sqrtf(1.0f - a_prev - sigma_t * sigma_t);
-  dim3 grid(grid_for(numel, 256)), block(256);
-  if (eps_is_f32)
-    hipLaunchKernelGGL((ddim_cfg_step_kernel<float, T>), grid, block, 0, (hipStream_t)s, x, (const float*)eps, noise, x_prev,
-                       pred_x0, (long long)numel, cfg_scale, sqrt_at, sqrt_one_minus_at, sqrt_aprev, dir_coef,
-                       sigma_t);
-  else
-    hipLaunchKernelGGL((ddim_cfg_step_kernel<T, T>), grid, block, 0, (hipStream_t)s, x, (const T*)eps, noise, x_prev,
-                       pred_x0, (long long)numel, cfg_scale, sqrt_at, sqrt_one_minus_at, sqrt_aprev, dir_coef,
-                       sigma_t);
-  return lr_launch_status();
-}
-
-template <int V, typename EpsT, typename T>
-static void launch_plms(const float* x, const void* eps, const float* h1, const float* h2, const float* h3, float* e_out,
-                        float* x_prev, float* pred_x0, long long numel, int n_hist, float scale, const float* w, float div,
-                        float sqrt_at, float sqrt_1m_at, float sqrt_aprev, float dir_coef, hipStream_t s) {
-  hipLaunchKernelGGL((plms_cfg_step_kernel<V, EpsT, T>), dim3(grid_for(numel / V, 256)), dim3(256), 0, s, x, (const EpsT*)eps,
-                     h1, h2, h3, e_out, x_prev, pred_x0, numel, n_hist, scale, w[0], w[1], w[2], w[3], div, sqrt_at, sqrt_1m_at,
-                     sqrt_aprev, dir_coef);
+  const DdimStep st{{x, noise}, {x_prev, pred_x0}, cfg_scale, ddim_coefs(a_t, a_prev, sigma_t, sqrt_one_minus_at)};
+  return launch_sampler_step<T>(st, eps, eps_is_f32, numel, s);
 }
 
 template <typename T>
@@ -607,35 +639,14 @@ static int lr_plms_cfg_step_t(const float* x, const void* eps, int eps_is_f32, c
                               float cfg_scale, float a_t, float a_prev, float sqrt_one_minus_at, lr_stream_t s) {
   if (!x || !eps || !x_prev || !pred_x0 || !weights || numel <= 0 || n_hist < 0 || n_hist > 3 || divisor == 0.f) return LR_E_ARG;
   if (n_hist > 0 && !hist) return LR_E_ARG;
-  const float* h[3] = {nullptr, nullptr, nullptr};
+  PlmsStep st{{x, nullptr, nullptr, nullptr}, {e_out, x_prev, pred_x0}, n_hist, cfg_scale, {weights[0], 0.f, 0.f, 0.f}, divisor,
+              ddim_coefs(a_t, a_prev, 0.0f, sqrt_one_minus_at)};
   for (int k = 0; k < n_hist; ++k) {
     if (!hist[k]) return LR_E_ARG;
-    h[k] = hist[k];
+    st.in[k + 1] = hist[k];
+    st.w[k + 1] = weights[k + 1];
   }
-  float w[4] = {weights[0], 0.f, 0.f, 0.f};
-  for (int k = 0; k < n_hist; ++k) w[k + 1] = weights[k + 1];
-  // same fp32 scalar arithmetic as the reference's 0-dim fp32 tensors (plms.py:204-223, sigma = 0)
-  const float sqrt_at = sqrtf(a_t);
-  const float sqrt_aprev = sqrtf(a_prev);
-  const float dir_coef = sqrtf(1.0f - a_prev - 0.0f);
-  const bool vec = numel % 4 == 0 && aligned16(x) && aligned16(h[0]) && aligned16(h[1]) && aligned16(h[2]) && aligned16(e_out) &&
-                   aligned16(x_prev) && aligned16(pred_x0) && ((uintptr_t)eps & (eps_is_f32 ? 15 : 7)) == 0;
-  hipStream_t st = (hipStream_t)s;
-  if (eps_is_f32) {
-    if (vec) launch_plms<4, float, T>(x, eps, h[0], h[1], h[2], e_out, x_prev, pred_x0, numel, n_hist, cfg_scale, w, divisor, sqrt_at, sqrt_one_minus_at, sqrt_aprev, dir_coef, st);
-    else launch_plms<1, float, T>(x, eps, h[0], h[1], h[2], e_out, x_prev, pred_x0, numel, n_hist, cfg_scale, w, divisor, sqrt_at, sqrt_one_minus_at, sqrt_aprev, dir_coef, st);
-  } else {
-    if (vec) launch_plms<4, T, T>(x, eps, h[0], h[1], h[2], e_out, x_prev, pred_x0, numel, n_hist, cfg_scale, w, divisor, sqrt_at, sqrt_one_minus_at, sqrt_aprev, dir_coef, st);
-    else launch_plms<1, T, T>(x, eps, h[0], h[1], h[2], e_out, x_prev, pred_x0, numel, n_hist, cfg_scale, w, divisor, sqrt_at, sqrt_one_minus_at, sqrt_aprev, dir_coef, st);
-  }
-  return lr_launch_status();
-}
-
-template <int V, typename EpsT, typename T>
-static void launch_dpmpp(const float* x, const void* eps, const float* x0_prev, float* x0_out, float* x_next, long long numel,
-                         float scale, float sigma_s, float alpha_s, float ratio, float c, float c_half, float inv_r0, hipStream_t s) {
-  hipLaunchKernelGGL((dpmpp_cfg_step_kernel<V, EpsT, T>), dim3(grid_for(numel / V, 256)), dim3(256), 0, s, x, (const EpsT*)eps,
-                     x0_prev, x0_out, x_next, numel, scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0);
+  return launch_sampler_step<T>(st, eps, eps_is_f32, numel, s);
 }
 
 template <typename T>
@@ -643,48 +654,16 @@ static int lr_dpmpp_cfg_step_t(const float* x, const void* eps, int eps_is_f32, 
                                int64_t numel, float cfg_scale, float sigma_s, float alpha_s, float ratio, float c, float c_half,
                                float inv_r0, lr_stream_t s) {
   if (!x || !eps || !x0_out || !x_next || numel <= 0 || alpha_s == 0.f) return LR_E_ARG;
-  const bool vec = numel % 4 == 0 && aligned16(x) && aligned16(x0_prev) && aligned16(x0_out) && aligned16(x_next) &&
-                   ((uintptr_t)eps & (eps_is_f32 ? 15 : 7)) == 0;
-  hipStream_t st = (hipStream_t)s;
-  if (eps_is_f32) {
-    if (vec) launch_dpmpp<4, float, T>(x, eps, x0_prev, x0_out, x_next, numel, cfg_scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0, st);
-    else launch_dpmpp<1, float, T>(x, eps, x0_prev, x0_out, x_next, numel, cfg_scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0, st);
-  } else {
-    if (vec) launch_dpmpp<4, T, T>(x, eps, x0_prev, x0_out, x_next, numel, cfg_scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0, st);
-    else launch_dpmpp<1, T, T>(x, eps, x0_prev, x0_out, x_next, numel, cfg_scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0, st);
-  }
-  return lr_launch_status();
-}
-
-template <int V, typename EpsT, typename T>
-static void launch_ddim_inv(const float* x, const void* eps, float* x_next, long long numel, float scale, float c1, float c2,
-                            hipStream_t s) {
-  hipLaunchKernelGGL((ddim_inv_cfg_step_kernel<V, EpsT, T>), dim3(grid_for(numel / V, 256)), dim3(256), 0, s, x,
-                     (const EpsT*)eps, x_next, numel, scale, c1, c2);
+  const DpmppStep st{{x, x0_prev}, {x0_out, x_next}, cfg_scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0};
+  return launch_sampler_step<T>(st, eps, eps_is_f32, numel, s);
 }
 
 template <typename T>
 static int lr_ddim_inv_cfg_step_t(const float* x, const void* eps, int eps_is_f32, float* x_next, int64_t numel, float cfg_scale,
                                   float c1, float c2, lr_stream_t s) {
   if (!x || !eps || !x_next || numel <= 0) return LR_E_ARG;
-  const bool vec = numel % 4 == 0 && aligned16(x) && aligned16(x_next) && ((uintptr_t)eps & (eps_is_f32 ? 15 : 7)) == 0;
-  hipStream_t st = (hipStream_t)s;
-  if (eps_is_f32) {
-    if (vec) launch_ddim_inv<4, float, T>(x, eps, x_next, numel, cfg_scale, c1, c2, st);
-    else launch_ddim_inv<1, float, T>(x, eps, x_next, numel, cfg_scale, c1, c2, st);
-  } else {
-    if (vec) launch_ddim_inv<4, T, T>(x, eps, x_next, numel, cfg_scale, c1, c2, st);
-    else launch_ddim_inv<1, T, T>(x, eps, x_next, numel, cfg_scale, c1, c2, st);
-  }
-  return lr_launch_status();
-}
-
-template <int V, typename EpsT, typename T>
-static void launch_ddim_cfg3(const float* x, const void* eps, const float* noise, float* x_prev, float* pred_x0, long long numel,
-                             float scale, float w, float w1m, float sqrt_at, float sqrt_1m_at, float sqrt_aprev, float dir_coef,
-                             float sigma, hipStream_t s) {
-  hipLaunchKernelGGL((ddim_cfg3_step_kernel<V, EpsT, T>), dim3(grid_for(numel / V, 256)), dim3(256), 0, s, x, (const EpsT*)eps,
-                     noise, x_prev, pred_x0, numel, scale, w, w1m, sqrt_at, sqrt_1m_at, sqrt_aprev, dir_coef, sigma);
+  const DdimInvStep st{{x}, {x_next}, cfg_scale, c1, c2};
+  return launch_sampler_step<T>(st, eps, eps_is_f32, numel, s);
 }
 
 template <typename T>
@@ -692,22 +671,9 @@ static int lr_ddim_cfg3_step_t(const float* x, const void* eps, int eps_is_f32, 
                                int64_t numel, float cfg_scale, float cond_weight, float one_minus_cond_weight, float a_t,
                                float a_prev, float sigma_t, float sqrt_one_minus_at, lr_stream_t s) {
   if (!x || !eps || !x_prev || !pred_x0 || numel <= 0) return LR_E_ARG;
-  // same fp32 scalar arithmetic as the reference's [b,1,1,1] fp32 tensors (ddim.py:623-645), as lr_ddim_cfg_step
-  const float sqrt_at = sqrtf(a_t);
-  const float sqrt_aprev = sqrtf(a_prev);
-  const float dir_coef = sqrtf(1.0f - a_prev - sigma_t * sigma_t);
-  const bool vec = numel % 4 == 0 && aligned16(x) && aligned16(noise) && aligned16(x_prev) && aligned16(pred_x0) &&
-                   ((uintptr_t)eps & (eps_is_f32 ? 15 : 7)) == 0;
-  hipStream_t st = (hipStream_t)s;
-  const float w = cond_weight, w1m = one_minus_cond_weight;
-  if (eps_is_f32) {
-    if (vec) launch_ddim_cfg3<4, float, T>(x, eps, noise, x_prev, pred_x0, numel, cfg_scale, w, w1m, sqrt_at, sqrt_one_minus_at, sqrt_aprev, dir_coef, sigma_t, st);
-    else launch_ddim_cfg3<1, float, T>(x, eps, noise, x_prev, pred_x0, numel, cfg_scale, w, w1m, sqrt_at, sqrt_one_minus_at, sqrt_aprev, dir_coef, sigma_t, st);
-  } else {
-    if (vec) launch_ddim_cfg3<4, T, T>(x, eps, noise, x_prev, pred_x0, numel, cfg_scale, w, w1m, sqrt_at, sqrt_one_minus_at, sqrt_aprev, dir_coef, sigma_t, st);
-    else launch_ddim_cfg3<1, T, T>(x, eps, noise, x_prev, pred_x0, numel, cfg_scale, w, w1m, sqrt_at, sqrt_one_minus_at, sqrt_aprev, dir_coef, sigma_t, st);
-  }
-  return lr_launch_status();
+  const DdimCfg3Step st{{x, noise}, {x_prev, pred_x0}, cfg_scale, cond_weight, one_minus_cond_weight,
+                        ddim_coefs(a_t, a_prev, sigma_t, sqrt_one_minus_at)};
+  return launch_sampler_step<T>(st, eps, eps_is_f32, numel, s);
 }
 
 extern "C" int lr_ddim_q_sample(const float* x0, const float* noise, float* out, int B, int64_t per_sample, const float* sa,

@@ -15,6 +15,8 @@ Also served: `encode` (DDIM inversion, one lr_ddim_inv_cfg_step per evaluation),
 for index >= Tm, one lr_ddim_cfg3_step per evaluation, then two-way guidance with cond_simple).  All of them accept dict
 conditioning as well as tensors.
 """
+import contextlib
+
 import numpy as np
 import torch
 
@@ -53,11 +55,31 @@ class CFGModelEval(object):
         if hasattr(unet, "prepare_timesteps"):
             unet.prepare_timesteps(int(s_) for s_ in steps)
 
+    @contextlib.contextmanager
     def _step_hint(self, step):
-        """step: the host timestep of this evaluation -- an int, or the exact fp32 value of a continuous time (a python float)."""
+        """The model evaluations inside the `with` block run with their host timestep named to the UNet; the name is always cleared
+        on the way out.  step: an int, or the exact fp32 value of a continuous time (a python float); None = unknown."""
         unet = self._unet()
-        if hasattr(unet, "prepare_timesteps"):
+        named = hasattr(unet, "prepare_timesteps")
+        if named:
             unet._t_host = None if step is None else (step if isinstance(step, float) else int(step))
+        try:
+            yield
+        finally:
+            if named:
+                unet._t_host = None
+
+    @staticmethod
+    def _warn_conditioning_count(conditioning, batch_size, dict_only=False):
+        """The reference samplers' notice when the first conditioning entry does not have batch_size rows (DDIM looks at dict
+        conditioning only)."""
+        if conditioning is None or (dict_only and not isinstance(conditioning, dict)):
+            return
+        c0 = conditioning[list(conditioning.keys())[0]] if isinstance(conditioning, dict) else conditioning
+        while isinstance(c0, list):
+            c0 = c0[0]
+        if c0.shape[0] != batch_size:
+            print(f"Warning: Got {c0.shape[0]} conditionings but batch-size is {batch_size}")
 
     # the conditioning is constant over the loop: build the [uncond; cond] batch once instead of 50 torch.cat calls
     def _prepare_cfg_inputs(self, c, uc, scale):
@@ -159,12 +181,7 @@ class DDIMSampler(CFGModelEval):
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
                unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None, **kwargs):
-        if conditioning is not None and isinstance(conditioning, dict):
-            c0 = conditioning[list(conditioning.keys())[0]]
-            while isinstance(c0, list):
-                c0 = c0[0]
-            if c0.shape[0] != batch_size:
-                print(f"Warning: Got {c0.shape[0]} conditionings but batch-size is {batch_size}")
+        self._warn_conditioning_count(conditioning, batch_size, dict_only=True)
         if quantize_x0 or score_corrector is not None or dynamic_threshold is not None or noise_dropout > 0.:
             raise NotImplementedError("quantize_x0 / score_corrector / dynamic_threshold / noise_dropout are unused")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
@@ -269,13 +286,10 @@ class DDIMSampler(CFGModelEval):
                       t_host=None, **kwargs):
         """t_host: the timestep every entry of `t` holds, as a host integer (the sampling loops pass it; None = unknown).  It is named
         to the UNet only around this method's own apply_model calls (precomputed embedding rows, UNetModel.prepare_timesteps)."""
-        self._step_hint(t_host)
-        try:
+        with self._step_hint(t_host):
             return self._p_sample_ddim(x, c, t, index, repeat_noise, use_original_steps, quantize_denoised, temperature, noise_dropout,
                                        score_corrector, corrector_kwargs, unconditional_guidance_scale, unconditional_conditioning,
                                        dynamic_threshold)
-        finally:
-            self._step_hint(None)
 
     def _p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                        temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
@@ -375,11 +389,8 @@ class DDIMSampler(CFGModelEval):
             for i in range(num_steps):
                 t = torch.full((x0.shape[0],), i, device=x0.device, dtype=torch.long)
                 x_in = x_next.float().contiguous()
-                self._step_hint(i)
-                try:
+                with self._step_hint(i):
                     eps, sc = self._cfg_eps(x_in, c, t, uc, scale)
-                finally:
-                    self._step_hint(None)
                 x_next = ops.ddim_inv_cfg_step(x_in, eps, sc, c1[i], c2[i])
                 if return_intermediates and i % (num_steps // return_intermediates) == 0 and i < num_steps - 1:
                     intermediates.append(x_next)
@@ -464,12 +475,7 @@ class StructureDDIMSampler(DDIMSampler):
                                   log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, dynamic_threshold=dynamic_threshold,
                                   ucg_schedule=ucg_schedule)
-        if conditioning is not None and isinstance(conditioning, dict):
-            c0 = conditioning[list(conditioning.keys())[0]]
-            while isinstance(c0, list):
-                c0 = c0[0]
-            if c0.shape[0] != batch_size:
-                print(f"Warning: Got {c0.shape[0]} conditionings but batch-size is {batch_size}")
+        self._warn_conditioning_count(conditioning, batch_size, dict_only=True)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
         return self.ddim_sampling(conditioning, (batch_size, C, H, W), callback=callback, img_callback=img_callback,
@@ -563,14 +569,11 @@ class StructureDDIMSampler(DDIMSampler):
         three = unconditional_conditioning is not None and scale != 1.
         if three:
             self._check_extras("StructureDDIMSampler", False, unconditional_conditioning, scale)
-        self._step_hint(t_host)
-        try:
+        with self._step_hint(t_host):
             if three:
                 eps = self._cfg3_eps(x, c, c_simple, t, unconditional_conditioning)
             else:
                 eps, _ = self._cfg_eps(x, c, t, None, 1.)
-        finally:
-            self._step_hint(None)
         noise = noise_like(x.shape, x.device, repeat_noise)      # drawn every step like the reference (ddim.py:643)
         sigma = float(self.ddim_sigmas[index]) * float(temperature)
         a_t, a_prev, s1 = self.ddim_alphas[index], self.ddim_alphas_prev[index], self.ddim_sqrt_one_minus_alphas[index]

@@ -74,12 +74,7 @@ class DPMSolverSampler(CFGModelEval):
             from leftrefill_amd import dist as lrd
             if lrd.split_cfg_active():
                 _unsupported("split classifier-free guidance across ranks")
-        if conditioning is not None:
-            c0 = conditioning[list(conditioning.keys())[0]] if isinstance(conditioning, dict) else conditioning
-            while isinstance(c0, list):
-                c0 = c0[0]
-            if c0.shape[0] != batch_size:
-                print(f"Warning: Got {c0.shape[0]} conditionings but batch-size is {batch_size}")
+        self._warn_conditioning_count(conditioning, batch_size)
         C, H, W = shape
         device = self.model.betas.device
         x = torch.randn((batch_size, C, H, W), device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
@@ -94,11 +89,8 @@ class DPMSolverSampler(CFGModelEval):
         try:
             for k in range(S):
                 t = torch.full((batch_size,), t_model[k], device=device, dtype=torch.float32)
-                self._step_hint(t_model[k])
-                try:
+                with self._step_hint(t_model[k]):
                     eps, sc = self._cfg_eps(x, conditioning, t, unconditional_conditioning, scale)
-                finally:
-                    self._step_hint(None)
                 second = plan["order"][k] == 2
                 x, x0 = ops.dpmpp_cfg_step(x, eps, x0_prev if second else None, sc, plan["sigma_s"][k], plan["alpha_s"][k],
                                            plan["ratio"][k], plan["c"][k], plan["c_half"][k] if second else 0.0,

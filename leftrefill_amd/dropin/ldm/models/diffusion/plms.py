@@ -51,12 +51,7 @@ class PLMSSampler(CFGModelEval):
                unconditional_conditioning=None, dynamic_threshold=None, **kwargs):
         if isinstance(conditioning, list):
             _unsupported("list conditioning (the multi-conditioning NVS sampler)")
-        if conditioning is not None:
-            c0 = conditioning[list(conditioning.keys())[0]] if isinstance(conditioning, dict) else conditioning
-            while isinstance(c0, list):
-                c0 = c0[0]
-            if c0.shape[0] != batch_size:
-                print(f"Warning: Got {c0.shape[0]} conditionings but batch-size is {batch_size}")
+        self._warn_conditioning_count(conditioning, batch_size)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
         return self.plms_sampling(conditioning, (batch_size, C, H, W), callback=callback, img_callback=img_callback,
@@ -134,11 +129,8 @@ class PLMSSampler(CFGModelEval):
         return img, intermediates
 
     def _eval(self, x, c, t, t_host, uc, scale):
-        self._step_hint(t_host)
-        try:
+        with self._step_hint(t_host):
             return self._cfg_eps(x, c, t, uc, scale)
-        finally:
-            self._step_hint(None)
 
     @torch.no_grad()
     def p_sample_plms(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,

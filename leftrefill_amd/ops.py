@@ -842,95 +842,72 @@ def mv_scatter(seq, b, v, s):
     return x
 
 
-def ddim_cfg_step(x, eps, noise, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at):
-    """x [B,...] fp32; eps [2B,...] fp16|fp32 (uncond first); returns (x_prev, pred_x0) fp32."""
-    lib = _lib.load()
-    assert x.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous()
-    assert eps.numel() == 2 * x.numel() and eps.dtype in (torch.float16, torch.bfloat16, torch.float32)
-    if noise is not None:
-        noise = noise.float().contiguous()
-    x_prev = torch.empty_like(x)
-    pred = torch.empty_like(x)
-    _lib.check(_fn(lib, "lr_ddim_cfg_step", torch.bfloat16 if eps.dtype == torch.bfloat16 else torch.float16)(_p(x), _p(eps), int(eps.dtype == torch.float32), _p(noise), _p(x_prev), _p(pred),
-                                    x.numel(), float(cfg_scale), float(a_t), float(a_prev), float(sigma_t),
-                                    float(sqrt_one_minus_at), _stream()), "ddim_cfg_step")
-    return x_prev, pred
-
-
 def _eps16(eps):
     return torch.bfloat16 if eps.dtype == torch.bfloat16 else torch.float16
+
+
+def _cfg_step(name, x, eps, n_eps, extra, outs, scalars):
+    """The call path of the fused CFG sampler steps: lr_<name>[_bf16](x, eps, eps_is_f32, *extra, *outputs, numel, *scalars,
+    stream), the 16-bit twin chosen by eps.dtype.  x [B,...] fp32; eps [n_eps B,...] fp16|bf16|fp32; extra: the step's own
+    arguments in front of the outputs -- an optional fp32 stream (tensor or None: its fp32 contiguous form is passed) or a plain
+    ctypes value; outs: one flag per output, False = not wanted (null).  Returns the fp32 outputs, each like x (None where not
+    wanted), in the order of the C signature."""
+    lib = _lib.load()
+    assert x.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous()
+    assert eps.numel() == n_eps * x.numel() and eps.dtype in (torch.float16, torch.bfloat16, torch.float32)
+    extra = [a.float().contiguous() if torch.is_tensor(a) else a for a in extra]
+    outs = [torch.empty_like(x) if wanted else None for wanted in outs]
+    _lib.check(_fn(lib, "lr_" + name, _eps16(eps))(
+        _p(x), _p(eps), int(eps.dtype == torch.float32), *[_p(a) if a is None or torch.is_tensor(a) else a for a in extra],
+        *[_p(o) for o in outs], x.numel(), *[float(v) for v in scalars], _stream()), name)
+    return outs
+
+
+def ddim_cfg_step(x, eps, noise, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at):
+    """x [B,...] fp32; eps [2B,...] fp16|fp32 (uncond first); returns (x_prev, pred_x0) fp32."""
+    x_prev, pred = _cfg_step("ddim_cfg_step", x, eps, 2, (noise,), (True, True),
+                             (cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at))
+    return x_prev, pred
 
 
 def plms_cfg_step(x, eps, hist, weights, divisor, cfg_scale, a_t, a_prev, sqrt_one_minus_at, write_e=True):
     """One PLMS update (sigma = 0).  x [B,...] fp32; eps [2B,...] fp16|bf16|fp32 (uncond first); hist: up to 3 fp32 tensors
     like x, newest first; weights: len(hist) + 1 integer weights, divisor their common denominator.
     Returns (x_prev, pred_x0, e): e is this evaluation's CFG-combined eps in fp32 (None unless write_e)."""
-    lib = _lib.load()
-    assert x.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous()
-    assert eps.numel() == 2 * x.numel() and eps.dtype in (torch.float16, torch.bfloat16, torch.float32)
     assert len(hist) <= 3 and len(weights) == len(hist) + 1
     for h in hist:
         assert h.dtype == torch.float32 and h.is_contiguous() and h.numel() == x.numel() and h.device == x.device
     ptrs = (ctypes.c_void_p * 3)(*[h.data_ptr() for h in hist], *([None] * (3 - len(hist))))
     w = (ctypes.c_float * 4)(*[float(w_) for w_ in weights], *([0.0] * (4 - len(weights))))
-    x_prev = torch.empty_like(x)
-    pred = torch.empty_like(x)
-    e = torch.empty_like(x) if write_e else None
-    _lib.check(_fn(lib, "lr_plms_cfg_step", _eps16(eps))(_p(x), _p(eps), int(eps.dtype == torch.float32), ctypes.addressof(ptrs),
-                                                         len(hist), ctypes.addressof(w),
-                                                         float(divisor), _p(e), _p(x_prev), _p(pred), x.numel(), float(cfg_scale),
-                                                         float(a_t), float(a_prev), float(sqrt_one_minus_at), _stream()),
-               "plms_cfg_step")
+    e, x_prev, pred = _cfg_step("plms_cfg_step", x, eps, 2, (ctypes.addressof(ptrs), len(hist), ctypes.addressof(w), float(divisor)),
+                                (write_e, True, True), (cfg_scale, a_t, a_prev, sqrt_one_minus_at))
     return x_prev, pred, e
 
 
 def dpmpp_cfg_step(x, eps, x0_prev, cfg_scale, sigma_s, alpha_s, ratio, c, c_half=0.0, inv_r0=0.0):
     """One DPM-Solver++ multistep update: order 1 when x0_prev is None, else order 2.  x [B,...] fp32; eps [2B,...]
     fp16|bf16|fp32 (uncond first); x0_prev fp32 like x.  Returns (x_next, x0) -- x0 is this step's data prediction."""
-    lib = _lib.load()
-    assert x.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous()
-    assert eps.numel() == 2 * x.numel() and eps.dtype in (torch.float16, torch.bfloat16, torch.float32)
     if x0_prev is not None:
         assert x0_prev.dtype == torch.float32 and x0_prev.is_contiguous() and x0_prev.numel() == x.numel()
-    x_next = torch.empty_like(x)
-    x0 = torch.empty_like(x)
-    _lib.check(_fn(lib, "lr_dpmpp_cfg_step", _eps16(eps))(_p(x), _p(eps), int(eps.dtype == torch.float32), _p(x0_prev), _p(x0),
-                                                          _p(x_next), x.numel(), float(cfg_scale), float(sigma_s), float(alpha_s),
-                                                          float(ratio), float(c), float(c_half), float(inv_r0), _stream()),
-               "dpmpp_cfg_step")
+    x0, x_next = _cfg_step("dpmpp_cfg_step", x, eps, 2, (x0_prev,), (True, True),
+                           (cfg_scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0))
     return x_next, x0
 
 
 def ddim_inv_cfg_step(x, eps, cfg_scale, c1, c2):
     """One DDIM inversion step (DDIMSampler.encode): x_next = c1 x + c2 e with e = e_u + s (e_c - e_u).  x [B,...] fp32;
     eps [2B,...] fp16|bf16|fp32 (uncond first); c1, c2: the host coefficients (python / float64 values).  Returns x_next fp32."""
-    lib = _lib.load()
-    assert x.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous()
-    assert eps.numel() == 2 * x.numel() and eps.dtype in (torch.float16, torch.bfloat16, torch.float32)
-    if eps.dtype != torch.float32:      # the reference casts the 0-dim float64 c2 to eps's dtype: round once, from float64
+    if eps.dtype in HALF_TYPES:      # the reference casts the 0-dim float64 c2 to eps's dtype: round once, from float64
         c2 = torch.tensor(float(c2), dtype=torch.float64).to(eps.dtype).item()
-    x_next = torch.empty_like(x)
-    _lib.check(_fn(lib, "lr_ddim_inv_cfg_step", _eps16(eps))(_p(x), _p(eps), int(eps.dtype == torch.float32), _p(x_next), x.numel(),
-                                                             float(cfg_scale), float(c1), float(c2), _stream()),
-               "ddim_inv_cfg_step")
-    return x_next
+    return _cfg_step("ddim_inv_cfg_step", x, eps, 2, (), (True,), (cfg_scale, c1, c2))[0]
 
 
 def ddim_cfg3_step(x, eps, noise, cfg_scale, cond_weight, a_t, a_prev, sigma_t, sqrt_one_minus_at):
     """Three-way guidance + DDIM update (StructureDDIMSampler.p_sample_ddim_guide).  x [B,...] fp32; eps [3B,...] fp16|bf16|fp32
     in the order uncond, cond, cond_simple; noise fp32 like x or None.  Returns (x_prev, pred_x0) fp32."""
-    lib = _lib.load()
-    assert x.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous()
-    assert eps.numel() == 3 * x.numel() and eps.dtype in (torch.float16, torch.bfloat16, torch.float32)
-    if noise is not None:
-        noise = noise.float().contiguous()
-    x_prev = torch.empty_like(x)
-    pred = torch.empty_like(x)
     w = float(cond_weight)
-    _lib.check(_fn(lib, "lr_ddim_cfg3_step", _eps16(eps))(_p(x), _p(eps), int(eps.dtype == torch.float32), _p(noise), _p(x_prev),
-                                                          _p(pred), x.numel(), float(cfg_scale), w, 1 - w, float(a_t),
-                                                          float(a_prev), float(sigma_t), float(sqrt_one_minus_at), _stream()),
-               "ddim_cfg3_step")
+    x_prev, pred = _cfg_step("ddim_cfg3_step", x, eps, 3, (noise,), (True, True),
+                             (cfg_scale, w, 1 - w, a_t, a_prev, sigma_t, sqrt_one_minus_at))
     return x_prev, pred
 
 
