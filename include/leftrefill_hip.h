@@ -424,6 +424,27 @@ int lr_ddim_cfg3_step(const float* x, const void* eps, int eps_is_f32, const flo
                       int64_t numel, float cfg_scale, float cond_weight, float one_minus_cond_weight, float a_t, float a_prev,
                       float sigma_t, float sqrt_one_minus_at, lr_stream_t s);
 
+/* ---- ancestral DDPM posterior step (ABI 30) -----------------------------------------------------------------------------
+ * replaces: LatentDiffusion.p_sample after the model call (ddpm.py:950-960 predict_start_from_noise / clamp / q_posterior, 986-997
+ *           noise and nonzero mask) and, with a known region, the blend of p_sample_loop / progressive_denoising
+ *           (ddpm.py:1093-1095, 1044-1047), op by op in fp32 (no fused multiply-add):
+ *             x_recon = sqrt_recip_ac x - sqrt_recipm1_ac eps;  clamp to [-1, 1] if clip_denoised
+ *             x_prev  = coef1 x_recon + coef2 x + sigma noise
+ *             x_prev  = (sqrt_ac known_x0 + sqrt_one_minus_ac known_noise) mask + (1 - mask) x_prev        if mask
+ * x, noise, x_prev, x0_out (= x_recon, may be NULL), known_x0, known_noise: fp32 [numel]; eps: ONE slab [numel] fp16 (bf16 in
+ * the twin) or fp32 (eps_is_f32), widened to fp32 on load -- the ancestral sampler has no classifier-free guidance.
+ * The coefficients are the fp32 table entries at the step's timestep, read on the HOST (no device->host sync in the loop):
+ * sqrt_recip(m1)_alphas_cumprod[t], posterior_mean_coef1/2[t], sigma = (t != 0) exp(0.5 posterior_log_variance_clipped[t]) formed
+ * in fp32; a temperature is applied to `noise` by the caller.  noise may be NULL when sigma == 0 (t == 0: x_prev is the mean).
+ * They are scalars: a batch whose samples sit at different timesteps (a direct p_sample call) is one call per run of equal t on
+ * that run's slice -- the sampling loops step the whole batch at one t, so they issue one launch.
+ * mask, known_x0, known_noise: all three or none.  mask_hw > 0: mask is [numel / mask_chw][mask_hw] and broadcasts over the
+ * mask_chw / mask_hw channels of each sample ([B,1,H,W] against [B,C,H,W]); mask_hw == 0: mask is fp32 [numel]. */
+int lr_ddpm_step(const float* x, const void* eps, int eps_is_f32, const float* noise, const float* known_x0,
+                 const float* known_noise, const float* mask, int64_t mask_chw, int64_t mask_hw, int clip_denoised, float* x_prev,
+                 float* x0_out, int64_t numel, float sqrt_recip_ac, float sqrt_recipm1_ac, float coef1, float coef2, float sigma,
+                 float sqrt_ac, float sqrt_one_minus_ac, lr_stream_t s);
+
 /* ---- DDIM forward noising with a per-sample step (ABI 28) ----------------------------------------------------------
  * replaces: DDIMSampler.stochastic_encode (ddim.py:436-449): out[b] = sa[b] x0[b] + s1ma[b] noise[b] with
  *           sa = sqrt(ddim_alphas)[t[b]], s1ma = ddim_sqrt_one_minus_alphas[t[b]] (extract_into_tensor), all fp32.
@@ -548,6 +569,10 @@ int lr_ddim_inv_cfg_step_bf16(const float* x, const void* eps, int eps_is_f32, f
 int lr_ddim_cfg3_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* noise, float* x_prev, float* pred_x0,
     int64_t numel, float cfg_scale, float cond_weight, float one_minus_cond_weight, float a_t, float a_prev, float sigma_t,
     float sqrt_one_minus_at, lr_stream_t s);
+int lr_ddpm_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* noise, const float* known_x0,
+    const float* known_noise, const float* mask, int64_t mask_chw, int64_t mask_hw, int clip_denoised, float* x_prev,
+    float* x0_out, int64_t numel, float sqrt_recip_ac, float sqrt_recipm1_ac, float coef1, float coef2, float sigma,
+    float sqrt_ac, float sqrt_one_minus_ac, lr_stream_t s);
 int lr_geglu_fwd_bf16(const lr_half* pre, lr_half* out, int M, int H, lr_stream_t s);
 int lr_geglu_bwd_bf16(const lr_half* pre, const lr_half* dy, lr_half* dpre, int M, int H, lr_stream_t s);
 int lr_sumpool2x2_bf16(const lr_half* x, lr_half* y, int N, int H, int W, int C, lr_stream_t s);

@@ -205,7 +205,8 @@ __global__ void row_copy_kernel(const RowCopyJobs J) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Fused sampler updates (DDIM, PLMS, DPM-Solver++, DDIM inversion, three-way DDIM): CFG combine + update of the fp32 state, one pass.
+// Fused sampler updates (DDIM, PLMS, DPM-Solver++, DDIM inversion, three-way DDIM: CFG combine + update of the fp32 state; ancestral
+// DDPM: posterior step of one eps), one pass.
 // sampler_step_kernel owns the grid-stride loop and the loads of the eps slabs; a Step (below) holds its fp32 streams and scalars
 // and loads, updates and stores the V elements of one thread (an optional stream is loaded where it is used, so each Step compiles
 // to the code of a hand-written kernel).  V = 4: 16-byte fp32 / 8-byte 16-bit accesses (numel % 4 == 0, aligned buffers), V = 1: scalar.
@@ -454,6 +455,47 @@ struct DdimCfg3Step {
   }
 };
 
+// Ancestral DDPM posterior step (LatentDiffusion.p_sample after the model call, ddpm.py:950-960, 986-997): one eps slab, no guidance.
+//   x_recon = recip x - recipm1 e, clamped to [-1, 1] if clip;  mean = coef1 x_recon + coef2 x;  x_prev = mean + sigma noise
+// sigma = nonzero(t) exp(0.5 logvar_clipped[t]) from the host (noise null: sigma == 0, x_prev is exactly the mean).  With a known
+// region (in[2..4] set; p_sample_loop, ddpm.py:1093-1095) the same pass blends: x_prev = (sa x0 + s1ma qnoise) m + (1 - m) x_prev.
+struct DdpmStep {
+  static constexpr int NE = 1, MAX_V = 4;
+  const float* in[5];      // x, noise (optional), then all or none of: known x0, its q_sample noise, mask
+  float* out[2];           // x_prev, x_recon (optional)
+  long long mask_chw, mask_hw;   // mask_hw > 0: mask [B][hw] broadcast over the channels of x [B][chw / hw][hw]; 0: mask shaped like x
+  int clip;
+  float recip, recipm1, coef1, coef2, sigma, sa, s1ma;
+  template <typename EpsT, typename T, int V>
+  __device__ __forceinline__ void apply(long long i, const float (&e)[NE][V]) const {
+#pragma clang fp contract(off)
+    float xv[V], nz[V], k0[V], kn[V], xr[V], xp[V];
+    ld_f32<V>(in[0], i, xv);
+    if (in[1]) ld_f32<V>(in[1], i, nz);
+    if (in[4]) {
+      ld_f32<V>(in[2], i, k0);
+      ld_f32<V>(in[3], i, kn);
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      float r = recip * xv[k] - recipm1 * e[0][k];
+      if (clip) r = r < -1.0f ? -1.0f : (r > 1.0f ? 1.0f : r);      // NaN passes through, as in torch.clamp
+      xr[k] = r;
+      float v = coef1 * r + coef2 * xv[k];
+      if (in[1]) v = v + sigma * nz[k];
+      if (in[4]) {
+        const long long j = i + k;
+        const float m = in[4][mask_hw > 0 ? (j / mask_chw) * mask_hw + j % mask_hw : j];
+        const float orig = sa * k0[k] + s1ma * kn[k];
+        v = orig * m + (1.0f - m) * v;
+      }
+      xp[k] = v;
+    }
+    if (out[1]) st_f32<V>(out[1], i, xr);
+    st_f32<V>(out[0], i, xp);
+  }
+};
+
 // DDIMSampler.stochastic_encode (ddim.py:436-449): out = sa[b] x0 + s1ma[b] noise, sample b = blockIdx.y; the coefficient pairs
 // are kernel arguments (at most LR_Q_SAMPLE_MAX_B samples per launch).
 struct QSampleCoefs { float sa[LR_Q_SAMPLE_MAX_B]; float s1ma[LR_Q_SAMPLE_MAX_B]; };
@@ -492,7 +534,7 @@ static inline int grid_for(long long total, int block, int cap = 4096) {
   return (int)g;
 }
 
-extern "C" int lr_abi_version(void) { return 29; }
+extern "C" int lr_abi_version(void) { return 30; }
 
 #ifdef LR_DEV_VARIANTS
 // developer build only: name -> value table behind LR_DEV (common.h); set through lr_dev_set by the Python front end
@@ -673,6 +715,24 @@ static int lr_ddim_cfg3_step_t(const float* x, const void* eps, int eps_is_f32, 
   if (!x || !eps || !x_prev || !pred_x0 || numel <= 0) return LR_E_ARG;
   const DdimCfg3Step st{{x, noise}, {x_prev, pred_x0}, cfg_scale, cond_weight, one_minus_cond_weight,
                         ddim_coefs(a_t, a_prev, sigma_t, sqrt_one_minus_at)};
+  return launch_sampler_step<T>(st, eps, eps_is_f32, numel, s);
+}
+
+template <typename T>
+static int lr_ddpm_step_t(const float* x, const void* eps, int eps_is_f32, const float* noise, const float* known_x0,
+                          const float* known_noise, const float* mask, int64_t mask_chw, int64_t mask_hw, int clip_denoised,
+                          float* x_prev, float* x0_out, int64_t numel, float sqrt_recip_ac, float sqrt_recipm1_ac, float coef1,
+                          float coef2, float sigma, float sqrt_ac, float sqrt_one_minus_ac, lr_stream_t s) {
+  if (!x || !eps || !x_prev || numel <= 0 || (!noise && sigma != 0.f)) return LR_E_ARG;
+  if (mask) {      // known-region blend: all three streams, and a mask that tiles x exactly
+    if (!known_x0 || !known_noise || mask_hw < 0) return LR_E_ARG;
+    if (mask_hw > 0 && (mask_chw <= 0 || mask_chw % mask_hw || numel % mask_chw)) return LR_E_ARG;
+  } else if (known_x0 || known_noise) {
+    return LR_E_ARG;
+  }
+  const DdpmStep st{{x, sigma != 0.f ? noise : nullptr, known_x0, known_noise, mask}, {x_prev, x0_out}, (long long)mask_chw,
+                    (long long)mask_hw, clip_denoised, sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, sigma, sqrt_ac,
+                    sqrt_one_minus_ac};
   return launch_sampler_step<T>(st, eps, eps_is_f32, numel, s);
 }
 
@@ -898,6 +958,8 @@ extern "C" int lr_ddim_inv_cfg_step(const float* x, const void* eps, int eps_is_
 extern "C" int lr_ddim_inv_cfg_step_bf16(const float* x, const void* eps, int eps_is_f32, float* x_next, int64_t numel, float cfg_scale, float c1, float c2, lr_stream_t s) { return lr_ddim_inv_cfg_step_t<bf16>(x, eps, eps_is_f32, x_next, numel, cfg_scale, c1, c2, s); }
 extern "C" int lr_ddim_cfg3_step(const float* x, const void* eps, int eps_is_f32, const float* noise, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float cond_weight, float one_minus_cond_weight, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, lr_stream_t s) { return lr_ddim_cfg3_step_t<f16>(x, eps, eps_is_f32, noise, x_prev, pred_x0, numel, cfg_scale, cond_weight, one_minus_cond_weight, a_t, a_prev, sigma_t, sqrt_one_minus_at, s); }
 extern "C" int lr_ddim_cfg3_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* noise, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float cond_weight, float one_minus_cond_weight, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, lr_stream_t s) { return lr_ddim_cfg3_step_t<bf16>(x, eps, eps_is_f32, noise, x_prev, pred_x0, numel, cfg_scale, cond_weight, one_minus_cond_weight, a_t, a_prev, sigma_t, sqrt_one_minus_at, s); }
+extern "C" int lr_ddpm_step(const float* x, const void* eps, int eps_is_f32, const float* noise, const float* known_x0, const float* known_noise, const float* mask, int64_t mask_chw, int64_t mask_hw, int clip_denoised, float* x_prev, float* x0_out, int64_t numel, float sqrt_recip_ac, float sqrt_recipm1_ac, float coef1, float coef2, float sigma, float sqrt_ac, float sqrt_one_minus_ac, lr_stream_t s) { return lr_ddpm_step_t<f16>(x, eps, eps_is_f32, noise, known_x0, known_noise, mask, mask_chw, mask_hw, clip_denoised, x_prev, x0_out, numel, sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, sigma, sqrt_ac, sqrt_one_minus_ac, s); }
+extern "C" int lr_ddpm_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* noise, const float* known_x0, const float* known_noise, const float* mask, int64_t mask_chw, int64_t mask_hw, int clip_denoised, float* x_prev, float* x0_out, int64_t numel, float sqrt_recip_ac, float sqrt_recipm1_ac, float coef1, float coef2, float sigma, float sqrt_ac, float sqrt_one_minus_ac, lr_stream_t s) { return lr_ddpm_step_t<bf16>(x, eps, eps_is_f32, noise, known_x0, known_noise, mask, mask_chw, mask_hw, clip_denoised, x_prev, x0_out, numel, sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, sigma, sqrt_ac, sqrt_one_minus_ac, s); }
 extern "C" int lr_geglu_fwd(const lr_half* pre, lr_half* out, int M, int H, lr_stream_t s) { return lr_geglu_fwd_t<f16>(pre, out, M, H, s); }
 extern "C" int lr_geglu_fwd_bf16(const lr_half* pre, lr_half* out, int M, int H, lr_stream_t s) { return lr_geglu_fwd_t<bf16>(pre, out, M, H, s); }
 extern "C" int lr_geglu_bwd(const lr_half* pre, const lr_half* dy, lr_half* dpre, int M, int H, lr_stream_t s) { return lr_geglu_bwd_t<f16>(pre, dy, dpre, M, H, s); }

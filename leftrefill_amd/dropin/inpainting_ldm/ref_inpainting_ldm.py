@@ -12,7 +12,8 @@ from ldm.models.diffusion.ddpm import LatentInpaintDiffusion
 
 
 def make_sampler(name, model):
-    """"ddim" | "plms" | "dpm_solver" -> the drop-in sampler of that name over `model`."""
+    """"ddim" | "plms" | "dpm_solver" -> the drop-in sampler of that name over `model`.  ("ddpm", the ancestral sampler, is not a
+    sampler object: it lives on the model -- `LatentDiffusion.sample` -- and `RefInpaintLDM.sample_log` routes to it.)"""
     if name == "ddim":
         return DDIMSampler(model)
     if name == "plms":
@@ -21,7 +22,14 @@ def make_sampler(name, model):
     if name == "dpm_solver":
         from ldm.models.diffusion.dpm_solver import DPMSolverSampler
         return DPMSolverSampler(model)
-    raise ValueError(f"unknown sampler {name!r}: 'ddim', 'plms' or 'dpm_solver'")
+    if name == "ddpm":
+        raise ValueError("'ddpm' is the model's own ancestral sampler (model.sample / sample_log(sampler='ddpm')), not a sampler class")
+    raise ValueError(f"unknown sampler {name!r}: 'ddim', 'plms', 'dpm_solver' or 'ddpm'")
+
+
+def _ddpm_has_no_guidance(scale):
+    raise ValueError(f"sampler 'ddpm' (ancestral) has no classifier-free guidance: unconditional_guidance_scale={scale!r} would be "
+                     "dropped; use 1.0, or one of the guided samplers 'ddim', 'plms', 'dpm_solver'")
 
 
 class RefInpaintLDM(LatentInpaintDiffusion):
@@ -48,7 +56,11 @@ class RefInpaintLDM(LatentInpaintDiffusion):
 
     @torch.no_grad()
     def log_images(self, batch, N=4, ddim_steps=50, ddim_eta=0.0, unconditional_guidance_scale=9.0, sampler="ddim", **kwargs):
-        """sampler: "ddim" (the reference's), "plms" or "dpm_solver"; ddim_steps is the step count of any of them."""
+        """sampler: "ddim" (the reference's), "plms" or "dpm_solver"; ddim_steps is the step count of any of them.  "ddpm": the
+        ancestral sampler over the full schedule (ddim_steps is ignored), which has no guidance -- unconditional_guidance_scale must
+        be 1 (or 0: the empty-prompt condition)."""
+        if sampler == "ddpm" and unconditional_guidance_scale not in (0.0, 1.0):
+            _ddpm_has_no_guidance(unconditional_guidance_scale)
         use_ddim = ddim_steps is not None
         log = dict()
         z, c = self.get_input(batch, self.first_stage_key, bs=N)
@@ -74,7 +86,15 @@ class RefInpaintLDM(LatentInpaintDiffusion):
 
     @torch.no_grad()
     def sample_log(self, cond, batch_size, ddim, ddim_steps, sampler="ddim", **kwargs):
-        sampler = make_sampler(sampler, self)
         _, _, h, w = cond["c_concat"][0].shape
+        if sampler == "ddpm":
+            scale = kwargs.pop("unconditional_guidance_scale", 1.)
+            kwargs.pop("unconditional_conditioning", None)
+            if scale != 1.:
+                _ddpm_has_no_guidance(scale)
+            kwargs.pop("eta", None)      # a DDIM knob; the ancestral chain has its own variance
+            return self.sample(cond=cond, batch_size=batch_size, return_intermediates=True, verbose=False,
+                               shape=(batch_size, self.channels, h, w), **kwargs)
+        sampler = make_sampler(sampler, self)
         shape = (self.channels, h, w)   # latent size comes from c_concat (reference 77-79)
         return sampler.sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)

@@ -5,6 +5,9 @@ Keeps the reference's class names, constructor kwargs and attributes that the sa
 LatentFinetuneDiffusion 1512-1651, LatentInpaintDiffusion 1654-1701), minus the PyTorch-Lightning trainer hooks,
 EMA, logging and the unused upscale/depth variants (out of scope).
 
+The ancestral DDPM sampler lives here as in the reference (`LatentDiffusion.sample` / `p_sample_loop` / `p_sample` /
+`progressive_denoising` / `sample_log`, 937-1136): per timestep one replay of the captured UNet step and one lr_ddpm_step launch.
+
 On the hot path only `apply_model` -> `DiffusionWrapper.forward` ('hybrid': channel-concat of the noisy latent with
 [mask | masked-image latent], cross-attention context) -> `UNetModel.forward` is exercised; VAE encode/decode and the
 prompt encoder stay PyTorch-ROCm host code as the north star prescribes.
@@ -13,7 +16,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ldm.modules.diffusionmodules.util import extract_into_tensor, make_beta_schedule
+from leftrefill_amd import ops
+from ldm.models.diffusion.ddim import CFGModelEval, DDIMSampler
+from ldm.modules.diffusionmodules.util import extract_into_tensor, make_beta_schedule, noise_like
 from ldm.modules.distributions.distributions import DiagonalGaussianDistribution
 from ldm.util import default, exists, instantiate_from_config
 
@@ -113,6 +118,14 @@ class DDPM(nn.Module):
         alphas = 1. - betas
         post_var = (1 - self.v_posterior) * betas * (1. - ac_prev) / (1. - ac) + self.v_posterior * betas
         self.register_buffer("posterior_variance", f32(post_var))
+        # the posterior tables of the ancestral sampler (reference 185-189), float64 -> fp32.  Non-persistent: state_dict() keeps the
+        # keys it had before these tables existed, so checkpoints written by this package keep loading strictly; a reference
+        # checkpoint that carries the three keys goes through the tolerant loader, and the values are functions of betas anyway.
+        for name, val in (("posterior_log_variance_clipped", np.log(np.maximum(post_var, 1e-20))),
+                          ("posterior_mean_coef1", betas * np.sqrt(ac_prev) / (1. - ac)),
+                          ("posterior_mean_coef2", (1. - ac_prev) * np.sqrt(alphas) / (1. - ac))):
+            self.register_buffer(name, f32(val), persistent=False)
+        self._ddpm_host_tables = None
         if self.parameterization == "eps":
             lvlb = self.betas ** 2 / (2 * self.posterior_variance * f32(alphas) * (1 - self.alphas_cumprod))
         elif self.parameterization == "x0":
@@ -136,6 +149,34 @@ class DDPM(nn.Module):
         noise = default(noise, lambda: torch.randn_like(x_start))
         return (extract_into_tensor(self.sqrt_alphas_cumprod, t, x_start.shape) * x_start +
                 extract_into_tensor(self.sqrt_one_minus_alphas_cumprod, t, x_start.shape) * noise)
+
+    def q_mean_variance(self, x_start, t):
+        """q(x_t | x_0): (mean, variance, log_variance) (reference 283-293)"""
+        mean = extract_into_tensor(self.sqrt_alphas_cumprod, t, x_start.shape) * x_start
+        variance = extract_into_tensor(1.0 - self.alphas_cumprod, t, x_start.shape)
+        log_variance = extract_into_tensor(self.log_one_minus_alphas_cumprod, t, x_start.shape)
+        return mean, variance, log_variance
+
+    def predict_start_from_noise(self, x_t, t, noise):
+        """reference 295-299"""
+        return (extract_into_tensor(self.sqrt_recip_alphas_cumprod, t, x_t.shape) * x_t -
+                extract_into_tensor(self.sqrt_recipm1_alphas_cumprod, t, x_t.shape) * noise)
+
+    def q_posterior(self, x_start, x_t, t):
+        """q(x_{t-1} | x_t, x_0): (mean, variance, log_variance_clipped) (reference 315-322)"""
+        posterior_mean = (extract_into_tensor(self.posterior_mean_coef1, t, x_t.shape) * x_start +
+                          extract_into_tensor(self.posterior_mean_coef2, t, x_t.shape) * x_t)
+        posterior_variance = extract_into_tensor(self.posterior_variance, t, x_t.shape)
+        posterior_log_variance_clipped = extract_into_tensor(self.posterior_log_variance_clipped, t, x_t.shape)
+        return posterior_mean, posterior_variance, posterior_log_variance_clipped
+
+    def p_sample_loop(self, *args, **kwargs):
+        raise NotImplementedError("DDPM.p_sample_loop (unconditional) is not supported by this build: the UNet always has a "
+                                  "context; use LatentDiffusion.p_sample_loop / sample")
+
+    def sample(self, *args, **kwargs):
+        raise NotImplementedError("DDPM.sample (unconditional) is not supported by this build: the UNet always has a context; "
+                                  "use LatentDiffusion.sample")
 
     def get_input(self, batch, k):
         x = batch[k]
@@ -251,6 +292,215 @@ class LatentDiffusion(DDPM):
         if isinstance(out, tuple) and not return_ids:
             return out[0]
         return out
+
+    # ---- ancestral DDPM sampling (reference 937-1136) -------------------------------------------------------------------------
+    # Per step: one model evaluation at batch B (a replay of the captured UNet step, the one a scale-1 DDIM run of the same batch
+    # and conditioning uses) and ONE lr_ddpm_step launch, which also does the known-region blend of a masked run.  The loops step
+    # the whole batch at one timestep they know on the host, so nothing is read back from the device; a direct p_sample call
+    # reads its `t` back once and issues one launch per run of equal t.
+    def _ddpm_unsupported(self, who, **flags):
+        bad = [k for k, v in flags.items() if v]
+        if bad:
+            raise NotImplementedError(f"{who}: {' / '.join(bad)} is not supported by this build (eps-parameterisation, no score "
+                                      "corrector, no quantisation of the denoised latent, no shortened conditioning schedule)")
+        if self.parameterization != "eps":
+            raise NotImplementedError(f"{who}: parameterization {self.parameterization!r} is not supported by this build "
+                                      "(LeftRefill samples in the eps-parameterisation)")
+
+    def _ddpm_tables(self):
+        """The fp32 tables the posterior step reads, on the host: one download per model (and per schedule), not per step.
+        std = exp(0.5 logvar) is formed in fp32 in the reference's order, (0.5 * v).exp() on an fp32 value."""
+        tab = self._ddpm_host_tables
+        if tab is None or tab["src"] is not self.posterior_log_variance_clipped:
+            host = lambda b: b.detach().to(torch.float32).cpu()
+            lv = host(self.posterior_log_variance_clipped)
+            tab = {"src": self.posterior_log_variance_clipped,
+                   "recip": host(self.sqrt_recip_alphas_cumprod).tolist(), "recipm1": host(self.sqrt_recipm1_alphas_cumprod).tolist(),
+                   "coef1": host(self.posterior_mean_coef1).tolist(), "coef2": host(self.posterior_mean_coef2).tolist(),
+                   "std": (0.5 * lv).exp().tolist(), "sa": host(self.sqrt_alphas_cumprod).tolist(),
+                   "s1ma": host(self.sqrt_one_minus_alphas_cumprod).tolist()}
+            self._ddpm_host_tables = tab
+        return tab
+
+    def _model_eval(self):
+        """The samplers' machinery around one model evaluation (precomputed embedding rows, host-named timestep), over this model."""
+        ev = CFGModelEval()
+        ev.model = self
+        return ev
+
+    def _posterior_step(self, x, eps, t_host, noise, clip_denoised, return_x0, known=None):
+        tab = self._ddpm_tables()
+        i = int(t_host)
+        if known is not None:
+            known = (known[0], known[1], known[2], tab["sa"][i], tab["s1ma"][i])
+        return ops.ddpm_step(x, eps.contiguous(), noise, tab["recip"][i], tab["recipm1"][i], tab["coef1"][i], tab["coef2"][i],
+                             0.0 if i == 0 else tab["std"][i], clip_denoised=clip_denoised, return_x0=return_x0, known=known)
+
+    def _p_sample(self, ev, x, c, t, t_host, clip_denoised=False, repeat_noise=False, return_x0=False, temperature=1.,
+                  noise_dropout=0., known=None):
+        """One ancestral step.  t_host: the timestep every entry of `t` holds, as a host integer (the loops), or None (read `t`
+        back).  known: None or (x0, mask) -- the blend with q_sample(x0, t) of the masked loops, whose randn_like is drawn AFTER
+        the step's own noise, as in the reference."""
+        x = x.float().contiguous()
+        with ev._step_hint(t_host):
+            eps = self.apply_model(x, t, c)
+        noise = noise_like(x.shape, x.device, repeat_noise)      # drawn every step like the reference (986), also at t == 0
+        if temperature != 1.:
+            noise = noise * temperature
+        if noise_dropout > 0.:
+            noise = torch.nn.functional.dropout(noise, p=noise_dropout)
+        if known is not None:
+            x0, mask = known
+            known = (x0.float().contiguous(), torch.randn_like(x0).float(), mask.to(device=x.device, dtype=torch.float32).contiguous())
+        if t_host is not None:
+            return self._posterior_step(x, eps, t_host, noise, clip_denoised, return_x0, known)
+        assert known is None
+        ts = [int(v) for v in t.tolist()]
+        assert len(ts) == x.shape[0], "one timestep per sample"
+        eps = eps.contiguous()
+        prev, rec, b0 = [], [], 0
+        while b0 < len(ts):          # one launch per run of equal t
+            b1 = b0 + 1
+            while b1 < len(ts) and ts[b1] == ts[b0]:
+                b1 += 1
+            xp, xr = self._posterior_step(x[b0:b1], eps[b0:b1], ts[b0], noise[b0:b1].contiguous(), clip_denoised, return_x0)
+            prev.append(xp)
+            rec.append(xr)
+            b0 = b1
+        one = len(prev) == 1
+        return (prev[0] if one else torch.cat(prev)), ((rec[0] if one else torch.cat(rec)) if return_x0 else None)
+
+    def p_mean_variance(self, x, c, t, clip_denoised: bool, return_codebook_ids=False, quantize_denoised=False, return_x0=False,
+                        score_corrector=None, corrector_kwargs=None):
+        """(model_mean, posterior_variance, posterior_log_variance[, x_recon]) in plain torch (reference 937-966); the sampling
+        loops do not come through here -- their step is the fused kernel of `p_sample`."""
+        self._ddpm_unsupported("LatentDiffusion.p_mean_variance", return_codebook_ids=return_codebook_ids,
+                               quantize_denoised=quantize_denoised, score_corrector=score_corrector is not None)
+        model_out = self.apply_model(x, t, c)
+        x_recon = self.predict_start_from_noise(x, t=t, noise=model_out)
+        if clip_denoised:
+            x_recon.clamp_(-1., 1.)
+        model_mean, posterior_variance, posterior_log_variance = self.q_posterior(x_start=x_recon, x_t=x, t=t)
+        if return_x0:
+            return model_mean, posterior_variance, posterior_log_variance, x_recon
+        return model_mean, posterior_variance, posterior_log_variance
+
+    @torch.no_grad()
+    def p_sample(self, x, c, t, clip_denoised=False, repeat_noise=False, return_codebook_ids=False, quantize_denoised=False,
+                 return_x0=False, temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None):
+        """x_{t-1} ~ p(x_{t-1} | x_t) (reference 969-997): model call + one lr_ddpm_step per run of equal `t` (read back once here;
+        the loops name their timestep on the host instead).  Returns x_prev, or (x_prev, x0) with return_x0."""
+        self._ddpm_unsupported("LatentDiffusion.p_sample", return_codebook_ids=return_codebook_ids,
+                               quantize_denoised=quantize_denoised, score_corrector=score_corrector is not None)
+        x_prev, x0 = self._p_sample(self._model_eval(), x, c, t, None, clip_denoised, repeat_noise, return_x0, temperature,
+                                    noise_dropout)
+        return (x_prev, x0) if return_x0 else x_prev
+
+    @staticmethod
+    def _slice_cond(cond, batch_size):
+        if cond is None:
+            return None
+        if isinstance(cond, dict):
+            return {key: cond[key][:batch_size] if not isinstance(cond[key], list) else [x[:batch_size] for x in cond[key]]
+                    for key in cond}
+        return [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
+
+    def _ancestral_chain(self, who, cond, img, timesteps, step_kwargs, mask, x0, quantize_denoised, score_corrector=None):
+        """Generator over the chain timesteps-1 .. 0: yields (i, img, x0_partial) after each step."""
+        self._ddpm_unsupported(who, quantize_denoised=quantize_denoised, score_corrector=score_corrector is not None,
+                               shorten_cond_schedule=getattr(self, "shorten_cond_schedule", False))
+        b = img.shape[0]
+        known = None
+        if mask is not None:
+            assert x0 is not None
+            known = (x0, mask)
+        ev = self._model_eval()
+        ev._prepare_cfg_inputs(cond, None, 1.)
+        ev._prepare_timesteps(range(timesteps))
+        for i in reversed(range(0, timesteps)):
+            ts = torch.full((b,), i, device=img.device, dtype=torch.long)
+            img, x0_partial = self._p_sample(ev, img, cond, ts, i, known=known, **step_kwargs(i))
+            yield i, img, x0_partial
+
+    @torch.no_grad()
+    def progressive_denoising(self, cond, shape, verbose=True, callback=None, quantize_denoised=False, img_callback=None,
+                              mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
+                              batch_size=None, x_T=None, start_T=None, log_every_t=None):
+        """The chain with the x0 predictions as intermediates (reference 1000-1053).  Returns (img, intermediates)."""
+        if not log_every_t:
+            log_every_t = self.log_every_t
+        timesteps = self.num_timesteps
+        if batch_size is not None:
+            shape = [batch_size] + list(shape)
+        else:
+            batch_size = shape[0]
+        img = torch.randn(shape, device=self.device) if x_T is None else x_T
+        intermediates = []
+        cond = self._slice_cond(cond, batch_size)
+        if start_T is not None:
+            timesteps = min(timesteps, start_T)
+        if type(temperature) == float:
+            temperature = [temperature] * timesteps
+        kw = lambda i: dict(clip_denoised=self.clip_denoised, return_x0=True, temperature=temperature[i],
+                            noise_dropout=noise_dropout)
+        for i, img, x0_partial in self._ancestral_chain("LatentDiffusion.progressive_denoising", cond, img, timesteps, kw, mask, x0,
+                                                        quantize_denoised, score_corrector):
+            if i % log_every_t == 0 or i == timesteps - 1:
+                intermediates.append(x0_partial)
+            if callback:
+                callback(i)
+            if img_callback:
+                img_callback(img, i)
+        return img, intermediates
+
+    @torch.no_grad()
+    def p_sample_loop(self, cond, shape, return_intermediates=False, x_T=None, verbose=True, callback=None, timesteps=None,
+                      quantize_denoised=False, mask=None, x0=None, img_callback=None, start_T=None, log_every_t=None):
+        """The ancestral chain from x_T over `timesteps` (default: all) steps (reference 1056-1104)."""
+        if not log_every_t:
+            log_every_t = self.log_every_t
+        img = torch.randn(shape, device=self.betas.device) if x_T is None else x_T
+        intermediates = [img]
+        if timesteps is None:
+            timesteps = self.num_timesteps
+        if start_T is not None:
+            timesteps = min(timesteps, start_T)
+        if mask is not None:
+            assert x0 is not None
+            assert x0.shape[2:3] == mask.shape[2:3], "mask and x0 differ in height (the reference's check, 1081)"
+        kw = lambda i: dict(clip_denoised=self.clip_denoised)
+        for i, img, _ in self._ancestral_chain("LatentDiffusion.p_sample_loop", cond, img, timesteps, kw, mask, x0,
+                                               quantize_denoised):
+            if i % log_every_t == 0 or i == timesteps - 1:
+                intermediates.append(img)
+            if callback:
+                callback(i)
+            if img_callback:
+                img_callback(img, i)
+        if return_intermediates:
+            return img, intermediates
+        return img
+
+    @torch.no_grad()
+    def sample(self, cond, batch_size=16, return_intermediates=False, x_T=None, verbose=True, timesteps=None,
+               quantize_denoised=False, mask=None, x0=None, shape=None, **kwargs):
+        """reference 1107-1122"""
+        if shape is None:
+            shape = (batch_size, self.channels, self.image_size, self.image_size)
+        cond = self._slice_cond(cond, batch_size)
+        return self.p_sample_loop(cond, shape, return_intermediates=return_intermediates, x_T=x_T, verbose=verbose,
+                                  timesteps=timesteps, quantize_denoised=quantize_denoised, mask=mask, x0=x0)
+
+    @torch.no_grad()
+    def sample_log(self, cond, batch_size, ddim, ddim_steps, **kwargs):
+        """reference 1125-1136"""
+        if ddim:
+            ddim_sampler = DDIMSampler(self)
+            shape = (self.channels, self.image_size, self.image_size)
+            samples, intermediates = ddim_sampler.sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
+        else:
+            samples, intermediates = self.sample(cond=cond, batch_size=batch_size, return_intermediates=True, **kwargs)
+        return samples, intermediates
 
 
     # ---- training objective (reference 854-863, 900-935); the UNet backward runs on the HIP kernels (train_ops) ----------

@@ -870,6 +870,31 @@ def ddim_cfg_step(x, eps, noise, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus
     return x_prev, pred
 
 
+def ddpm_step(x, eps, noise, sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, sigma, clip_denoised=False, return_x0=False,
+              known=None):
+    """One ancestral DDPM posterior step (LatentDiffusion.p_sample after the model call).  x [B,...] fp32; eps like x,
+    fp16|bf16|fp32 (one slab: no guidance); noise fp32 like x (None allowed when sigma == 0); the five coefficients are host
+    floats, the fp32 table entries of the step's timestep -- sigma = (t != 0) exp(0.5 logvar_clipped[t]).  known: None, or
+    (x0, q_noise, mask, sqrt_ac, sqrt_one_minus_ac) -- the known-region blend (sqrt_ac x0 + sqrt_one_minus_ac q_noise) mask +
+    (1 - mask) x_prev in the same launch; mask is shaped like x or [B,1,H,W] against x [B,C,H,W].
+    Returns (x_prev, x_recon) fp32; x_recon is None unless return_x0."""
+    x0 = qn = mask = None
+    chw = hw = 0
+    sa = s1ma = 0.0
+    if known is not None:
+        x0, qn, mask, sa, s1ma = known
+        assert x0.shape == x.shape and qn.shape == x.shape
+        if mask.shape != x.shape:
+            assert x.dim() == 4 and mask.shape == (x.shape[0], 1) + tuple(x.shape[2:]), "mask: like x, or [B,1,H,W]"
+            hw = x.shape[2] * x.shape[3]
+            chw = x.shape[1] * hw
+    if float(sigma) == 0.0:
+        noise = None
+    x_prev, x_recon = _cfg_step("ddpm_step", x, eps, 1, (noise, x0, qn, mask, chw, hw, int(bool(clip_denoised))),
+                                (True, return_x0), (sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, sigma, sa, s1ma))
+    return x_prev, x_recon
+
+
 def plms_cfg_step(x, eps, hist, weights, divisor, cfg_scale, a_t, a_prev, sqrt_one_minus_at, write_e=True):
     """One PLMS update (sigma = 0).  x [B,...] fp32; eps [2B,...] fp16|bf16|fp32 (uncond first); hist: up to 3 fp32 tensors
     like x, newest first; weights: len(hist) + 1 integer weights, divisor their common denominator.

@@ -93,8 +93,9 @@ def main():
     ap.add_argument("--metric_output", type=str, default="metric_outputs")
     ap.add_argument("--ngpu", type=int, default=1)       # parsed but unused, like the reference (62, 99)
     ap.add_argument("--fp16", action="store_true")       # idem (63)
-    ap.add_argument("--sampler", type=str, default="ddim", choices=["ddim", "plms", "dpm_solver"],
-                    help="plms needs --eta 0; dpm_solver ignores eta (reference dpm_solver/sampler.py)")
+    ap.add_argument("--sampler", type=str, default="ddim", choices=["ddim", "plms", "dpm_solver", "ddpm"],
+                    help="plms needs --eta 0; dpm_solver ignores eta (reference dpm_solver/sampler.py); ddpm: ancestral, full "
+                         "schedule, needs a guidance scale of 1")
     ap.add_argument("--steps", type=int, default=50, help="sampler steps (the reference's log_images default: 50)")
     ap.add_argument("--synthetic", type=int, default=0)
     ap.add_argument("--pretrained", type=str, default="pretrained_models/512-inpainting-ema.ckpt")
