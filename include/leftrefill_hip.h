@@ -527,6 +527,34 @@ int lr_mv_scatter_bwd(const lr_half* dx, lr_half* dseq, int b, int v, int s, int
 /* nearest-2x upsample: y[n][h][w][:] = sum of the four fine pixels of x [N][2H][2W][C]. */
 int lr_sumpool2x2(const lr_half* x, lr_half* y, int N, int H, int W, int C, lr_stream_t s);
 
+/* ---- scoring a decoded prediction: PSNR, SSIM, finite check and 8-bit image in one pass (added under ABI 30: one new symbol,
+ *      nothing renumbered or re-typed; a library without it fails to bind, which is the staleness check) -----------------------------
+ * replaces: the tail of the evaluation harness and of the task models' validation_step --
+ *             `pred = pred * mask + origin_image * (1 - mask)`, the `[:, :, :, w // 2:]` crop                 test_inpainting.py:146-150
+ *             `F.interpolate(..., mode='area')` to metric_size at an integer ratio                            test_inpainting.py:151-155
+ *             `peak_signal_noise_ratio((pred + 1) / 2, (origin + 1) / 2, data_range=1.0)` per image           test_inpainting.py:158
+ *             `TF.rgb_to_grayscale` + `structural_similarity` (scikit-image 0.18.1 defaults) per image        test_inpainting.py:160-162
+ *             `((pred.clamp(-1, 1) + 1) / 2 * 255).astype(uint8)` for the PNG                                 test_inpainting.py:168-190
+ *           and the same sequence in ref_inpainting_ldm.py:119-146, multiview_ref_inpainting_ldm.py:225-263, NVS_ldm.py:374-401
+ *           (the NVS validation scores the raw prediction: mask = NULL, NVS_ldm.py:380-381).
+ * pred [N][3][H][W] of element type `pred_kind`, origin [N][3][H][W] fp32, both in [-1, 1]; mask [N][1][H][W] fp32 or NULL (no
+ * composite).  Columns [x0, x0 + Wc) of the canvas are scored; r >= 1 is the integer area-down-sampling factor (H % r == 0,
+ * Wc % r == 0, H / r >= 7, Wc / r >= 7).  SSIM: 7 x 7 uniform window on the luma 0.2989 R + 0.587 G + 0.114 B of (x + 1) / 2, sample
+ * covariance (49 / 48), K1 = 0.01, K2 = 0.03, data_range = 2, mean over the windows that lie fully inside the scored image.
+ *   out [N][4] fp32 = (mse of (x + 1) / 2, psnr in dB (+inf when mse == 0), ssim, number of non-finite pred values in the scored columns);
+ *   rgb8 [N][H / r][Wc / r][3] or NULL: (clamp(p, -1, 1) + 1) / 2 * 255 of the (composited, down-sampled) prediction, truncated;
+ *   partials: LR_EVAL_SLOT_FLOATS floats per workgroup = N * ceil(H / r / LR_EVAL_TILE_H) * ceil(Wc / r / LR_EVAL_TILE_W) slots,
+ *   16-byte aligned like out.  Two launches (tiles, then a fixed-order fp64 sum per sample); no atomics: bitwise reproducible. */
+#define LR_EVAL_PRED_F32 0
+#define LR_EVAL_PRED_F16 1
+#define LR_EVAL_PRED_BF16 2
+#define LR_EVAL_TILE_H 32
+#define LR_EVAL_TILE_W 64
+#define LR_EVAL_SLOT_FLOATS 8
+#define LR_EVAL_MAX_R 32
+int lr_eval_metrics(const void* pred, int pred_kind, const float* origin, const float* mask, int N, int H, int W, int x0, int Wc,
+                    int r, float* partials, float* out, uint8_t* rgb8, lr_stream_t s);
+
 /* ---- bfloat16 twins: same signatures and semantics as the fp16 entry points above, every lr_half is bfloat16 bits -------- */
 int lr_groupnorm_stats_bf16(const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, float* partials,
     lr_stream_t s);

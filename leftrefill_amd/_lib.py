@@ -166,6 +166,9 @@ SIGNATURES = {
     "lr_ddpm_step": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
                      c_int64, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p],
     "lr_ddim_q_sample": [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p],
+    # added under ABI 30 (one new symbol; a library built before it fails the getattr in load())
+    "lr_eval_metrics": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                        c_void_p],
 }
 
 # bfloat16 twins (include/leftrefill_hip.h, last section): same argument lists as the fp16 entry points

@@ -8,14 +8,15 @@ configs/nvs_training_config.yaml) on the MI355X build.
     before every block that does not end in a Down / Upsample (canvas width W -> W + 1) and cut out again after it.
 `NVSLDM` (107-298): conditioning glue (get_input with the refinement branch, unconditional prompts incl. deep prompts), `log_images`,
 `log_multi_cond_images` (K conditionings through DDIMSampler.ddim_multi_sampling) and `sample_log`; the parameter groups its
-optimizer owns (`trainable_parameters`, reference 314-337).  The Lightning hooks, dataloaders, LoRA injection and validation metrics
-(299-435) stay out of scope.  The shipped configs use the plain UNetModel with `use_sep: False` and no refinement; the
+optimizer owns (`trainable_parameters`, reference 314-337); `validation_step` / `validation_epoch_end` (374-412): the right half of
+the RAW prediction (no paste: "whole image test", 380-381) scored by the HIP metrics kernel (evalglue.device_metrics).  The other
+Lightning hooks, dataloaders and LoRA injection (299-372, 414-435) stay out of scope.  The shipped configs use the plain UNetModel with `use_sep: False` and no refinement; the
 class is kept a drop-in for checkpoints / configs that turn them on.
 """
 import torch
 import torch.nn as nn
 
-from leftrefill_amd import engine
+from leftrefill_amd import engine, evalglue
 from ldm.models.diffusion.ddim import DDIMSampler
 from ldm.models.diffusion.ddpm import LatentInpaintDiffusion
 from ldm.modules.diffusionmodules.openaimodel import UNetModel
@@ -179,3 +180,20 @@ class NVSLDM(LatentInpaintDiffusion):
             params.extend(self.refinement_model.parameters())
             params.append(self.refinement_alpha)
         return params
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx):
+        """reference 374-401: columns w//2: of the prediction as sampled -- the mask is not pasted -- against the same columns of the
+        image; mean PSNR / SSIM (/ LPIPS) over the batch as Python floats."""
+        N = batch["image"].shape[0]
+        log = self.log_images(batch, N=N, unconditional_guidance_scale=self.data_cfg["cfg"])
+        metrics = evalglue.device_metrics(log, None, compose=False, right_half=True)
+
+        def lpips_pair():
+            w = log["origin_image"].shape[3]
+            return log["pred"].float()[:, :, :, w // 2:], log["origin_image"].float()[:, :, :, w // 2:]
+
+        return evalglue.validation_result(self, metrics, lpips_pair)
+
+    def validation_epoch_end(self, outputs):
+        return evalglue.validation_epoch_mean(self, outputs)

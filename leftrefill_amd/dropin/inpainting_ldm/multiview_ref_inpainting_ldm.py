@@ -7,8 +7,12 @@ MultiViewUnetModel's re-arranged self-attention) and returns the target view plu
   concat_target: canvases are [ref_i | target]; pred / origin / masked = right half of canvas 0, reference = left halves;
   otherwise    : view 0 is the target, views 1.. are the references.
 Training objective `p_losses` (38-91): the single-reference objective per canvas, of which only view 0 of every sample counts.
+`validation_step` (225-263): the target view pasted with the mask of canvas 0 of every sample, scored by the HIP metrics kernel
+(evalglue.device_metrics_multiview); `validation_epoch_end` is the single-view model's.
 """
 import torch
+
+from leftrefill_amd import evalglue
 
 from inpainting_ldm.ref_inpainting_ldm import RefInpaintLDM as _SingleViewLDM
 from ldm.modules.diffusionmodules.util import extract_into_tensor
@@ -106,3 +110,24 @@ class RefInpaintLDM(_SingleViewLDM):
             log["origin_image"] = origin[:, 0]
             log["pred"] = pred[:, 0]
         return log
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx):
+        """reference 225-263: every canvas of every sample is sampled, the target view is pasted with the mask of canvas 0 (its target
+        half under concat_target) and scored whole."""
+        img = batch['image']
+        N = img.shape[0] * img.shape[1] if img.dim() == 5 else img.shape[0]
+        log = self.log_images(batch, N=N, unconditional_guidance_scale=self.data_cfg['cfg'])
+        v = self.view_num - 1 if self.concat_target else self.view_num
+        flat = batch['mask']                     # [(b v), H, W, 1]: log_images flattened it in place, like the reference
+        metrics, _ = evalglue.device_metrics_multiview(log, flat, flat.shape[0] // v)
+
+        def lpips_pair():
+            mask = flat.float().permute(0, 3, 1, 2)
+            mask = mask.reshape(mask.shape[0] // v, v, *mask.shape[1:])[:, 0]
+            if self.concat_target:
+                mask = mask[:, :, :, mask.shape[2]:]
+            pred, origin = log['pred'].float(), log['origin_image'].float()
+            return pred * mask + origin * (1 - mask), origin
+
+        return evalglue.validation_result(self, metrics, lpips_pair)

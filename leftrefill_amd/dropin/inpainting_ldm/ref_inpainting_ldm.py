@@ -2,10 +2,13 @@
 
 Reproduces `log_images` / `sample_log` / `get_unconditional_conditioning` (reference
 inpainting_ldm/ref_inpainting_ldm.py:30-81) and the attributes callers read (`cond_cfg`, `data_cfg`, `world_size`,
-`loss_fn_alex`, `save_prompt_only`, test_inpainting.py:95-110).  The Lightning training / validation hooks
-(83-173) are out of scope.
+`loss_fn_alex`, `save_prompt_only`, test_inpainting.py:95-110), and the validation hooks `validation_step` /
+`validation_epoch_end` (119-157): PSNR / SSIM of the pasted right half come from one HIP kernel (evalglue.device_metrics), LPIPS from
+`loss_fn_alex` when one is set.  Optimizer, dataloaders and checkpoint hooks (83-117, 159-173) are out of scope.
 """
 import torch
+
+from leftrefill_amd import evalglue
 
 from ldm.models.diffusion.ddim import DDIMSampler
 from ldm.models.diffusion.ddpm import LatentInpaintDiffusion
@@ -98,3 +101,22 @@ class RefInpaintLDM(LatentInpaintDiffusion):
         sampler = make_sampler(sampler, self)
         shape = (self.channels, h, w)   # latent size comes from c_concat (reference 77-79)
         return sampler.sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx):
+        """reference 119-146: sample the batch at guidance scale data_cfg['cfg'], paste the known pixels back, keep columns w//2:,
+        mean PSNR / SSIM (/ LPIPS) over the batch as Python floats."""
+        N = batch['image'].shape[0]
+        log = self.log_images(batch, N=N, unconditional_guidance_scale=self.data_cfg['cfg'])
+        metrics = evalglue.device_metrics(log, batch['mask'], right_half=True)
+
+        def lpips_pair():
+            mask = batch['mask'].permute(0, 3, 1, 2).float()
+            pred, origin = log['pred'].float(), log['origin_image'].float()
+            w = origin.shape[3]
+            return (pred * mask + origin * (1 - mask))[:, :, :, w // 2:], origin[:, :, :, w // 2:]
+
+        return evalglue.validation_result(self, metrics, lpips_pair)
+
+    def validation_epoch_end(self, outputs):
+        return evalglue.validation_epoch_mean(self, outputs)

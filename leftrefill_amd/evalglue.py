@@ -4,7 +4,13 @@ pixels, keep the right (target) half of a stitched canvas, optional area down-sa
 Pure torch on whatever device the tensors live on.  SSIM restates `skimage.metrics.structural_similarity` of the pinned
 scikit_image==0.18.1 with the defaults the reference call uses (test_inpainting.py:160-162); `LPIPSAlex` restates the published
 LPIPS(alex) computation (test_inpainting.py:159) and takes the pretrained weights from the user (none ship without network;
-parity-unpinned: the `lpips` package is absent here)."""
+parity-unpinned: the `lpips` package is absent here).
+
+`device_metrics*` score a prediction with one HIP kernel (ops.eval_metrics: composite, crop, integer area down-sampling, PSNR, SSIM,
+finite count and the PNG's bytes in one pass, results left on the device); `metrics_reference` is the float64 CPU statement of what
+that kernel computes -- the yardstick of its tests, not a fallback: nothing on the product path calls it.  The task models'
+`validation_step` / `validation_epoch_end` (reference ref_inpainting_ldm.py:119-157, multiview_ref_inpainting_ldm.py:225-274,
+NVS_ldm.py:374-412) are built from `device_metrics*` and the two `validation_*` helpers at the end of this module."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -91,6 +97,110 @@ def ssim_gray(pred_gray, origin_gray):
     s = ((2 * ua * ub + c1) * (2 * vab + c2)) / ((ua * ua + ub * ub + c1) * (va + vb + c2))
     pad = (win - 1) // 2
     return float(s[pad:-pad, pad:-pad].mean())
+
+
+def metrics_reference(pred, origin, mask=None, x0=0, Wc=None, r=1):
+    """What ops.eval_metrics computes, in float64 on the CPU, composed from the pinned pieces above: the reference's composite
+    `pred * mask + origin * (1 - mask)` (mask None: none), columns [x0, x0 + Wc), the r x r area mean (F.interpolate(mode='area') at an
+    integer ratio), psnr01's formula, rgb_to_gray01's weights and ssim_gray.  pred, origin [N,3,H,W] in [-1, 1], mask [N,1,H,W].
+    Returns (mse, psnr, ssim): float64 tensors [N]."""
+    p, o = pred.detach().cpu().double(), origin.detach().cpu().double()
+    if mask is not None:
+        m = mask.detach().cpu().double()
+        p = p * m + o * (1 - m)
+    Wc = p.shape[3] - x0 if Wc is None else Wc
+    p, o = p[:, :, :, x0:x0 + Wc], o[:, :, :, x0:x0 + Wc]
+    if r > 1:
+        N, C, H, W = p.shape
+        if H % r or W % r:
+            raise ValueError(f"r={r} must divide the scored size {H} x {W}")
+        p = p.reshape(N, C, H // r, r, W // r, r).mean((3, 5))
+        o = o.reshape(N, C, H // r, r, W // r, r).mean((3, 5))
+    p01, o01 = (p + 1) / 2, (o + 1) / 2
+    mse = ((p01 - o01) ** 2).flatten(1).mean(1)
+    with np.errstate(divide="ignore"):
+        psnr = torch.from_numpy(10.0 * np.log10(1.0 / mse.numpy()))
+    gray = lambda x: 0.2989 * x[0] + 0.587 * x[1] + 0.114 * x[2]
+    if min(p.shape[2], p.shape[3]) < 7:      # no 7 x 7 window fits (skimage refuses such an image; the kernel returns an argument error)
+        ssim = torch.full_like(mse, float("nan"))
+    else:
+        ssim = torch.tensor([ssim_gray(gray(p01[j]), gray(o01[j])) for j in range(p.shape[0])], dtype=torch.float64)
+    return mse, psnr, ssim
+
+
+def _score(pred, origin, mask_nchw, x0, test_size, metric_size, want_rgb8):
+    """The one call of the kernel behind device_metrics*: works out the down-sampling factor, returns the dict of device tensors."""
+    from . import ops
+    Wc = pred.shape[3] - x0
+    r = 1
+    if metric_size is not None and test_size is not None and metric_size < test_size:
+        if test_size % metric_size or pred.shape[2] != test_size or Wc != test_size:
+            raise ValueError(f"device metrics need an integer area ratio on a {test_size} x {test_size} image: scored "
+                             f"{pred.shape[2]} x {Wc}, metric_size {metric_size}; the host route (compose_prediction + ssim_gray) "
+                             "handles the general case")
+        r = test_size // metric_size
+    out, rgb8 = ops.eval_metrics(pred, origin, mask_nchw, x0=x0, Wc=Wc, r=r, want_rgb8=want_rgb8)
+    return {"mse": out[:, 0], "psnr": out[:, 1], "ssim": out[:, 2], "nonfinite": out[:, 3], "rgb8": rgb8}
+
+
+def device_metrics(out, mask_nhwc, *, compose=True, right_half=None, test_size=None, metric_size=None, want_rgb8=False):
+    """compose_prediction + psnr01 + rgb_to_gray01 + ssim_gray + the finite check + the PNG's uint8 conversion as ONE kernel pass.
+    out: dict from log_images; mask_nhwc: batch['mask'] [N, H, W, 1] (ignored when compose is False: the NVS validation scores the raw
+    prediction).  right_half: None -> columns w//2: when h != w, as compose_prediction; True -> always (the task models'
+    validation_step); False -> the whole canvas.  metric_size < test_size -> area down-sampling by r = test_size // metric_size; a
+    non-integer ratio raises ValueError (use compose_prediction + ssim_gray, the host route).
+    Returns {"psnr", "ssim", "mse", "nonfinite": [N] fp32, "rgb8": [N, H', W', 3] uint8 or None} as DEVICE tensors ("nonfinite" counts
+    the scored columns); the caller reads them back once per batch."""
+    pred, origin = out["pred"], out["origin_image"]
+    h, w = pred.shape[2], pred.shape[3]
+    x0 = w // 2 if (h != w if right_half is None else right_half) else 0
+    mask = mask_nhwc.permute(0, 3, 1, 2) if compose else None
+    return _score(pred, origin, mask, x0, test_size, metric_size, want_rgb8)
+
+
+def device_metrics_multiview(out, mask_flat_nhwc, batch_size, global_view_num=0, test_size=None, metric_size=None, want_rgb8=False):
+    """compose_prediction_multiview's mask selection (the mask of canvas 0 of every sample, its target half on a [reference | target]
+    canvas), then the kernel of device_metrics.  Returns (metrics dict, global_view_num)."""
+    mask = mask_flat_nhwc.permute(0, 3, 1, 2)
+    view_num = int(mask.shape[0] / batch_size)
+    if global_view_num == 0:
+        global_view_num = view_num
+    real_bs = int(mask.shape[0] / global_view_num)
+    mask = mask.reshape(real_bs, global_view_num, *mask.shape[1:])[:, 0]
+    if mask.shape[3] != mask.shape[2]:
+        mask = mask[:, :, :, mask.shape[2]:]
+    h, w = out["pred"].shape[2], out["pred"].shape[3]
+    return _score(out["pred"], out["origin_image"], mask, w // 2 if h != w else 0, test_size, metric_size, want_rgb8), global_view_num
+
+
+def validation_result(module, metrics, lpips_pair):
+    """The tail of the reference's validation_step: batch means as Python floats, logged as 'val/<key>' when the module has a `log`
+    (a LightningModule; the drop-in is a plain nn.Module).  metrics: dict from device_metrics*, read back here in one copy.
+    'lpips' only with `module.loss_fn_alex` set (any callable on [-1, 1] images): lpips_pair() then returns the composited, cropped
+    (pred, origin) pair it is evaluated on, one sample at a time like the reference."""
+    psnr, ssim = torch.stack([metrics["psnr"].double().mean(), metrics["ssim"].double().mean()]).tolist()
+    res = {"psnr": psnr, "ssim": ssim}
+    fn = getattr(module, "loss_fn_alex", None)
+    if fn is not None:
+        pred, origin = lpips_pair()
+        res["lpips"] = float(np.mean([float(fn(pred[i:i + 1], origin[i:i + 1])) for i in range(pred.shape[0])]))
+    if hasattr(module, "log"):
+        for k, v in res.items():
+            module.log("val/" + k, v, sync_dist=True)
+    return res
+
+
+def validation_epoch_mean(module, outputs):
+    """validation_epoch_end of the three task models: per-key mean over the steps' dicts, printed by rank 0; the means are returned."""
+    keys = []
+    for o in outputs:
+        keys.extend(k for k in o if k not in keys)
+    means = {k: float(np.mean([o[k] for o in outputs if k in o])) for k in keys}
+    if getattr(module, "local_rank", 0) == 0:
+        print("Steps:", getattr(module, "global_step", 0))
+        for k, v in means.items():
+            print(k, v)
+    return means
 
 
 class LPIPSAlex(torch.nn.Module):

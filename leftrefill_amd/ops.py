@@ -956,3 +956,35 @@ def ddim_q_sample(x0, noise, sa, s1ma):
         _lib.check(lib.lr_ddim_q_sample(_p(x0[b0:b0 + n]), _p(noise[b0:b0 + n]), _p(out[b0:b0 + n]), n, per, ctypes.addressof(a),
                                         ctypes.addressof(s), _stream()), "ddim_q_sample")
     return out
+
+
+EVAL_TILE_H, EVAL_TILE_W, EVAL_SLOT_FLOATS = 32, 64, 8      # LR_EVAL_TILE_H / _W / LR_EVAL_SLOT_FLOATS
+EVAL_PRED_KIND = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}      # LR_EVAL_PRED_*
+
+
+def eval_metrics(pred, origin, mask=None, x0=0, Wc=None, r=1, want_rgb8=False):
+    """Score a decoded prediction on the device (lr_eval_metrics: composite, crop, area down-sampling, PSNR, SSIM, finite count, uint8
+    image in one pass).  pred [N,3,H,W] fp32|fp16|bf16 and origin [N,3,H,W] (fp32 is passed) in [-1, 1]; mask [N,1,H,W] or None (no
+    composite); columns [x0, x0 + Wc) are scored (Wc None: to the right edge); r: integer area-down-sampling factor.
+    Returns (out, rgb8): out [N,4] fp32 = (mse, psnr_db, ssim, nonfinite) per sample, rgb8 [N,H/r,Wc/r,3] uint8 or None -- device
+    tensors, nothing is read back here."""
+    lib = _lib.load()
+    assert pred.is_cuda and pred.dim() == 4 and pred.shape[1] == 3 and pred.dtype in EVAL_PRED_KIND, "pred: cuda [N,3,H,W] fp32 / fp16 / bf16"
+    N, _, H, W = pred.shape
+    assert origin.shape == pred.shape and origin.device == pred.device, "origin: like pred"
+    pred, origin = pred.contiguous(), origin.float().contiguous()
+    if mask is not None:
+        assert mask.shape == (N, 1, H, W) and mask.device == pred.device, "mask: [N,1,H,W]"
+        mask = mask.float().contiguous()
+    Wc = W - x0 if Wc is None else Wc
+    r = int(r)
+    if r < 1 or H % r or Wc % r:
+        raise ValueError(f"eval_metrics: r={r} must divide the scored size {H} x {Wc}")
+    Ho, Wo = H // r, Wc // r
+    slots = N * (-(-Ho // EVAL_TILE_H)) * (-(-Wo // EVAL_TILE_W))
+    partials = torch.empty(slots * EVAL_SLOT_FLOATS, device=pred.device, dtype=torch.float32)
+    out = torch.empty(N, 4, device=pred.device, dtype=torch.float32)
+    rgb8 = torch.empty(N, Ho, Wo, 3, device=pred.device, dtype=torch.uint8) if want_rgb8 else None
+    _lib.check(lib.lr_eval_metrics(_p(pred), EVAL_PRED_KIND[pred.dtype], _p(origin), _p(mask), N, H, W, int(x0), int(Wc), r,
+                                   _p(partials), _p(out), _p(rgb8), _stream()), "eval_metrics")
+    return out, rgb8

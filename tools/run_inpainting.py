@@ -23,6 +23,11 @@ directories with source / target / mask files) and torch's DataLoader, exactly l
 [reference | target] canvas keeps its target half (`evalglue.compose_prediction_multiview`, reference 141-170).  Its dataset
 (dataloaders/inpainting_crossview_dataset.py) is outside this build, so the mode runs on `--synthetic N` batches with that
 batch contract: one prompt list per view, txt[view][batch].
+
+--device_metrics: PSNR, SSIM, the finite check and the PNG's bytes come from one HIP kernel pass per batch
+(`evalglue.device_metrics*`, read back once) in place of the eager composite / crop / interpolate / psnr01 launches, the fp32
+read-backs and the per-image float64 scipy SSIM on the host; printed lines, metric file and PNG names are the same.  It needs an
+integer --test_size / --metric_size ratio.
 """
 import argparse
 import glob
@@ -101,6 +106,7 @@ def main():
     ap.add_argument("--pretrained", type=str, default="pretrained_models/512-inpainting-ema.ckpt")
     ap.add_argument("--lpips_weights", type=str, default=None, help="comma-separated state-dict files for LPIPS(alex)")
     ap.add_argument("--multiview", action="store_true", help="multi-view task model: the call sequence of test_multiview_inpainting.py")
+    ap.add_argument("--device_metrics", action="store_true", help="score on the device: PSNR / SSIM / finite check / PNG bytes from one HIP kernel")
     a = ap.parse_args()
     if a.multiview and a.test_path:
         raise SystemExit("--multiview reads --synthetic batches only: the cross-view dataset loader is outside this build (SURVEY 2a)")
@@ -138,6 +144,33 @@ def main():
             batch = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in batch.items()}
             out = model.log_images(batch, batch["image"].shape[0], unconditional_guidance_scale=a.cfg, ddim_eta=a.eta,
                                        ddim_steps=a.steps, **({} if a.sampler == "ddim" else {"sampler": a.sampler}))
+            if a.device_metrics:
+                if a.multiview:
+                    m, global_view_num = evalglue.device_metrics_multiview(out, batch["mask"], a.batch_size, global_view_num, a.test_size,
+                                                                           a.metric_size, want_rgb8=True)
+                else:
+                    m = evalglue.device_metrics(out, batch["mask"], test_size=a.test_size, metric_size=a.metric_size, want_rgb8=True)
+                psnr_b, ssim_b, bad_b = torch.stack([m["psnr"], m["ssim"], m["nonfinite"]]).tolist()      # the batch's one read-back
+                if sum(bad_b):
+                    scored = m["rgb8"].numel() * (a.test_size // a.metric_size if a.metric_size < a.test_size else 1) ** 2
+                    print(f"WARNING: {100 * sum(bad_b) / scored:.2f} % of the decoded prediction is not finite (batch {bi})")
+                psnrs.extend(psnr_b)
+                ssims.extend(ssim_b)
+                if lpips_fn is not None:      # LPIPS stays a torch module: it gets the torch composite
+                    if a.multiview:
+                        pred, origin, _ = evalglue.compose_prediction_multiview(out, batch["mask"], a.batch_size, global_view_num,
+                                                                                a.test_size, a.metric_size)
+                    else:
+                        pred, origin = evalglue.compose_prediction(out, batch["mask"], a.test_size, a.metric_size)
+                    with torch.autocast("cuda", enabled=False):
+                        lpipss.extend(lpips_fn(pred.float(), origin.float()).flatten().tolist())
+                try:
+                    from PIL import Image
+                    for j, arr in enumerate(m["rgb8"].cpu().numpy()):
+                        Image.fromarray(arr).save(os.path.join(a.output_path, f"{bi:04d}_{j}.png"))
+                except ImportError:
+                    pass
+                continue
             if not torch.isfinite(out["pred"]).all():
                 bad = (~torch.isfinite(out["pred"])).float().mean().item()
                 print(f"WARNING: {100 * bad:.2f} % of the decoded prediction is not finite (batch {bi})")
