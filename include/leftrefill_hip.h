@@ -555,6 +555,57 @@ int lr_sumpool2x2(const lr_half* x, lr_half* y, int N, int H, int W, int C, lr_s
 int lr_eval_metrics(const void* pred, int pred_kind, const float* origin, const float* mask, int N, int H, int W, int x0, int Wc,
                     int r, float* partials, float* out, uint8_t* rgb8, lr_stream_t s);
 
+/* ---- the optimizer tail of a mixed-precision training step (added under ABI 30 like lr_eval_metrics: one new symbol, a library
+ *      without it fails to bind) ------------------------------------------------------------------------------------------------------
+ * replaces: `scaler.unscale_(opt)`, the host-side isfinite read-back, `opt.step()` of torch.optim.AdamW and `scaler.update()` --
+ *           what Lightning `precision=16` runs after every backward of train_inpainting.py, and the hand-rolled scaler of bench.py.
+ * Semantics: torch.amp.GradScaler around torch.optim.AdamW (decoupled decay, bias correction, amsgrad off).  Gradients are up-cast to
+ * fp32 and multiplied by 1 / scale; if any scaled gradient of any tensor is non-finite the whole update is skipped (parameters and
+ * moments keep their bits), the scale is multiplied by backoff_factor and the growth tracker reset; otherwise AdamW is applied and
+ * after growth_interval applied steps in a row the scale is multiplied by growth_factor.  growth_interval == 0: no scaler dynamics
+ * (the scale, normally 1, never changes -- the bf16 / fp32 mode); a non-finite gradient still skips and is counted.
+ * The index into each group's lr table advances on EVERY call (a per-step scheduler steps whether or not the optimizer did) and
+ * holds the last entry past the end; the bias-correction step advances only on applied steps.
+ *   tensors [n_tensors], groups [n_groups <= LR_OPT_MAX_GROUPS], state [LR_OPT_STATE_WORDS 32-bit words], partials [4 * blocks floats]:
+ *   DEVICE memory, 16-byte aligned.  blocks (1 .. LR_OPT_MAX_BLOCKS): workgroups of the two element-wise launches.
+ *   launches: host counter incremented once per kernel launch, or NULL.
+ * Three launches for any number of tensors; sums in a fixed order, no atomics: bitwise reproducible.  Reads nothing back: capturable. */
+#define LR_OPT_GRAD_F32 0
+#define LR_OPT_GRAD_F16 1
+#define LR_OPT_GRAD_BF16 2
+#define LR_OPT_MAX_GROUPS 8
+#define LR_OPT_MAX_BLOCKS 1024
+/* state block, 32-bit words */
+#define LR_OPT_SCALE 0           /* float: loss scale */
+#define LR_OPT_GROWTH_TRACKER 1  /* int: applied steps since the scale last changed */
+#define LR_OPT_FOUND_INF 2       /* int: 1 when the last call skipped */
+#define LR_OPT_APPLIED_STEPS 3   /* int: AdamW bias-correction step */
+#define LR_OPT_SCHED_STEPS 4     /* int: calls so far = next lr index */
+#define LR_OPT_SKIPPED 5         /* int: skipped calls so far */
+#define LR_OPT_GRAD_NORM 6       /* float: l2 norm of the last call's finite unscaled gradients */
+#define LR_OPT_INV_SCALE 7       /* float: 1 / scale the last call unscaled with */
+#define LR_OPT_LR_INDEX 8        /* int: lr index the last call used (before the clamp to the table) */
+#define LR_OPT_CONSTS 16         /* per group: float step_size, decay, sqrt(bias_correction2), lr of the last call */
+#define LR_OPT_STATE_WORDS (LR_OPT_CONSTS + 4 * LR_OPT_MAX_GROUPS)
+typedef struct lr_optim_tensor {
+  float* param;
+  const void* grad;      /* element type grad_kind, scaled by the loss scale */
+  float* exp_avg;
+  float* exp_avg_sq;
+  int64_t numel;
+  int32_t grad_kind;     /* LR_OPT_GRAD_* */
+  int32_t group;
+} lr_optim_tensor;
+typedef struct lr_optim_group {
+  double beta1, beta2, eps, weight_decay;
+  const float* lr_table; /* device, lr_len entries */
+  int32_t lr_len;
+  int32_t reserved;
+} lr_optim_group;
+int lr_amp_adamw_step(const lr_optim_tensor* tensors, int n_tensors, const lr_optim_group* groups, int n_groups, void* state,
+                      float* partials, int blocks, float growth_factor, float backoff_factor, int growth_interval, int* launches,
+                      lr_stream_t s);
+
 /* ---- bfloat16 twins: same signatures and semantics as the fp16 entry points above, every lr_half is bfloat16 bits -------- */
 int lr_groupnorm_stats_bf16(const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, float* partials,
     lr_stream_t s);

@@ -94,6 +94,18 @@ class FfnArgs(ctypes.Structure):
                 ("gn_group_out", c_void_p), ("gn_hw", ctypes.c_int32)]
 
 
+class OptimTensor(ctypes.Structure):
+    """struct lr_optim_tensor (include/leftrefill_hip.h)."""
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("numel", ctypes.c_int64),
+                ("grad_kind", ctypes.c_int32), ("group", ctypes.c_int32)]
+
+
+class OptimGroup(ctypes.Structure):
+    """struct lr_optim_group (include/leftrefill_hip.h)."""
+    _fields_ = [("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double),
+                ("lr_table", c_void_p), ("lr_len", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 # symbol -> argtypes; every function returns int
 SIGNATURES = {
     "lr_abi_version": [],
@@ -169,6 +181,9 @@ SIGNATURES = {
     # added under ABI 30 (one new symbol; a library built before it fails the getattr in load())
     "lr_eval_metrics": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                         c_void_p],
+    # added under ABI 30 as well: the sync-free AMP AdamW tail (csrc/optim.hip)
+    "lr_amp_adamw_step": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_int,
+                          ctypes.POINTER(c_int), c_void_p],
 }
 
 # bfloat16 twins (include/leftrefill_hip.h, last section): same argument lists as the fp16 entry points

@@ -197,3 +197,24 @@ class NVSLDM(LatentInpaintDiffusion):
 
     def validation_epoch_end(self, outputs):
         return evalglue.validation_epoch_mean(self, outputs)
+
+    # ---- training (reference 314-345, 418-435) -------------------------------------------------------------------------------------------
+    def configure_optimizers(self):
+        """One group: prompt tokens (+ pose MLP, + refinement network and its gate where configured), on AmpAdamW."""
+        from leftrefill_amd.optim import configure_prompt_optimizer
+        if self.optim_cfg.get("all_trainable", False):
+            raise NotImplementedError("all_trainable: this build computes no weight gradients of the UNet (its backward stops at the "
+                                      "activations and the context)")
+        if self.unet_lora_params is not None:
+            raise NotImplementedError("LoRA parameter group: this build computes no weight gradients, LoRA factors included")
+        return configure_prompt_optimizer(self, [{"params": self.trainable_parameters(), "lr": self.optim_cfg["learning_rate"]}])
+
+    def on_save_checkpoint(self, checkpoint):
+        if self.save_prompt_only:
+            from leftrefill_amd.optim import keep_keys
+
+            def keep(k):      # the prompt encoder without its CLIP tower, the refinement network, LoRA factors, the separator token
+                return ((k.startswith("cond_stage_model") and not k.startswith("cond_stage_model.model.")) or k.startswith("refinement_")
+                        or "lora_down" in k or "lora_up" in k or "sep_token" in k)
+
+            keep_keys(checkpoint, keep)

@@ -120,3 +120,13 @@ class RefInpaintLDM(LatentInpaintDiffusion):
 
     def validation_epoch_end(self, outputs):
         return evalglue.validation_epoch_mean(self, outputs)
+
+    # ---- training: the optimizer owns the learned prompt tokens only (reference 83-96), a checkpoint keeps only them (164-173) ----------
+    def configure_optimizers(self):
+        from leftrefill_amd.optim import configure_prompt_optimizer
+        return configure_prompt_optimizer(self, [{"params": list(self.cond_stage_model.special_embeddings.parameters())}])
+
+    def on_save_checkpoint(self, checkpoint):
+        if self.save_prompt_only:      # everything of the prompt encoder except its frozen CLIP tower (`cond_stage_model.model.`)
+            from leftrefill_amd.optim import keep_keys
+            keep_keys(checkpoint, lambda k: k.startswith("cond_stage_model") and not k.startswith("cond_stage_model.model."))

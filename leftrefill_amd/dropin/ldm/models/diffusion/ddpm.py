@@ -81,6 +81,11 @@ class DDPM(nn.Module):
         self.use_positional_encodings = use_positional_encodings
         self.model = DiffusionWrapper(unet_config, conditioning_key)
         self.use_ema = False  # every LeftRefill config sets use_ema: False
+        self.use_scheduler = scheduler_config is not None
+        self.ucg_training = ucg_training or {}
+        self.ucg_prng = np.random.RandomState()
+        self.trainer = None      # leftrefill_amd.trainer.Trainer sets itself here and serves global_step / local_rank / log
+        self.loss_scale = None
         self.v_posterior = v_posterior
         self.original_elbo_weight = original_elbo_weight
         self.l_simple_weight = l_simple_weight
@@ -177,6 +182,52 @@ class DDPM(nn.Module):
     def sample(self, *args, **kwargs):
         raise NotImplementedError("DDPM.sample (unconditional) is not supported by this build: the UNet always has a context; "
                                   "use LatentDiffusion.sample")
+
+    # ---- what PyTorch-Lightning gives a LightningModule, served by leftrefill_amd.trainer.Trainer ---------------------------------
+    @property
+    def global_step(self):
+        return getattr(self.trainer, "global_step", 0)
+
+    @property
+    def current_epoch(self):
+        return getattr(self.trainer, "current_epoch", 0)
+
+    @property
+    def local_rank(self):
+        return getattr(self.trainer, "local_rank", 0)
+
+    def optimizers(self):
+        return self.trainer.optimizer
+
+    def _log(self, name, value, **kw):      # `self.log` exists only while a trainer serves it (it installs log / log_dict on the module)
+        log = getattr(self, "log", None)
+        if log is not None:
+            log(name, value, **kw)
+
+    # ---- training hooks (reference 438-482) ------------------------------------------------------------------------------------------
+    def shared_step(self, batch):
+        return self(self.get_input(batch, self.first_stage_key))
+
+    def training_step(self, batch, batch_idx):
+        for k, ucg in self.ucg_training.items():      # unconditional-guidance training: blank entry i of key k with probability p
+            p, val = ucg["p"], ("" if ucg["val"] is None else ucg["val"])
+            for i in range(len(batch[k])):
+                if self.ucg_prng.choice(2, p=[1 - p, p]):
+                    batch[k][i] = val
+        loss, loss_dict = self.shared_step(batch)
+        for k, v in loss_dict.items():
+            self._log(k, v, prog_bar=True, logger=True, on_step=True, on_epoch=True)
+        self._log("global_step", self.global_step, prog_bar=True, logger=True, on_step=True, on_epoch=False)
+        if self.use_scheduler:
+            self._log("lr_abs", self.optimizers().param_groups[0]["lr"], prog_bar=True, logger=True, on_step=True, on_epoch=False)
+        self.loss_dict = loss_dict
+        return loss
+
+    def on_train_batch_end(self, *args, **kwargs):
+        # None unless precision 16; the scale stays a device scalar: reading it here would put a host sync back into every step
+        get_scale = getattr(self.trainer, "loss_scale_after_step", None)
+        if get_scale is not None:
+            self.loss_scale = get_scale()
 
     def get_input(self, batch, k):
         x = batch[k]
@@ -503,7 +554,11 @@ class LatentDiffusion(DDPM):
         return samples, intermediates
 
 
-    # ---- training objective (reference 854-863, 900-935); the UNet backward runs on the HIP kernels (train_ops) ----------
+    # ---- training objective (reference 849-863, 900-935); the UNet backward runs on the HIP kernels (train_ops) ----------
+    def shared_step(self, batch, **kwargs):
+        x, c = self.get_input(batch, self.first_stage_key)
+        return self(x, c)
+
     def forward(self, x, c, *args, **kwargs):
         t = torch.randint(0, self.num_timesteps, (x.shape[0],), device=self.device).long()
         assert self.model.conditioning_key is None or c is not None

@@ -988,3 +988,29 @@ def eval_metrics(pred, origin, mask=None, x0=0, Wc=None, r=1, want_rgb8=False):
     _lib.check(lib.lr_eval_metrics(_p(pred), EVAL_PRED_KIND[pred.dtype], _p(origin), _p(mask), N, H, W, int(x0), int(Wc), r,
                                    _p(partials), _p(out), _p(rgb8), _stream()), "eval_metrics")
     return out, rgb8
+
+
+OPT_GRAD_KIND = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}      # LR_OPT_GRAD_*
+OPT_MAX_GROUPS, OPT_MAX_BLOCKS, OPT_STATE_WORDS, OPT_CONSTS = 8, 1024, 48, 16      # LR_OPT_* of include/leftrefill_hip.h
+# state-block word -> name (LR_OPT_SCALE ... LR_OPT_LR_INDEX); scale / grad_norm / inv_scale are float bits, the rest int32
+OPT_STATE_FIELDS = ("scale", "growth_tracker", "found_inf", "applied_steps", "sched_steps", "skipped", "grad_norm", "inv_scale",
+                    "lr_index")
+# kernel launches of amp_adamw_step so far, as the library itself counted them (no profiler involved)
+OPT_LAUNCHES = ctypes.c_int(0)
+
+
+def amp_adamw_step(tensors, n_tensors, groups, n_groups, state, partials, blocks, growth_factor=2.0, backoff_factor=0.5,
+                   growth_interval=2000):
+    """lr_amp_adamw_step: unscale + non-finite scan, GradScaler update and AdamW over the device table `tensors` (uint8 image of
+    n_tensors lr_optim_tensor), `groups` (n_groups lr_optim_group), the int32 `state` block and `partials` [4 * blocks] fp32.  Nothing
+    is read back; three launches whatever n_tensors."""
+    lib = _lib.load()
+    for t, name in ((tensors, "tensors"), (groups, "groups"), (state, "state"), (partials, "partials")):
+        assert t.is_cuda and t.is_contiguous(), f"{name}: contiguous device tensor"
+    assert tensors.numel() * tensors.element_size() >= n_tensors * ctypes.sizeof(_lib.OptimTensor), "tensor table too small"
+    assert groups.numel() * groups.element_size() >= n_groups * ctypes.sizeof(_lib.OptimGroup), "group table too small"
+    assert state.dtype == torch.int32 and state.numel() >= OPT_STATE_WORDS, "state: int32 [LR_OPT_STATE_WORDS]"
+    assert partials.dtype == torch.float32 and partials.numel() >= 4 * blocks, "partials: fp32 [4 * blocks]"
+    _lib.check(lib.lr_amp_adamw_step(_p(tensors), int(n_tensors), _p(groups), int(n_groups), _p(state), _p(partials), int(blocks),
+                                     float(growth_factor), float(backoff_factor), int(growth_interval), ctypes.byref(OPT_LAUNCHES),
+                                     _stream()), "amp_adamw_step")
