@@ -606,6 +606,47 @@ int lr_amp_adamw_step(const lr_optim_tensor* tensors, int n_tensors, const lr_op
                       float* partials, int blocks, float growth_factor, float backoff_factor, int growth_interval, int* launches,
                       lr_stream_t s);
 
+/* ---- LPIPS(alex) of a decoded prediction: AlexNet features on the matrix cores and the learned distance, results left on the device
+ *      (added under ABI 30 like lr_eval_metrics: new symbols only, nothing renumbered or re-typed; a library without them fails to
+ *      bind, which is the staleness check) ------------------------------------------------------------------------------------------------
+ * replaces: `model.loss_fn_alex(pred, origin)` of the evaluation harness and of the task models' validation_step, one sample at a
+ *           time with a read-back each --                                                                       test_inpainting.py:159
+ *             ref_inpainting_ldm.py:119-146, multiview_ref_inpainting_ldm.py:225-263, NVS_ldm.py:374-401 (`val/lpips`)
+ *           together with the composite / crop / area image they are handed (test_inpainting.py:146-155), which is formed inside the
+ *           first convolution's gather exactly as lr_eval_metrics forms it and never written to memory; in this tree
+ *           leftrefill_amd/evalglue.py: LPIPSAlex.forward, validation_result, and tools/run_inpainting.py (`lpips_fn(...)`).
+ * pred, origin, mask, N, H, W, x0, Wc, r: as lr_eval_metrics (pred_kind: LR_EVAL_PRED_*; mask NULL: no composite; r <= LR_EVAL_MAX_R).
+ * The scored image is Ho x Wo = H / r x Wc / r.  Stage sizes (height; widths alike), all floor divisions:
+ *     h1 = (Ho - 7) / 4 + 1           conv 11 x 11 stride 4 pad 2,  3 ->  64
+ *     h2 = (h1 - 3) / 2 + 1           MaxPool(3, 2), conv 5 x 5 pad 2,  64 -> 192
+ *     h3 = h4 = h5 = (h2 - 3) / 2 + 1 MaxPool(3, 2), conv 3 x 3 pad 1, 192 -> 384 -> 256 -> 256
+ * each followed by ReLU; per stage and pixel sum_c lin_c (fa_c / (|fa| + 1e-10) - fb_c / (|fb| + 1e-10))^2, spatial mean, sum of the
+ * five stages -> out [N] fp32.  Activations are fp16 NHWC, accumulation fp32, the head fp32 with fp64 sums.
+ * Packing: wt[k] = [Cout_k][Kpad_k] fp16, K index = (ky * ks + kx) * Cin + c (tap-major, channel-minor), Kpad_k = K rounded up to
+ * 64 with ZERO weights (363 -> 384 for conv 1; 1600, 1728, 3456, 2304); bias[k] [Cout_k], lin[k] [Cout_k] fp32.  wt / bias 16-byte
+ * aligned, workspace 256-byte aligned (LR_E_ALIGN).
+ * Workspace (lr_lpips_workspace_bytes; every term rounded up to 256): the five stage outputs 2N * h_k * w_k * Cout_k * 2 bytes, the
+ * two pooled maps 2N * h2 * w2 * 64 * 2 and 2N * h3 * w3 * 192 * 2, and 8 bytes per head workgroup: N * sum_k ceil(h_k w_k /
+ * LR_LPIPS_HEAD_PIXELS).
+ * LR_LPIPS_LAUNCHES = 13 launches (5 conv, 2 pool, 5 head, 1 finish) whatever N and the image size; no atomics, sums in a fixed
+ * order: bitwise reproducible, and a sample's score does not depend on the rest of the batch.  No synchronisation, allocation or
+ * read-back: capturable on one stream.
+ * LR_E_ARG, before any launch: a null pointer, N outside 1 .. 32767, H % r or Wc % r non-zero, a scored side below
+ * LR_LPIPS_MIN_SIDE = 31 pixels (some stage would be empty), columns outside the canvas, workspace_bytes below
+ * lr_lpips_workspace_bytes (which itself returns LR_E_ARG for such sizes). */
+#define LR_LPIPS_LAUNCHES 13
+#define LR_LPIPS_MIN_SIDE 31
+#define LR_LPIPS_HEAD_PIXELS 64
+typedef struct lr_lpips_args {
+  const void* pred; int32_t pred_kind; const float* origin; const float* mask;
+  int32_t N, H, W, x0, Wc, r;
+  const lr_half* wt[5]; const float* bias[5]; const float* lin[5];   /* packed: wt[k] = [Cout][Kpad], tap-major */
+  void* workspace; int64_t workspace_bytes;
+  float* out;                                                        /* [N] fp32 */
+} lr_lpips_args;
+int64_t lr_lpips_workspace_bytes(int N, int H, int Wc, int r);
+int lr_lpips_alex(const lr_lpips_args* args, lr_stream_t s);
+
 /* ---- bfloat16 twins: same signatures and semantics as the fp16 entry points above, every lr_half is bfloat16 bits -------- */
 int lr_groupnorm_stats_bf16(const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, float* partials,
     lr_stream_t s);

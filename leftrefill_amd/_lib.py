@@ -94,6 +94,14 @@ class FfnArgs(ctypes.Structure):
                 ("gn_group_out", c_void_p), ("gn_hw", ctypes.c_int32)]
 
 
+class LpipsArgs(ctypes.Structure):
+    """struct lr_lpips_args (include/leftrefill_hip.h)."""
+    _fields_ = [("pred", c_void_p), ("pred_kind", ctypes.c_int32), ("origin", c_void_p), ("mask", c_void_p)] + \
+               [(n, ctypes.c_int32) for n in ("N", "H", "W", "x0", "Wc", "r")] + \
+               [("wt", c_void_p * 5), ("bias", c_void_p * 5), ("lin", c_void_p * 5),
+                ("workspace", c_void_p), ("workspace_bytes", ctypes.c_int64), ("out", c_void_p)]
+
+
 class OptimTensor(ctypes.Structure):
     """struct lr_optim_tensor (include/leftrefill_hip.h)."""
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("numel", ctypes.c_int64),
@@ -184,7 +192,11 @@ SIGNATURES = {
     # added under ABI 30 as well: the sync-free AMP AdamW tail (csrc/optim.hip)
     "lr_amp_adamw_step": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_int,
                           ctypes.POINTER(c_int), c_void_p],
+    # added under ABI 30 as well: LPIPS(alex) on the device (csrc/lpips.hip)
+    "lr_lpips_workspace_bytes": [c_int, c_int, c_int, c_int],
+    "lr_lpips_alex": [ctypes.POINTER(LpipsArgs), c_void_p],
 }
+INT64_RETURNS = ("lr_gemm_workspace_bytes", "lr_lpips_workspace_bytes")
 
 # bfloat16 twins (include/leftrefill_hip.h, last section): same argument lists as the fp16 entry points
 BF16_TWINS = ["lr_groupnorm_stats", "lr_groupnorm_apply", "lr_groupnorm_apply_n", "lr_layernorm", "lr_layernorm_bwd",
@@ -238,7 +250,7 @@ def load():
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export what the header declares
         fn.argtypes = argtypes
-        fn.restype = c_int64 if name == "lr_gemm_workspace_bytes" else c_int
+        fn.restype = c_int64 if name in INT64_RETURNS else c_int
     v = lib.lr_abi_version()
     if v != ABI_VERSION:
         raise RuntimeError(f"libleftrefill_hip.so ABI {v} != binding ABI {ABI_VERSION}; rebuild")

@@ -193,7 +193,7 @@ class NVSLDM(LatentInpaintDiffusion):
             w = log["origin_image"].shape[3]
             return log["pred"].float()[:, :, :, w // 2:], log["origin_image"].float()[:, :, :, w // 2:]
 
-        return evalglue.validation_result(self, metrics, lpips_pair)
+        return evalglue.validation_result(self, metrics, lpips_pair, lambda fn: fn.score(log, None, compose=False, right_half=True))
 
     def validation_epoch_end(self, outputs):
         return evalglue.validation_epoch_mean(self, outputs)

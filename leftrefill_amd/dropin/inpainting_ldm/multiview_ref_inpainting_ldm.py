@@ -130,4 +130,4 @@ class RefInpaintLDM(_SingleViewLDM):
             pred, origin = log['pred'].float(), log['origin_image'].float()
             return pred * mask + origin * (1 - mask), origin
 
-        return evalglue.validation_result(self, metrics, lpips_pair)
+        return evalglue.validation_result(self, metrics, lpips_pair, lambda fn: fn.score_multiview(log, flat, flat.shape[0] // v)[0])

@@ -116,7 +116,7 @@ class RefInpaintLDM(LatentInpaintDiffusion):
             w = origin.shape[3]
             return (pred * mask + origin * (1 - mask))[:, :, :, w // 2:], origin[:, :, :, w // 2:]
 
-        return evalglue.validation_result(self, metrics, lpips_pair)
+        return evalglue.validation_result(self, metrics, lpips_pair, lambda fn: fn.score(log, batch['mask'], right_half=True))
 
     def validation_epoch_end(self, outputs):
         return evalglue.validation_epoch_mean(self, outputs)

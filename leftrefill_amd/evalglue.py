@@ -173,17 +173,24 @@ def device_metrics_multiview(out, mask_flat_nhwc, batch_size, global_view_num=0,
     return _score(out["pred"], out["origin_image"], mask, w // 2 if h != w else 0, test_size, metric_size, want_rgb8), global_view_num
 
 
-def validation_result(module, metrics, lpips_pair):
+def validation_result(module, metrics, lpips_pair, lpips_device=None):
     """The tail of the reference's validation_step: batch means as Python floats, logged as 'val/<key>' when the module has a `log`
     (a LightningModule; the drop-in is a plain nn.Module).  metrics: dict from device_metrics*, read back here in one copy.
     'lpips' only with `module.loss_fn_alex` set (any callable on [-1, 1] images): lpips_pair() then returns the composited, cropped
-    (pred, origin) pair it is evaluated on, one sample at a time like the reference."""
-    psnr, ssim = torch.stack([metrics["psnr"].double().mean(), metrics["ssim"].double().mean()]).tolist()
-    res = {"psnr": psnr, "ssim": ssim}
+    (pred, origin) pair it is evaluated on, one sample at a time like the reference.  A `DeviceLPIPS` is instead handed to
+    lpips_device(fn) -- the model's call of `fn.score` / `fn.score_multiview` on what it gave device_metrics* -- which scores the
+    whole batch in one kernel call; its [N] device tensor joins PSNR and SSIM in the one read-back."""
     fn = getattr(module, "loss_fn_alex", None)
-    if fn is not None:
-        pred, origin = lpips_pair()
-        res["lpips"] = float(np.mean([float(fn(pred[i:i + 1], origin[i:i + 1])) for i in range(pred.shape[0])]))
+    if isinstance(fn, DeviceLPIPS) and lpips_device is not None:
+        psnr, ssim, lp = torch.stack([metrics["psnr"].double().mean(), metrics["ssim"].double().mean(),
+                                      lpips_device(fn).double().mean()]).tolist()
+        res = {"psnr": psnr, "ssim": ssim, "lpips": lp}
+    else:
+        psnr, ssim = torch.stack([metrics["psnr"].double().mean(), metrics["ssim"].double().mean()]).tolist()
+        res = {"psnr": psnr, "ssim": ssim}
+        if fn is not None:
+            pred, origin = lpips_pair()
+            res["lpips"] = float(np.mean([float(fn(pred[i:i + 1], origin[i:i + 1])) for i in range(pred.shape[0])]))
     if hasattr(module, "log"):
         for k, v in res.items():
             module.log("val/" + k, v, sync_dist=True)
@@ -279,3 +286,69 @@ class LPIPSAlex(torch.nn.Module):
             nb = fb / (fb.pow(2).sum(1, keepdim=True).sqrt() + 1e-10)
             total = total + ((na - nb) ** 2 * lin).sum(1, keepdim=True).mean((2, 3), keepdim=True)
         return total
+
+
+class DeviceLPIPS(LPIPSAlex):
+    """LPIPSAlex on the HIP kernels of csrc/lpips.hip (ops.lpips_alex): same weights, same `load_weights`; the fp16 operands are packed
+    on first use on the device the module lives on (ops.pack_lpips; `load_weights` and a move to another device drop the pack).
+    `score*` take what `device_metrics*` take and form the composited / cropped / down-sampled image inside the first convolution;
+    `forward(a, b)` is the drop-in `loss_fn_alex` on two plain images.  Nothing is read back: the results are device tensors.
+    Parity-unpinned like its base class; the yardstick of the kernels is LPIPSAlex in float64 (tests/test_gpu_lpips.py)."""
+
+    def __init__(self):
+        super().__init__()
+        self._packed = None
+
+    def load_weights(self, *state_dicts):
+        self._packed = None
+        return super().load_weights(*state_dicts)
+
+    def packed(self):
+        if not self.loaded:
+            raise RuntimeError("DeviceLPIPS has no weights: call load_weights(alexnet_state_dict, lpips_alex_state_dict) first")
+        dev = self.convs[0].weight.device
+        if self._packed is None or self._packed["wt"][0].device != dev:
+            from . import ops
+            self._packed = ops.pack_lpips(self)
+        return self._packed
+
+    def _score(self, pred, origin, mask_nchw, x0, test_size, metric_size):
+        from . import ops
+        Wc = pred.shape[3] - x0
+        r = 1
+        if metric_size is not None and test_size is not None and metric_size < test_size:
+            if test_size % metric_size or pred.shape[2] != test_size or Wc != test_size:
+                raise ValueError(f"device LPIPS needs an integer area ratio on a {test_size} x {test_size} image: scored "
+                                 f"{pred.shape[2]} x {Wc}, metric_size {metric_size}; the host route (compose_prediction + LPIPSAlex) "
+                                 "handles the general case")
+            r = test_size // metric_size
+        return ops.lpips_alex(pred, origin, mask_nchw, x0, Wc, r, self.packed())
+
+    def score(self, out, mask_nhwc, *, compose=True, right_half=None, test_size=None, metric_size=None):
+        """LPIPS of what device_metrics scores, same arguments: [N] fp32 device tensor."""
+        pred = out["pred"]
+        h, w = pred.shape[2], pred.shape[3]
+        x0 = w // 2 if (h != w if right_half is None else right_half) else 0
+        mask = mask_nhwc.permute(0, 3, 1, 2) if compose else None
+        return self._score(pred, out["origin_image"], mask, x0, test_size, metric_size)
+
+    def score_multiview(self, out, mask_flat_nhwc, batch_size, global_view_num=0, test_size=None, metric_size=None):
+        """LPIPS of what device_metrics_multiview scores, same arguments: ([N] fp32 device tensor, global_view_num)."""
+        mask = mask_flat_nhwc.permute(0, 3, 1, 2)
+        view_num = int(mask.shape[0] / batch_size)
+        if global_view_num == 0:
+            global_view_num = view_num
+        real_bs = int(mask.shape[0] / global_view_num)
+        mask = mask.reshape(real_bs, global_view_num, *mask.shape[1:])[:, 0]
+        if mask.shape[3] != mask.shape[2]:
+            mask = mask[:, :, :, mask.shape[2]:]
+        h, w = out["pred"].shape[2], out["pred"].shape[3]
+        return self._score(out["pred"], out["origin_image"], mask, w // 2 if h != w else 0, test_size, metric_size), global_view_num
+
+    @torch.no_grad()
+    def forward(self, a, b):
+        """[N,3,H,W] x 2 -> [N,1,1,1]: the kernel route with no mask, x0 = 0, r = 1."""
+        from . import ops
+        if a.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            a = a.float()
+        return ops.lpips_alex(a, b, None, 0, a.shape[3], 1, self.packed()).view(-1, 1, 1, 1)

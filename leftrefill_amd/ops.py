@@ -1014,3 +1014,75 @@ def amp_adamw_step(tensors, n_tensors, groups, n_groups, state, partials, blocks
     _lib.check(lib.lr_amp_adamw_step(_p(tensors), int(n_tensors), _p(groups), int(n_groups), _p(state), _p(partials), int(blocks),
                                      float(growth_factor), float(backoff_factor), int(growth_interval), ctypes.byref(OPT_LAUNCHES),
                                      _stream()), "amp_adamw_step")
+
+
+LPIPS_LAUNCHES, LPIPS_MIN_SIDE, LPIPS_HEAD_PIXELS = 13, 31, 64      # LR_LPIPS_* of include/leftrefill_hip.h
+LPIPS_CONVS = ((3, 64, 11, 4, 2), (64, 192, 5, 1, 2), (192, 384, 3, 1, 1), (384, 256, 3, 1, 1), (256, 256, 3, 1, 1))   # evalglue.LPIPSAlex.CONVS
+
+
+def lpips_stage_sizes(Ho, Wo):
+    """(h_k, w_k) of the five stage outputs on an Ho x Wo scored image (the formula of the lr_lpips_alex header comment)."""
+    s1 = ((Ho - 7) // 4 + 1, (Wo - 7) // 4 + 1)
+    s2 = ((s1[0] - 3) // 2 + 1, (s1[1] - 3) // 2 + 1)
+    s3 = ((s2[0] - 3) // 2 + 1, (s2[1] - 3) // 2 + 1)
+    return [s1, s2, s3, s3, s3]
+
+
+def lpips_workspace_bytes(N, H, Wc, r=1):
+    """The Python statement of lr_lpips_workspace_bytes: five fp16 stage outputs of the 2N images, the two pooled maps, 8 bytes per
+    head workgroup; every term rounded up to 256 bytes."""
+    up = lambda v: (v + 255) // 256 * 256
+    sizes = lpips_stage_sizes(H // r, Wc // r)
+    total = sum(up(2 * N * h * w * conv[1] * 2) for (h, w), conv in zip(sizes, LPIPS_CONVS))
+    total += up(2 * N * sizes[1][0] * sizes[1][1] * 64 * 2) + up(2 * N * sizes[2][0] * sizes[2][1] * 192 * 2)
+    return total + up(8 * N * sum(-(-h * w // LPIPS_HEAD_PIXELS) for h, w in sizes))
+
+
+def pack_lpips(module):
+    """evalglue.LPIPSAlex (weights loaded) -> the operands of lr_lpips_alex on the module's device: {"wt": five fp16 [Cout, Kpad] with
+    K index (ky * ks + kx) * Cin + c and Kpad = K rounded up to 64 with zeros, "bias": five fp32 [Cout], "lin": five fp32 [Cout]}."""
+    wt, bias, lin = [], [], []
+    for conv, l in zip(module.convs, module.lins):
+        w = conv.weight.detach().float()
+        co = w.shape[0]
+        w = w.permute(0, 2, 3, 1).reshape(co, -1)
+        kpad = -(-w.shape[1] // 64) * 64
+        packed = torch.zeros(co, kpad, device=w.device, dtype=torch.float16)
+        packed[:, :w.shape[1]] = w.half()
+        wt.append(packed.contiguous())
+        bias.append(conv.bias.detach().float().contiguous().clone())
+        lin.append(l.detach().float().reshape(-1).contiguous().clone())
+    return {"wt": wt, "bias": bias, "lin": lin}
+
+
+def lpips_alex(pred, origin, mask, x0, Wc, r, packed, out=None):
+    """LPIPS(alex) of the image lr_eval_metrics scores -- composite pred * mask + origin * (1 - mask) (mask None: none), columns
+    [x0, x0 + Wc), r x r area mean -- against the same crop of origin, on the device (lr_lpips_alex: 13 launches whatever N, nothing
+    read back).  pred [N,3,H,W] fp32|fp16|bf16, origin like it (fp32 is passed), mask [N,1,H,W] or None; packed: pack_lpips(module).
+    Returns out [N] fp32 (a device tensor; `out` is filled when given)."""
+    lib = _lib.load()
+    assert pred.is_cuda and pred.dim() == 4 and pred.shape[1] == 3 and pred.dtype in EVAL_PRED_KIND, "pred: cuda [N,3,H,W] fp32 / fp16 / bf16"
+    N, _, H, W = pred.shape
+    assert origin.shape == pred.shape and origin.device == pred.device, "origin: like pred"
+    pred, origin = pred.contiguous(), origin.float().contiguous()
+    if mask is not None:
+        assert mask.shape == (N, 1, H, W) and mask.device == pred.device, "mask: [N,1,H,W]"
+        mask = mask.float().contiguous()
+    Wc = W - x0 if Wc is None else Wc
+    x0, Wc, r = int(x0), int(Wc), int(r)
+    need = int(lib.lr_lpips_workspace_bytes(N, H, Wc, r))
+    if need < 0:
+        _lib.check(need, f"lpips_alex (N {N}, scored {H} x {Wc}, r {r}: r must divide both sides and leave {LPIPS_MIN_SIDE} pixels)")
+    workspace = torch.empty(need, device=pred.device, dtype=torch.uint8)
+    if out is None:
+        out = torch.empty(N, device=pred.device, dtype=torch.float32)
+    assert out.is_cuda and out.dtype == torch.float32 and out.numel() == N and out.is_contiguous(), "out: fp32 [N]"
+    a = _lib.LpipsArgs()
+    a.pred, a.pred_kind, a.origin, a.mask = _p(pred), EVAL_PRED_KIND[pred.dtype], _p(origin), _p(mask)
+    a.N, a.H, a.W, a.x0, a.Wc, a.r = N, H, W, x0, Wc, r
+    for k in range(5):
+        assert packed["wt"][k].dtype == torch.float16 and packed["wt"][k].device == pred.device, "packed: pack_lpips on pred's device"
+        a.wt[k], a.bias[k], a.lin[k] = _p(packed["wt"][k]), _p(packed["bias"][k]), _p(packed["lin"][k])
+    a.workspace, a.workspace_bytes, a.out = _p(workspace), need, _p(out)
+    _lib.check(lib.lr_lpips_alex(ctypes.byref(a), _stream()), "lpips_alex")
+    return out

@@ -28,6 +28,10 @@ batch contract: one prompt list per view, txt[view][batch].
 (`evalglue.device_metrics*`, read back once) in place of the eager composite / crop / interpolate / psnr01 launches, the fp32
 read-backs and the per-image float64 scipy SSIM on the host; printed lines, metric file and PNG names are the same.  It needs an
 integer --test_size / --metric_size ratio.
+
+--device_lpips (with --device_metrics and --lpips_weights): the LPIPS line comes from `evalglue.DeviceLPIPS.score*` -- the HIP AlexNet
+of csrc/lpips.hip on the whole batch, the composite formed inside its first convolution -- and joins the batch's one read-back; the
+torch composite and the per-sample eager module are not run.  Same printed lines and metric file.
 """
 import argparse
 import glob
@@ -107,7 +111,10 @@ def main():
     ap.add_argument("--lpips_weights", type=str, default=None, help="comma-separated state-dict files for LPIPS(alex)")
     ap.add_argument("--multiview", action="store_true", help="multi-view task model: the call sequence of test_multiview_inpainting.py")
     ap.add_argument("--device_metrics", action="store_true", help="score on the device: PSNR / SSIM / finite check / PNG bytes from one HIP kernel")
+    ap.add_argument("--device_lpips", action="store_true", help="LPIPS from the HIP kernels (needs --device_metrics and --lpips_weights)")
     a = ap.parse_args()
+    if a.device_lpips and not (a.device_metrics and a.lpips_weights):
+        raise SystemExit("--device_lpips requires --device_metrics and --lpips_weights")
     if a.multiview and a.test_path:
         raise SystemExit("--multiview reads --synthetic batches only: the cross-view dataset loader is outside this build (SURVEY 2a)")
 
@@ -137,7 +144,7 @@ def main():
     global_view_num = 0
     lpips_fn = None
     if a.lpips_weights:
-        lpips_fn = evalglue.LPIPSAlex().load_weights(*[torch.load(f, map_location="cpu") for f in a.lpips_weights.split(",")]).cuda()
+        lpips_fn = (evalglue.DeviceLPIPS if a.device_lpips else evalglue.LPIPSAlex)().load_weights(*[torch.load(f, map_location="cpu") for f in a.lpips_weights.split(",")]).cuda()
     psnrs, ssims, lpipss = [], [], []
     with torch.no_grad(), torch.autocast("cuda"):
         for bi, batch in enumerate(batches):
@@ -150,13 +157,21 @@ def main():
                                                                            a.metric_size, want_rgb8=True)
                 else:
                     m = evalglue.device_metrics(out, batch["mask"], test_size=a.test_size, metric_size=a.metric_size, want_rgb8=True)
-                psnr_b, ssim_b, bad_b = torch.stack([m["psnr"], m["ssim"], m["nonfinite"]]).tolist()      # the batch's one read-back
+                rows = [m["psnr"], m["ssim"], m["nonfinite"]]
+                if a.device_lpips:      # one more kernel call on the same tensors, one more row of the same read-back
+                    if a.multiview:
+                        rows.append(lpips_fn.score_multiview(out, batch["mask"], a.batch_size, global_view_num, a.test_size, a.metric_size)[0])
+                    else:
+                        rows.append(lpips_fn.score(out, batch["mask"], test_size=a.test_size, metric_size=a.metric_size))
+                psnr_b, ssim_b, bad_b, *lp_b = torch.stack(rows).tolist()      # the batch's one read-back
+                if lp_b:
+                    lpipss.extend(lp_b[0])
                 if sum(bad_b):
                     scored = m["rgb8"].numel() * (a.test_size // a.metric_size if a.metric_size < a.test_size else 1) ** 2
                     print(f"WARNING: {100 * sum(bad_b) / scored:.2f} % of the decoded prediction is not finite (batch {bi})")
                 psnrs.extend(psnr_b)
                 ssims.extend(ssim_b)
-                if lpips_fn is not None:      # LPIPS stays a torch module: it gets the torch composite
+                if lpips_fn is not None and not a.device_lpips:      # the eager module gets the torch composite
                     if a.multiview:
                         pred, origin, _ = evalglue.compose_prediction_multiview(out, batch["mask"], a.batch_size, global_view_num,
                                                                                 a.test_size, a.metric_size)
