@@ -647,6 +647,46 @@ typedef struct lr_lpips_args {
 int64_t lr_lpips_workspace_bytes(int N, int H, int Wc, int r);
 int lr_lpips_alex(const lr_lpips_args* args, lr_stream_t s);
 
+/* ---- assembling a batch from raw decoded images: area shrink, crop, flip, masks and the [-1, 1] mapping in one launch (added under
+ *      ABI 30 like lr_eval_metrics: one new symbol, nothing renumbered or re-typed; a library without it fails to bind) -----------------
+ * replaces: the per-sample host work of the loaders --
+ *             `cv2.resize(..., INTER_AREA)`, the random crop, the flips, `/ 127.5 - 1`       dataloaders/inpainting_dataset.py:68-86, 175-184
+ *             `cv2.resize(mask, ..., INTER_NEAREST)`, `clip(m1 + m2, 0, 255)`, `> 127`, the outpainting mask             :88-118, 170-173
+ *             the [source | target] canvas with the all-zero left mask                           dataloaders/test_dataset.py:91-105
+ *           in this tree dropin/dataloaders/test_dataset.py (resize_area, resize_nearest) and leftrefill_amd/dataprep.py (run_plan_numpy),
+ *           whose float64 numpy statement is the yardstick.
+ * arena: the batch's raw bytes on the device, images uint8 [h][w][3] and masks uint8 [h][w] packed tightly at any byte offset; the
+ * arena itself 16-byte aligned, arena_bytes a multiple of 16 (LR_E_ALIGN).  jobs: n_jobs (<= 65535) lr_prep_job on the device,
+ * jobs_host the same table in host memory -- every offset, size and window is checked there before the launch.
+ * A job is one S x S tile of the canvas of sample `sample` (tiles tiles wide; tile column `tile`):
+ *   image: the source is area-averaged to rh x rw (destination cell i averages the source interval [i r, (i + 1) r) per axis with
+ *   coverage weights normalised per axis, fp64) and the S x S window at (y0, x0) of that is kept -- only the window is computed --,
+ *   rounded half-to-even to 0 .. 255, flipped left-right with LR_PREP_FLIP_IMAGE, mapped by v / 127.5f - 1.  rh <= img_h and
+ *   rw <= img_w: enlarging is LR_E_UNSUPPORTED, as is a window whose source row exceeds LR_PREP_ROW_BYTES - 30 bytes.
+ *   mask: outpaint_col >= 0: 1 from that column on; else LR_PREP_ZERO_MASK: 0; else up to two sources (mask_off[q] < 0: absent) read
+ *   at the nearest index min((int)(dst * (src / S)), src - 1), summed, clipped to 255, 1 where > 127.  LR_PREP_FLIP_MASK flips the
+ *   mask left-right, independent of the image flip.
+ *   LR_PREP_HOST: the kernel leaves the tile alone (the caller fills it).
+ * image, masked_image [B][S][tiles * S][3], mask [B][S][tiles * S][1] fp32; masked_image = image * (mask < 0.5).
+ * One launch, workgroups own (tile, band of output rows); plain stores, no atomics, nothing read back: capturable. */
+#define LR_PREP_FLIP_IMAGE 1
+#define LR_PREP_FLIP_MASK 2
+#define LR_PREP_ZERO_MASK 4
+#define LR_PREP_HOST 8
+#define LR_PREP_MAX_SIZE 512
+#define LR_PREP_ROW_BYTES 24576
+typedef struct lr_prep_job {
+  int64_t img_off;       /* byte offsets into the arena */
+  int64_t mask_off[2];
+  int32_t img_h, img_w, rh, rw, y0, x0;
+  int32_t mask_h[2], mask_w[2];
+  int32_t outpaint_col;  /* -1: none */
+  int32_t flags;         /* LR_PREP_* */
+  int32_t sample, tile;
+} lr_prep_job;
+int lr_batch_prep(const uint8_t* arena, int64_t arena_bytes, const lr_prep_job* jobs, const lr_prep_job* jobs_host, int n_jobs, int S,
+                  int tiles, int B, float* image, float* masked_image, float* mask, lr_stream_t s);
+
 /* ---- bfloat16 twins: same signatures and semantics as the fp16 entry points above, every lr_half is bfloat16 bits -------- */
 int lr_groupnorm_stats_bf16(const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, float* partials,
     lr_stream_t s);

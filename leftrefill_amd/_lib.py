@@ -102,6 +102,14 @@ class LpipsArgs(ctypes.Structure):
                 ("workspace", c_void_p), ("workspace_bytes", ctypes.c_int64), ("out", c_void_p)]
 
 
+class PrepJob(ctypes.Structure):
+    """struct lr_prep_job (include/leftrefill_hip.h); leftrefill_amd.dataprep.JOB_DTYPE is its numpy image."""
+    _fields_ = [("img_off", c_int64), ("mask_off", c_int64 * 2)] + \
+               [(n, ctypes.c_int32) for n in ("img_h", "img_w", "rh", "rw", "y0", "x0")] + \
+               [("mask_h", ctypes.c_int32 * 2), ("mask_w", ctypes.c_int32 * 2)] + \
+               [(n, ctypes.c_int32) for n in ("outpaint_col", "flags", "sample", "tile")]
+
+
 class OptimTensor(ctypes.Structure):
     """struct lr_optim_tensor (include/leftrefill_hip.h)."""
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("numel", ctypes.c_int64),
@@ -195,6 +203,8 @@ SIGNATURES = {
     # added under ABI 30 as well: LPIPS(alex) on the device (csrc/lpips.hip)
     "lr_lpips_workspace_bytes": [c_int, c_int, c_int, c_int],
     "lr_lpips_alex": [ctypes.POINTER(LpipsArgs), c_void_p],
+    # added under ABI 30 as well: batch assembly from raw decoded images (csrc/batch_prep.hip)
+    "lr_batch_prep": [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
 }
 INT64_RETURNS = ("lr_gemm_workspace_bytes", "lr_lpips_workspace_bytes")
 

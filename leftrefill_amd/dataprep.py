@@ -1,0 +1,255 @@
+"""Batch assembly from raw decoded images: the per-sample decisions as a plan of plain scalars, its execution on the host in numpy
+(`run_plan_numpy`, the yardstick) and on the device (`collate_raw` + `DevicePrep`: one arena copy, one job-table copy, one
+`lr_batch_prep` launch per batch, csrc/batch_prep.hip).
+
+A plan is `{"img_size": S, "tiles": [tile, ...], "txt": prompt}`; the canvas is `len(tiles)` tiles of S x S side by side (the
+single-image training sample has one, the evaluation canvas [source | target] two).  A tile is
+
+    image         index of the uint8 [h, w, 3] source in the sample's `raw` list
+    rh, rw        size the source is area-resized to;  y0, x0: origin of the S x S window kept of that
+    flip          left-right flip of the window
+    masks         indices of up to two uint8 [h, w] mask sources in `raw` (nearest-resized to S, summed, clipped, 1 where > 127)
+    mask_flip     left-right flip of the mask, independent of `flip`
+    outpaint_col  >= 0: the mask is 1 from this column on (no mask source);  zero_mask: the mask is all zero
+
+The device takes shrinking and identity resizes; a tile that enlarges its source on either axis (INTER_AREA is a different filter
+there, and `resize_area` states only its own formula for it) or whose window is wider than the kernel's row buffer sends its whole
+sample through `run_plan_numpy`, and `DevicePrep` copies the finished sample in (it warns once).
+
+Two masks are summed as integers and clipped to 255 -- what `np.clip(m1 + m2, 0, 255)` says.  (On uint8 arrays numpy wraps that
+sum before the clip; masks of {0, 255} give the same result either way after the `> 127` threshold.)
+"""
+import ctypes
+import random
+import warnings
+
+import numpy as np
+import torch
+
+from . import _lib
+from .dropin.dataloaders.test_dataset import _area_weights, resize_nearest
+
+FLIP_IMAGE, FLIP_MASK, ZERO_MASK, HOST = 1, 2, 4, 8      # LR_PREP_* of include/leftrefill_hip.h
+MAX_SIZE, ROW_BYTES = 512, 24576                         # LR_PREP_MAX_SIZE, LR_PREP_ROW_BYTES
+# numpy image of struct lr_prep_job
+JOB_DTYPE = np.dtype([("img_off", "<i8"), ("mask_off", "<i8", (2,)), ("img_h", "<i4"), ("img_w", "<i4"), ("rh", "<i4"), ("rw", "<i4"),
+                      ("y0", "<i4"), ("x0", "<i4"), ("mask_h", "<i4", (2,)), ("mask_w", "<i4", (2,)), ("outpaint_col", "<i4"),
+                      ("flags", "<i4"), ("sample", "<i4"), ("tile", "<i4")])
+assert JOB_DTYPE.itemsize == ctypes.sizeof(_lib.PrepJob) == 80
+
+
+# ---- plans: decisions only, no pixel work -----------------------------------------------------------------------------------------
+def plan_tile(image, rh, rw, y0=0, x0=0, flip=False, masks=(), mask_flip=False, outpaint_col=-1, zero_mask=False):
+    return dict(image=int(image), rh=int(rh), rw=int(rw), y0=int(y0), x0=int(x0), flip=bool(flip), masks=[int(m) for m in masks],
+                mask_flip=bool(mask_flip), outpaint_col=int(outpaint_col), zero_mask=bool(zero_mask))
+
+
+def plan_resize_train(h, w, size):
+    """The training resize (reference dataloaders/inpainting_dataset.py:68-83): with probability 1/2 straight to size x size, else the
+    short side to `size`, the long side to max(size, int(long * (size / short))) and a random size x size window.  Draws:
+    random.random, then -- second branch only -- random.randint for the window's column, then for its row."""
+    if random.random() < 0.5:
+        return dict(rh=size, rw=size, y0=0, x0=0)
+    if h < w:
+        rh, rw = size, max(size, int(w * (size / h)))
+    else:
+        rh, rw = max(size, int(h * (size / w))), size
+    x0 = random.randint(0, rw - size)
+    y0 = random.randint(0, rh - size)
+    return dict(rh=rh, rw=rw, y0=y0, x0=x0)
+
+
+def plan_mask_train(n_irregular, n_segment):
+    """Which mask files (reference 88-106): `(irregular indices, segment indices)` in the order they are summed.  Draws:
+    random.random, then one random.randint (irregular below 0.4, segment below 0.8) or two (segment, then irregular)."""
+    rdv = random.random()
+    if rdv < 0.4:
+        return [("irregular", random.randint(0, n_irregular - 1))]
+    if rdv < 0.8:
+        return [("segment", random.randint(0, n_segment - 1))]
+    first = ("segment", random.randint(0, n_segment - 1))
+    return [first, ("irregular", random.randint(0, n_irregular - 1))]
+
+
+def plan_outpaint_col(size, min_rate, max_rate):
+    """First masked column of the outpainting mask (reference 113-118).  Draws: np.random.random."""
+    return int((np.random.random() * (max_rate - min_rate) + min_rate) * size)
+
+
+def plan_flips():
+    """(image flip, mask flip) (reference 175-179).  Draws: random.random twice."""
+    flip = random.random() < 0.5
+    return flip, random.random() < 0.5
+
+
+def tile_needs_host(tile, raw, size):
+    """True when lr_batch_prep does not take the tile: it enlarges its source, or its window is wider than the kernel's row buffer."""
+    h, w = raw[tile["image"]].shape[:2]
+    if size > MAX_SIZE or tile["rh"] > h or tile["rw"] > w:
+        return True
+    rx = w / tile["rw"]
+    xa, xb = int(np.floor(tile["x0"] * rx)), min(w, int(np.ceil((tile["x0"] + size) * rx)))
+    return (xb - xa) * 3 + 30 > ROW_BYTES
+
+
+# ---- the host route ---------------------------------------------------------------------------------------------------------------
+def resize_area_hw(img, rh, rw):
+    """`resize_area` of dataloaders/test_dataset.py for a rectangular target: uint8 [h, w, c] -> uint8 [rh, rw, c], rows first."""
+    h, w = img.shape[:2]
+    if (h, w) == (rh, rw):
+        return img
+    out = np.einsum("ih,hwc->iwc", _area_weights(h, rh), img.astype(np.float64))
+    out = np.einsum("jw,iwc->ijc", _area_weights(w, rw), out)
+    return np.clip(np.rint(out), 0, 255).astype(np.uint8)
+
+
+def run_tile_numpy(tile, raw, size):
+    """One tile on the host: (image float32 [S, S, 3] in [-1, 1], mask float32 [S, S, 1] in {0, 1})."""
+    img = resize_area_hw(raw[tile["image"]], tile["rh"], tile["rw"])
+    img = img[tile["y0"]:tile["y0"] + size, tile["x0"]:tile["x0"] + size, :]
+    if tile["outpaint_col"] >= 0:
+        mask = np.zeros((size, size), dtype=np.uint8)
+        mask[:, tile["outpaint_col"]:] = 255
+    elif tile["zero_mask"]:
+        mask = np.zeros((size, size), dtype=np.uint8)
+    else:
+        total = sum(resize_nearest(raw[m], size).astype(np.int32) for m in tile["masks"])
+        mask = (np.clip(total, 0, 255) > 127).astype(np.uint8) * 255
+    mask = mask.astype(np.float32) / 255.0
+    if tile["flip"]:
+        img = img[:, ::-1].copy()
+    if tile["mask_flip"]:
+        mask = mask[:, ::-1].copy()
+    return img.astype(np.float32) / 127.5 - 1.0, mask[:, :, None]
+
+
+def run_plan_numpy(plan, raw):
+    """Execute a plan on the host: the finished sample `dict(image, txt, masked_image, mask)` of the batch contract."""
+    done = [run_tile_numpy(t, raw, plan["img_size"]) for t in plan["tiles"]]
+    image = done[0][0] if len(done) == 1 else np.concatenate([d[0] for d in done], axis=1)
+    mask = done[0][1] if len(done) == 1 else np.concatenate([d[1] for d in done], axis=1)
+    return dict(image=image, txt=plan["txt"], masked_image=image * (mask < 0.5), mask=mask)
+
+
+# ---- the device route -------------------------------------------------------------------------------------------------------------
+def collate_raw(items, pin=None):
+    """DataLoader collate_fn for `raw=True` datasets: a list of (plan, raw) -> one byte arena holding every source once, tightly packed
+    (so offsets are unaligned), and the lr_prep_job table, one job per tile.  A sample with a tile the kernel does not take is marked
+    LR_PREP_HOST and carried along in `host`; `txt` is collated as the DataLoader would.
+    pin: keep arena and table in page-locked memory (default: when a GPU is present and this is not a loader worker -- in a worker
+    leave it to `DataLoader(pin_memory=True)`)."""
+    from torch.utils.data import default_collate, get_worker_info
+    if pin is None:
+        pin = get_worker_info() is None and torch.cuda.is_available()
+    if not all(isinstance(it, tuple) and len(it) == 2 and isinstance(it[0], dict) and "tiles" in it[0] for it in items):
+        raise TypeError("collate_raw takes (plan, raw) items: build the dataset with raw=True (dataloaders.inpainting_dataset."
+                        "InpaintingDataset, dataloaders.raw_pairs.TestInpaintingDataset); dataloaders.test_dataset's own class has no raw mode")
+    size, tiles = items[0][0]["img_size"], len(items[0][0]["tiles"])
+    jobs = np.zeros(len(items) * tiles, dtype=JOB_DTYPE)
+    jobs["mask_off"] = -1
+    jobs["outpaint_col"] = -1
+    placed, host, off = [], [], 0
+    for b, (plan, raw) in enumerate(items):
+        assert plan["img_size"] == size and len(plan["tiles"]) == tiles, "one canvas shape per batch"
+        on_host = any(tile_needs_host(t, raw, size) for t in plan["tiles"])
+        if on_host:
+            host.append((b, plan, raw))
+        where = {}
+
+        def place(i):
+            nonlocal off
+            if i not in where:
+                arr = np.ascontiguousarray(raw[i])
+                assert arr.dtype == np.uint8, "raw sources are uint8"
+                where[i] = off
+                placed.append((off, arr))
+                off += arr.size
+            return where[i]
+
+        for t, tile in enumerate(plan["tiles"]):
+            job = jobs[b * tiles + t]
+            job["sample"], job["tile"] = b, t
+            if on_host:
+                job["flags"] = HOST
+                continue
+            img = raw[tile["image"]]
+            assert img.ndim == 3 and img.shape[2] == 3, "image sources are [h, w, 3]"
+            job["img_off"], job["img_h"], job["img_w"] = place(tile["image"]), img.shape[0], img.shape[1]
+            for k in ("rh", "rw", "y0", "x0", "outpaint_col"):
+                job[k] = tile[k]
+            job["flags"] = FLIP_IMAGE * tile["flip"] + FLIP_MASK * tile["mask_flip"] + ZERO_MASK * tile["zero_mask"]
+            if tile["outpaint_col"] < 0 and not tile["zero_mask"]:
+                assert 1 <= len(tile["masks"]) <= 2, "one or two mask sources"
+                for q, m in enumerate(tile["masks"]):
+                    assert raw[m].ndim == 2, "mask sources are [h, w]"
+                    job["mask_off"][q], job["mask_h"][q], job["mask_w"][q] = place(m), raw[m].shape[0], raw[m].shape[1]
+    n = max(16, -(-off // 16) * 16)
+    arena = torch.empty(n, dtype=torch.uint8, pin_memory=bool(pin))
+    table = torch.empty(jobs.nbytes, dtype=torch.uint8, pin_memory=bool(pin))
+    view = arena.numpy()
+    for o, arr in placed:
+        view[o:o + arr.size] = arr.reshape(-1)
+    view[off:] = 0
+    table.numpy()[:] = jobs.view(np.uint8).reshape(-1)
+    return dict(arena=arena, jobs=table, img_size=size, tiles=tiles, batch=len(items), host=host,
+                txt=default_collate([plan["txt"] for plan, _ in items]))
+
+
+def job_table(batch):
+    """The lr_prep_job records of a collated batch as a numpy structured array (a view)."""
+    return batch["jobs"].numpy().view(JOB_DTYPE)
+
+
+class DevicePrep:
+    """collate_raw's batch -> `dict(image, masked_image, mask, txt)` on the device: one copy of the arena, one of the job table, one
+    lr_batch_prep launch.  The arena, table and output buffers are kept and grow only when a batch needs more, so a fixed-shape loop
+    allocates nothing per step -- and the returned tensors are views of those buffers: the next call overwrites them."""
+
+    def __init__(self, img_size, tiles=1, device="cuda"):
+        self.img_size, self.tiles, self.device = int(img_size), int(tiles), torch.device(device)
+        self.arena = self.jobs = self.image = self.masked_image = self.mask = None
+        self.warned = False
+
+    @staticmethod
+    def _grown(buf, n, device):
+        return buf if buf is not None and buf.numel() >= n else torch.empty(n, dtype=torch.uint8, device=device)
+
+    def __call__(self, batch):
+        S, T, B = self.img_size, self.tiles, batch["batch"]
+        assert (batch["img_size"], batch["tiles"]) == (S, T), "the batch was planned for another canvas"
+        lib = _lib.load()
+        self.arena = self._grown(self.arena, batch["arena"].numel(), self.device)
+        self.jobs = self._grown(self.jobs, batch["jobs"].numel(), self.device)
+        if self.image is None or self.image.shape[0] < B:
+            self.image = torch.empty(B, S, T * S, 3, device=self.device)
+            self.masked_image = torch.empty(B, S, T * S, 3, device=self.device)
+            self.mask = torch.empty(B, S, T * S, 1, device=self.device)
+        n_bytes, n_jobs = batch["arena"].numel(), B * T
+        self.arena[:n_bytes].copy_(batch["arena"], non_blocking=True)
+        self.jobs[:batch["jobs"].numel()].copy_(batch["jobs"], non_blocking=True)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            _lib.check(lib.lr_batch_prep(self.arena.data_ptr(), n_bytes, self.jobs.data_ptr(), batch["jobs"].data_ptr(), n_jobs, S, T, B,
+                                         self.image.data_ptr(), self.masked_image.data_ptr(), self.mask.data_ptr(), stream), "batch_prep")
+        for b, plan, raw in batch["host"]:
+            if not self.warned:
+                self.warned = True
+                warnings.warn("DevicePrep: a sample enlarges its source (or is wider than the kernel's row buffer) and is prepared "
+                              "on the host; further such samples are routed silently")
+            done = run_plan_numpy(plan, raw)
+            for k, dst in (("image", self.image), ("masked_image", self.masked_image), ("mask", self.mask)):
+                dst[b].copy_(torch.from_numpy(np.ascontiguousarray(done[k])))
+        return dict(image=self.image[:B], masked_image=self.masked_image[:B], mask=self.mask[:B], txt=batch["txt"])
+
+
+class DevicePrepLoader:
+    """A re-iterable of device batches: every batch of `loader` (collate_fn=collate_raw) through `prep`."""
+
+    def __init__(self, loader, prep):
+        self.loader, self.prep = loader, prep
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        return (self.prep(batch) for batch in self.loader)

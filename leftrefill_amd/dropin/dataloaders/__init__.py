@@ -1,8 +1,8 @@
-"""Drop-in `dataloaders` package: only `test_dataset` is replaced.
+"""Drop-in `dataloaders` package: `test_dataset` and `inpainting_dataset` are replaced (`raw_pairs` is this package's own).
 
-The reference's `dataloaders` is a namespace directory that also holds inpainting_dataset, inpainting_crossview_dataset and
+The reference's `dataloaders` is a namespace directory that also holds inpainting_crossview_dataset and
 obj_nvs_dataset (training / multi-view entry points import them).  A regular package would shadow those, so this package
-appends every other `dataloaders` directory found on sys.path to its search path: `dataloaders.test_dataset` resolves here,
+appends every other `dataloaders` directory found on sys.path to its search path: `dataloaders.test_dataset` and `dataloaders.inpainting_dataset` resolve here,
 everything else still resolves to the reference's files.
 """
 import os

@@ -37,6 +37,7 @@ class Trainer:
         self.logged = {}            # last value of every logged name (device tensors stay on the device until someone reads them)
         self.val_results = []
         self.found_inf_history = []      # one 0-dim device tensor per optimizer step (1 = skipped); never read back by the trainer
+        self.loss_history = []           # the loss of every optimizer step's last micro-batch, 0-dim device tensors (fp32 copies)
         if hip_graph and self.accumulate_grad_batches != 1:
             raise ValueError("hip_graph needs accumulate_grad_batches == 1")
 
@@ -175,6 +176,7 @@ class Trainer:
                 self.global_step += 1
                 self.found_inf_history.append(self.optimizer.found_inf_tensor().clone())
                 self.logged["loss"] = loss.detach()
+                self.loss_history.append(loss.detach().float().clone())
                 model.on_train_batch_end()
                 if self.verbose and self.local_rank == 0 and self.global_step % self.log_every_n_steps == 0:
                     print(f"step {self.global_step}: loss {float(loss):.5f} lr {self.optimizer.param_groups[0]['lr']:.3e} "
@@ -193,8 +195,10 @@ class Trainer:
     def validate(self, model, val_batches):
         was_training = model.training
         model.eval()
+        device = next(model.parameters()).device      # Lightning moves a batch to the module's device; a DataLoader hands over host tensors
         with torch.no_grad():
-            outs = [model.validation_step(b, i) for i, b in enumerate(val_batches)]
+            outs = [model.validation_step({k: (v.to(device) if torch.is_tensor(v) else v) for k, v in b.items()} if isinstance(b, dict) else b, i)
+                    for i, b in enumerate(val_batches)]
         model.validation_epoch_end(outs)
         self.val_results.append(outs)
         model.train(was_training)

@@ -29,6 +29,9 @@ batch contract: one prompt list per view, txt[view][batch].
 read-backs and the per-image float64 scipy SSIM on the host; printed lines, metric file and PNG names are the same.  It needs an
 integer --test_size / --metric_size ratio.
 
+--device_prep (with --test_path): the loader only decodes; area resize, the [source | target] canvas, the mask (thresholded at > 127: a
+{0, 255} mask file gives the same mask) and the [-1, 1] mapping of a batch are one launch of csrc/batch_prep.hip.
+
 --device_lpips (with --device_metrics and --lpips_weights): the LPIPS line comes from `evalglue.DeviceLPIPS.score*` -- the HIP AlexNet
 of csrc/lpips.hip on the whole batch, the composite formed inside its first convolution -- and joins the batch's one read-back; the
 torch composite and the per-sample eager module are not run.  Same printed lines and metric file.
@@ -78,13 +81,20 @@ def synthetic_mv_batches(n, batch_size, size, views, concat, view_token_len, sp_
         yield {"image": img, "mask": mask, "masked_image": img * (mask < 0.5), "txt": [list(t) for t in txt]}
 
 
-def dataset_batches(path, batch_size, size, model):
-    """The reference's loader + DataLoader (test_inpainting.py:118-120)."""
+def dataset_batches(path, batch_size, size, model, device_prep=False):
+    """The reference's loader + DataLoader (test_inpainting.py:118-120).  device_prep: the loader hands over raw decoded images and the
+    [source | target] canvases of a batch are assembled by one HIP kernel launch (leftrefill_amd/dataprep.py)."""
     from torch.utils.data import DataLoader
     from dataloaders.test_dataset import TestInpaintingDataset
     cond_cfg = getattr(model, "cond_cfg", None) or {}
     data_cfg = dict(getattr(model, "data_cfg", None) or {})
     data_cfg.pop("img_size", None)
+    if device_prep:      # the same loader with the `raw` keyword: items are (plan, raw)
+        from dataloaders.raw_pairs import TestInpaintingDataset as RawDataset
+        from leftrefill_amd import dataprep
+        ds = RawDataset(path, img_size=size, deep_prompt=cond_cfg.get("deep_prompt", False), raw=True, **data_cfg)
+        loader = DataLoader(ds, batch_size=batch_size, shuffle=False, collate_fn=dataprep.collate_raw)
+        return dataprep.DevicePrepLoader(loader, dataprep.DevicePrep(size, 2, "cuda"))
     ds = TestInpaintingDataset(path, img_size=size, deep_prompt=cond_cfg.get("deep_prompt", False), **data_cfg)
     return DataLoader(ds, batch_size=batch_size, shuffle=False)
 
@@ -111,6 +121,7 @@ def main():
     ap.add_argument("--lpips_weights", type=str, default=None, help="comma-separated state-dict files for LPIPS(alex)")
     ap.add_argument("--multiview", action="store_true", help="multi-view task model: the call sequence of test_multiview_inpainting.py")
     ap.add_argument("--device_metrics", action="store_true", help="score on the device: PSNR / SSIM / finite check / PNG bytes from one HIP kernel")
+    ap.add_argument("--device_prep", action="store_true", help="assemble the --test_path batches on the device from raw decoded images")
     ap.add_argument("--device_lpips", action="store_true", help="LPIPS from the HIP kernels (needs --device_metrics and --lpips_weights)")
     a = ap.parse_args()
     if a.device_lpips and not (a.device_metrics and a.lpips_weights):
@@ -139,7 +150,7 @@ def main():
         batches = synthetic_mv_batches(max(1, a.synthetic), a.batch_size, a.test_size, views, concat, vlen,
                                        sp_token=dc.get("sp_token", "<special-token>"), repeat=int(dc.get("repeat_sp_token", 50)))
     else:
-        batches = dataset_batches(a.test_path, a.batch_size, a.test_size, model) if a.test_path else \
+        batches = dataset_batches(a.test_path, a.batch_size, a.test_size, model, a.device_prep) if a.test_path else \
             synthetic_batches(max(1, a.synthetic), a.batch_size, a.test_size)
     global_view_num = 0
     lpips_fn = None

@@ -5,12 +5,17 @@
     python tools/train_inpainting.py --config_file ... --exp_name my_run --fp16 --dataset mypkg.data:TrainSet
 
 The training config names `model_config`, `resume_path` (backbone weights), `optim_cfg`, `max_steps`, `accumulate_grad_batches`
-and `batch_size`, as the reference's check_points/*/training_config.yaml does.  Validation needs the reference's validation
-datasets, which are not part of this build: the CLI runs none (`val_check_interval` is ignored) and writes `last.ckpt` at the end.  Checkpoints go to
+and `batch_size`, as the reference's check_points/*/training_config.yaml does.  Checkpoints go to
 <save_path>/<exp_name>/ckpts/last.ckpt; --restore continues from it (the default when it exists, unless --no_restore).
 
-The training datasets are not part of this build: --synthetic N trains on N generated batches with the evaluation harness' batch
-contract (tools/run_inpainting.py), --dataset module:Class on `Class(**data_cfg)` through torch's DataLoader.
+Data: --dataset inpainting builds the `dataloaders.inpainting_dataset.InpaintingDataset` drop-in (the reference's single-image training
+set) from the config's `image_path` and `train_mask_path` (the irregular and the segmentation mask list) and the model's data section;
+--dataset module:Class builds `Class(**data_cfg)`; --synthetic N trains on N generated batches with the evaluation harness' batch
+contract (tools/run_inpainting.py).  The cross-view datasets are outside this build.
+--device_prep (with --dataset inpainting): the loader's workers only decode and plan; resize, crop, flips, masks and the [-1, 1]
+mapping of a whole batch are one HIP kernel launch (leftrefill_amd/dataprep.py, csrc/batch_prep.hip).
+--val (with --dataset inpainting): the `val`-mode dataset over `val_image_path` / `val_mask_path` (`test_limit` images, batches of
+`val_batch_size`, default 4; `test_limit` from the model's data section, else the training config) is validated every `val_check_interval` steps (a fraction: of an epoch) and its metrics printed.
 """
 import argparse
 import importlib
@@ -21,6 +26,34 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def inpainting_loaders(config, model, batch_size, device_prep, val, workers, device):
+    """(training batches, validation batches or None) of the single-image dataset, as the reference's train_dataloader builds it
+    (ref_inpainting_ldm.py:109-111); with device_prep the loaders collate raw bytes and a DevicePrep per loader finishes the batches."""
+    from torch.utils.data import DataLoader
+    from dataloaders.inpainting_dataset import InpaintingDataset
+    from leftrefill_amd import dataprep
+    size = int(model.img_size)
+    data_cfg = dict(model.data_cfg)      # the reference's model configs carry `test_limit` here (ref_inpainting_ldm.py:109-117 pass it on)
+    test_limit = int(data_cfg.pop("test_limit", config.get("test_limit", 200)))
+    common = dict(img_size=size, raw=device_prep, **data_cfg)
+    kw = dict(num_workers=workers, collate_fn=dataprep.collate_raw, pin_memory=True) if device_prep else dict(num_workers=workers)
+
+    def wrap(loader):
+        return dataprep.DevicePrepLoader(loader, dataprep.DevicePrep(size, 1, device)) if device_prep else loader
+
+    train = InpaintingDataset(image_list=config["image_path"], mask_path=list(config["train_mask_path"]), mode="train", test_limit=test_limit,
+                              **common)
+    loaders = [wrap(DataLoader(train, batch_size=batch_size, shuffle=True, drop_last=True, **kw)), None]
+    if val:
+        held = InpaintingDataset(image_list=config["val_image_path"], mask_path=config["val_mask_path"], mode="val", test_limit=test_limit,
+                                 **common)
+        val_bs = int(config.get("val_batch_size", 4))
+        if len(held) < val_bs:      # drop_last (as the reference has it) would leave no batch and validation nothing to average
+            raise SystemExit(f"--val: {len(held)} validation images are fewer than val_batch_size = {val_bs}")
+        loaders[1] = wrap(DataLoader(held, batch_size=val_bs, shuffle=False, drop_last=True, **kw))
+    return loaders
 
 
 def main():
@@ -34,9 +67,23 @@ def main():
     ap.add_argument("--restore", action="store_true")
     ap.add_argument("--no_restore", action="store_true")
     ap.add_argument("--synthetic", type=int, default=0, help="train on N generated batches")
-    ap.add_argument("--dataset", type=str, default=None, help="module:Class of a map-style training dataset")
+    ap.add_argument("--dataset", type=str, default=None, help="`inpainting`, or module:Class of a map-style training dataset")
+    ap.add_argument("--device_prep", action="store_true", help="assemble batches on the device from raw decoded images (--dataset inpainting)")
+    ap.add_argument("--val", action="store_true", help="validate on the config's val_image_path / val_mask_path (--dataset inpainting)")
+    ap.add_argument("--num_workers", type=int, default=8, help="loader workers, at most 8")
+    ap.add_argument("--seed", type=int, default=None, help="seed python's, numpy's and torch's generators")
+    ap.add_argument("--log_every_n_steps", type=int, default=50)
+    ap.add_argument("--loss_file", type=str, default=None, help="write every step's loss as a JSON list when the run ends")
     ap.add_argument("--hip_graph", action="store_true", help="replay the whole step as one hipGraph (fixed shapes)")
     a = ap.parse_args()
+    if (a.device_prep or a.val) and a.dataset != "inpainting":
+        raise SystemExit("--device_prep and --val need --dataset inpainting")
+    if a.seed is not None:
+        import random
+        import numpy as np
+        random.seed(a.seed)
+        np.random.seed(a.seed)
+        torch.manual_seed(a.seed)
 
     import leftrefill_amd.dropin as dropin
     dropin.install()
@@ -61,18 +108,28 @@ def main():
     if a.restore and resume is None:
         raise FileNotFoundError(last)
     bs = int(config.get("batch_size", 1))
-    if a.dataset:
+    val_data = val_every = None
+    if a.dataset == "inpainting":
+        data, val_data = inpainting_loaders(config, model, bs, a.device_prep, a.val, min(8, max(0, a.num_workers)), f"cuda:{rank}")
+        if val_data is not None:
+            every = config.get("val_check_interval", 1.0)
+            val_every = max(1, int(every * len(data))) if isinstance(every, float) else int(every)
+    elif a.dataset:
         mod, cls = a.dataset.split(":")
         data = torch.utils.data.DataLoader(getattr(importlib.import_module(mod), cls)(**dict(model.data_cfg)), batch_size=bs, shuffle=True,
                                            num_workers=8, drop_last=True)
     elif a.synthetic:
         data = list(synthetic_batches(a.synthetic, bs, int(model.img_size), seed=rank))
     else:
-        raise SystemExit("give --synthetic N or --dataset module:Class (the reference's training datasets are not part of this build)")
+        raise SystemExit("give --synthetic N, --dataset inpainting or --dataset module:Class")
     trainer = Trainer(max_steps=int(config["max_steps"]), accumulate_grad_batches=int(config.get("accumulate_grad_batches") or 1),
-                      val_check_interval=None, precision=16 if a.fp16 else ("bf16" if a.bf16 else 32), default_root_dir=root,
+                      val_check_interval=val_every, log_every_n_steps=a.log_every_n_steps, precision=16 if a.fp16 else ("bf16" if a.bf16 else 32), default_root_dir=root,
                       resume_from_checkpoint=resume, hip_graph=a.hip_graph, local_rank=rank)
-    trainer.fit(model, data)
+    trainer.fit(model, data, val_data)
+    if a.loss_file and rank == 0:
+        import json
+        with open(a.loss_file, "w") as f:
+            json.dump(torch.stack(trainer.loss_history).tolist(), f)      # one read-back, after the run
     print("saved", last)
 
 
