@@ -387,6 +387,9 @@ static int lr_attention_bwd_t(const lr_attn_bwd_args* a, lr_stream_t s) {
   if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o | (uintptr_t)a->dout) & 15) return LR_E_ALIGN;
   if (CAUSAL && a->Nq != a->Nkv) return LR_E_ARG;
   if (CAUSAL && a->ld_qt != 0) return LR_E_UNSUPPORTED;      // the causal dK / dV kernel walks every query tile of a key block itself
+  // the query split of the dK / dV kernel is validated here, ahead of the dQ launch: a rejected call launches nothing
+  const int q_splits = a->ld_qt > 1 && a->qt ? a->ld_qt : 1;
+  if (q_splits > 64 || (q_splits > 1 && ((uintptr_t)a->qt & 15))) return LR_E_ARG;
   AttnBwdParams<T> P;
   P.q = (const T*)a->q; P.k = (const T*)a->k; P.v = (const T*)a->v; P.o = (const T*)a->o;
   P.dout = (const T*)a->dout;
@@ -414,9 +417,8 @@ static int lr_attention_bwd_t(const lr_attn_bwd_args* a, lr_stream_t s) {
   // ABI 26: `qt` / `ld_qt` of the argument struct carry the query split of this kernel (few key blocks against many queries -- the 77-key
   // cross-attention of the 64 x 128 level is 1 key block per (batch, head): 80 blocks for 256 CUs): ld_qt = number of query slices (0 / 1 =
   // none), qt = fp32 workspace of ld_qt * B * heads * ceil(Nkv / 128) * 2 * 128 * 64 floats
-  P.q_splits = a->ld_qt > 1 && a->qt ? a->ld_qt : 1;
+  P.q_splits = q_splits;
   P.kv_ws = P.q_splits > 1 ? (float*)const_cast<lr_half*>(a->qt) : nullptr;
-  if (P.q_splits > 64 || (P.kv_ws && ((uintptr_t)P.kv_ws & 15))) return LR_E_ARG;
   hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, CAUSAL>), dim3(P.ntile_blocks * P.q_splits * a->heads * a->B), dim3(AB_THREADS), dkv_smem, st, P);
   rc = lr_launch_status();
   if (rc || P.q_splits == 1) return rc;

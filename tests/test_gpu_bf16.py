@@ -5,7 +5,9 @@ sides evaluate the same function.
 Tolerance: the kernels accumulate / normalise / softmax in fp32 exactly like the fp16 instances; the only difference is
 the 8-bit significand of the stored results (unit roundoff 2^-9 = 1.95e-3, vs 2^-12 for fp16).  The bound used here is
 the north star's fp16 bound (rtol 2e-3 / atol 1e-3) scaled by that ratio of 8: rtol 1.6e-2, atol 8e-3 -- per element, on
-outputs of O(1) magnitude -- and 3x tighter in relative L2 (printed for every case)."""
+outputs of O(1) magnitude -- and 3x tighter in relative L2 (printed for every case).
+
+The backward kernels' bf16 instances at the loop regimes of the training benchmark (per-element bound): tests/test_gpu_backward_regimes.py."""
 import numpy as np
 import pytest
 import torch
