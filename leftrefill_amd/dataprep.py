@@ -16,10 +16,17 @@ The device takes shrinking and identity resizes; a tile that enlarges its source
 there, and `resize_area` states only its own formula for it) or whose window is wider than the kernel's row buffer sends its whole
 sample through `run_plan_numpy`, and `DevicePrep` copies the finished sample in (it warns once).
 
+A multi-view plan carries several canvases instead: `{"img_size": S, "views": [[tile, ...], ...], "txt": prompts, "idx": n}`, every
+view a canvas of the same number of tiles over the sample's one `raw` list.  `collate_raw` flattens a batch of them to B·V samples of
+the job table (a source is still placed once per sample) and `DevicePrep` returns [B, V, S, T·S, C] views of its buffers.
+
 Two masks are summed as integers and clipped to 255 -- what `np.clip(m1 + m2, 0, 255)` says.  (On uint8 arrays numpy wraps that
 sum before the clip; masks of {0, 255} give the same result either way after the `> 127` threshold.)
 """
 import ctypes
+import math
+import os
+import pickle
 import random
 import warnings
 
@@ -82,6 +89,68 @@ def plan_flips():
     return flip, random.random() < 0.5
 
 
+def plan_match_mask(match_path, idx, target_pos, target_crop, source_crop, constant_place=False):
+    """The matching-based mask (reference dataloaders/inpainting_crossview_dataset.py:100-198): a closed polyline with round joints
+    through matched keypoints of the masked view.  `<match_path>/<idx:08d>.pkl` holds `mkpts0` (target), `mkpts1` (source) and `scores`
+    in 832-pixel coordinates; a crop record is `dict(w_start, h_start, w, h)` of the crop branch, None for the direct resize.
+    Returns `(mask_left, plane)`, the plane uint8 [256, 256] of {0, 255} (the reference draws 1 and never thresholds: the same mask
+    after `> 127`), or None -- no file (before any draw), fewer than 10 good points, a degenerate box, fewer than 10 picked points.
+    Draws: random.randint(15, 30); random.random for the side unless constant_place (then the right side); random.random for the
+    area; under rate < 1 two np.random.randint for the window; np.random.permutation; np.random.randint for the width."""
+    from PIL import Image, ImageDraw
+    pkl_name = os.path.join(match_path, str(idx).zfill(8) + ".pkl")
+    if not os.path.exists(pkl_name):
+        return None
+    with open(pkl_name, "rb") as f:
+        res = pickle.load(f)
+    min_width, max_width, min_area_rate, max_area_rate, min_num, match_size, grid = 35, 70, 0.2, 0.5, 10, 832, 256
+    num_vertex = random.randint(15, 30)
+    mask_left = (1.0 if constant_place else random.random()) < 0.5
+    target_side = (target_pos == "left") == mask_left      # the masked half shows the target
+    crop = target_crop if target_side else source_crop
+    pts = res["mkpts0" if target_side else "mkpts1"][np.where(res["scores"] > res["scores"].max() * 0.8)]
+    if crop is None:
+        pts = pts / match_size * grid
+    else:      # follow the crop: to the resized image, minus the window's origin, then short side -> 256
+        pts = pts / match_size
+        pts[:, 0] *= crop["w"]
+        pts[:, 1] *= crop["h"]
+        pts[:, 0] -= crop["w_start"]
+        pts[:, 1] -= crop["h_start"]
+        pts /= min(crop["w"], crop["h"]) / grid
+        pts = pts[(pts[:, 0] >= 0) * (pts[:, 1] >= 0) * (pts[:, 0] < grid) * (pts[:, 1] < grid)]
+    if len(pts) < min_num:
+        return None
+    x_min, x_max, y_min, y_max = pts[:, 0].min(), pts[:, 0].max(), pts[:, 1].min(), pts[:, 1].max()
+    good_w, good_h = x_max - x_min, y_max - y_min
+    good_area = good_w * good_h
+    if good_area == 0:
+        return None
+    rate = grid * grid * (min_area_rate + (max_area_rate - min_area_rate) * random.random()) / good_area
+    rate_1d = math.sqrt(rate)
+    if rate < 1:      # a window of that share of the points' box
+        a, b = good_w * rate_1d, good_h * rate_1d
+        x_start = x_min + np.random.randint(0, good_w - a + 1)
+        y_start = y_min + np.random.randint(0, good_h - b + 1)
+        temp = pts[np.where(pts[:, 0] > x_start)]
+        temp = temp[np.where(temp[:, 0] < x_start + a)]
+        temp = temp[np.where(temp[:, 1] > y_start)]
+        temp = temp[np.where(temp[:, 1] < y_start + b)]
+        picked = np.random.permutation(temp)
+    else:
+        picked = np.random.permutation(pts)
+    if picked.shape[0] < min_num:
+        return None
+    picked = picked[:num_vertex]
+    width = np.random.randint(min_width, max_width)
+    plane = Image.new("L", (grid, grid), 0)
+    draw = ImageDraw.Draw(plane)
+    draw.line(np.append(picked, picked[:1], axis=0), fill=255, width=width)
+    for v in picked:
+        draw.ellipse((v[0] - width // 2, v[1] - width // 2, v[0] + width // 2, v[1] + width // 2), fill=255)
+    return mask_left, np.asarray(plane, np.uint8)
+
+
 def tile_needs_host(tile, raw, size):
     """True when lr_batch_prep does not take the tile: it enlarges its source, or its window is wider than the kernel's row buffer."""
     h, w = raw[tile["image"]].shape[:2]
@@ -124,34 +193,49 @@ def run_tile_numpy(tile, raw, size):
 
 
 def run_plan_numpy(plan, raw):
-    """Execute a plan on the host: the finished sample `dict(image, txt, masked_image, mask)` of the batch contract."""
+    """Execute a plan on the host: the finished sample `dict(image, txt, masked_image, mask)` of the batch contract; a multi-view plan
+    gives [V, S, T S, C] arrays and carries its `idx` along."""
+    if "views" in plan:
+        views = [run_plan_numpy(dict(img_size=plan["img_size"], tiles=tiles, txt=None), raw) for tiles in plan["views"]]
+        out = {k: np.stack([v[k] for v in views]) for k in ("image", "masked_image", "mask")}
+        return dict(image=out["image"], txt=plan["txt"], masked_image=out["masked_image"], mask=out["mask"], idx=plan["idx"])
     done = [run_tile_numpy(t, raw, plan["img_size"]) for t in plan["tiles"]]
     image = done[0][0] if len(done) == 1 else np.concatenate([d[0] for d in done], axis=1)
     mask = done[0][1] if len(done) == 1 else np.concatenate([d[1] for d in done], axis=1)
     return dict(image=image, txt=plan["txt"], masked_image=image * (mask < 0.5), mask=mask)
 
 
+def plan_canvases(plan):
+    """The canvases of a plan as lists of tiles: its views, or its one canvas."""
+    return plan["views"] if "views" in plan else [plan["tiles"]]
+
+
 # ---- the device route -------------------------------------------------------------------------------------------------------------
 def collate_raw(items, pin=None):
     """DataLoader collate_fn for `raw=True` datasets: a list of (plan, raw) -> one byte arena holding every source once, tightly packed
     (so offsets are unaligned), and the lr_prep_job table, one job per tile.  A sample with a tile the kernel does not take is marked
-    LR_PREP_HOST and carried along in `host`; `txt` is collated as the DataLoader would.
+    LR_PREP_HOST and carried along in `host`; `txt` is collated as the DataLoader would.  Multi-view plans (`views`) become B·V samples
+    of the table, sample b's view v at index b V + v, over sample b's one set of sources; the batch then carries `views` = V and `idx`.
     pin: keep arena and table in page-locked memory (default: when a GPU is present and this is not a loader worker -- in a worker
     leave it to `DataLoader(pin_memory=True)`)."""
     from torch.utils.data import default_collate, get_worker_info
     if pin is None:
         pin = get_worker_info() is None and torch.cuda.is_available()
-    if not all(isinstance(it, tuple) and len(it) == 2 and isinstance(it[0], dict) and "tiles" in it[0] for it in items):
+    if not all(isinstance(it, tuple) and len(it) == 2 and isinstance(it[0], dict) and ("tiles" in it[0] or "views" in it[0]) for it in items):
         raise TypeError("collate_raw takes (plan, raw) items: build the dataset with raw=True (dataloaders.inpainting_dataset."
-                        "InpaintingDataset, dataloaders.raw_pairs.TestInpaintingDataset); dataloaders.test_dataset's own class has no raw mode")
-    size, tiles = items[0][0]["img_size"], len(items[0][0]["tiles"])
-    jobs = np.zeros(len(items) * tiles, dtype=JOB_DTYPE)
+                        "InpaintingDataset, dataloaders.raw_pairs.TestInpaintingDataset, dataloaders.inpainting_crossview_dataset's "
+                        "two); dataloaders.test_dataset's own class has no raw mode")
+    first = plan_canvases(items[0][0])
+    size, views, tiles, multi = items[0][0]["img_size"], len(first), len(first[0]), "views" in items[0][0]
+    jobs = np.zeros(len(items) * views * tiles, dtype=JOB_DTYPE)
     jobs["mask_off"] = -1
     jobs["outpaint_col"] = -1
     placed, host, off = [], [], 0
     for b, (plan, raw) in enumerate(items):
-        assert plan["img_size"] == size and len(plan["tiles"]) == tiles, "one canvas shape per batch"
-        on_host = any(tile_needs_host(t, raw, size) for t in plan["tiles"])
+        canvases = plan_canvases(plan)
+        assert plan["img_size"] == size and ("views" in plan) == multi and len(canvases) == views and \
+            all(len(c) == tiles for c in canvases), "one canvas shape per batch"
+        on_host = any(tile_needs_host(t, raw, size) for c in canvases for t in c)
         if on_host:
             host.append((b, plan, raw))
         where = {}
@@ -166,23 +250,24 @@ def collate_raw(items, pin=None):
                 off += arr.size
             return where[i]
 
-        for t, tile in enumerate(plan["tiles"]):
-            job = jobs[b * tiles + t]
-            job["sample"], job["tile"] = b, t
-            if on_host:
-                job["flags"] = HOST
-                continue
-            img = raw[tile["image"]]
-            assert img.ndim == 3 and img.shape[2] == 3, "image sources are [h, w, 3]"
-            job["img_off"], job["img_h"], job["img_w"] = place(tile["image"]), img.shape[0], img.shape[1]
-            for k in ("rh", "rw", "y0", "x0", "outpaint_col"):
-                job[k] = tile[k]
-            job["flags"] = FLIP_IMAGE * tile["flip"] + FLIP_MASK * tile["mask_flip"] + ZERO_MASK * tile["zero_mask"]
-            if tile["outpaint_col"] < 0 and not tile["zero_mask"]:
-                assert 1 <= len(tile["masks"]) <= 2, "one or two mask sources"
-                for q, m in enumerate(tile["masks"]):
-                    assert raw[m].ndim == 2, "mask sources are [h, w]"
-                    job["mask_off"][q], job["mask_h"][q], job["mask_w"][q] = place(m), raw[m].shape[0], raw[m].shape[1]
+        for v, canvas in enumerate(canvases):
+            for t, tile in enumerate(canvas):
+                job = jobs[(b * views + v) * tiles + t]
+                job["sample"], job["tile"] = b * views + v, t
+                if on_host:
+                    job["flags"] = HOST
+                    continue
+                img = raw[tile["image"]]
+                assert img.ndim == 3 and img.shape[2] == 3, "image sources are [h, w, 3]"
+                job["img_off"], job["img_h"], job["img_w"] = place(tile["image"]), img.shape[0], img.shape[1]
+                for k in ("rh", "rw", "y0", "x0", "outpaint_col"):
+                    job[k] = tile[k]
+                job["flags"] = FLIP_IMAGE * tile["flip"] + FLIP_MASK * tile["mask_flip"] + ZERO_MASK * tile["zero_mask"]
+                if tile["outpaint_col"] < 0 and not tile["zero_mask"]:
+                    assert 1 <= len(tile["masks"]) <= 2, "one or two mask sources"
+                    for q, m in enumerate(tile["masks"]):
+                        assert raw[m].ndim == 2, "mask sources are [h, w]"
+                        job["mask_off"][q], job["mask_h"][q], job["mask_w"][q] = place(m), raw[m].shape[0], raw[m].shape[1]
     n = max(16, -(-off // 16) * 16)
     arena = torch.empty(n, dtype=torch.uint8, pin_memory=bool(pin))
     table = torch.empty(jobs.nbytes, dtype=torch.uint8, pin_memory=bool(pin))
@@ -191,8 +276,11 @@ def collate_raw(items, pin=None):
         view[o:o + arr.size] = arr.reshape(-1)
     view[off:] = 0
     table.numpy()[:] = jobs.view(np.uint8).reshape(-1)
-    return dict(arena=arena, jobs=table, img_size=size, tiles=tiles, batch=len(items), host=host,
-                txt=default_collate([plan["txt"] for plan, _ in items]))
+    out = dict(arena=arena, jobs=table, img_size=size, tiles=tiles, batch=len(items), host=host,
+               txt=default_collate([plan["txt"] for plan, _ in items]))
+    if multi:
+        out.update(views=views, idx=default_collate([plan["idx"] for plan, _ in items]))
+    return out
 
 
 def job_table(batch):
@@ -215,21 +303,22 @@ class DevicePrep:
         return buf if buf is not None and buf.numel() >= n else torch.empty(n, dtype=torch.uint8, device=device)
 
     def __call__(self, batch):
-        S, T, B = self.img_size, self.tiles, batch["batch"]
+        S, T, B, V = self.img_size, self.tiles, batch["batch"], batch.get("views")
         assert (batch["img_size"], batch["tiles"]) == (S, T), "the batch was planned for another canvas"
+        N = B * (V or 1)      # canvases: the kernel's samples
         lib = _lib.load()
         self.arena = self._grown(self.arena, batch["arena"].numel(), self.device)
         self.jobs = self._grown(self.jobs, batch["jobs"].numel(), self.device)
-        if self.image is None or self.image.shape[0] < B:
-            self.image = torch.empty(B, S, T * S, 3, device=self.device)
-            self.masked_image = torch.empty(B, S, T * S, 3, device=self.device)
-            self.mask = torch.empty(B, S, T * S, 1, device=self.device)
-        n_bytes, n_jobs = batch["arena"].numel(), B * T
+        if self.image is None or self.image.shape[0] < N:
+            self.image = torch.empty(N, S, T * S, 3, device=self.device)
+            self.masked_image = torch.empty(N, S, T * S, 3, device=self.device)
+            self.mask = torch.empty(N, S, T * S, 1, device=self.device)
+        n_bytes, n_jobs = batch["arena"].numel(), N * T
         self.arena[:n_bytes].copy_(batch["arena"], non_blocking=True)
         self.jobs[:batch["jobs"].numel()].copy_(batch["jobs"], non_blocking=True)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream().cuda_stream
-            _lib.check(lib.lr_batch_prep(self.arena.data_ptr(), n_bytes, self.jobs.data_ptr(), batch["jobs"].data_ptr(), n_jobs, S, T, B,
+            _lib.check(lib.lr_batch_prep(self.arena.data_ptr(), n_bytes, self.jobs.data_ptr(), batch["jobs"].data_ptr(), n_jobs, S, T, N,
                                          self.image.data_ptr(), self.masked_image.data_ptr(), self.mask.data_ptr(), stream), "batch_prep")
         for b, plan, raw in batch["host"]:
             if not self.warned:
@@ -238,8 +327,12 @@ class DevicePrep:
                               "on the host; further such samples are routed silently")
             done = run_plan_numpy(plan, raw)
             for k, dst in (("image", self.image), ("masked_image", self.masked_image), ("mask", self.mask)):
-                dst[b].copy_(torch.from_numpy(np.ascontiguousarray(done[k])))
-        return dict(image=self.image[:B], masked_image=self.masked_image[:B], mask=self.mask[:B], txt=batch["txt"])
+                src = torch.from_numpy(np.ascontiguousarray(done[k]))
+                (dst[b] if V is None else dst[b * V:(b + 1) * V]).copy_(src)
+        if V is None:
+            return dict(image=self.image[:B], masked_image=self.masked_image[:B], mask=self.mask[:B], txt=batch["txt"])
+        shape = lambda t: t[:N].view(B, V, *t.shape[1:])
+        return dict(image=shape(self.image), masked_image=shape(self.masked_image), mask=shape(self.mask), txt=batch["txt"], idx=batch["idx"])
 
 
 class DevicePrepLoader:
@@ -250,6 +343,10 @@ class DevicePrepLoader:
 
     def __len__(self):
         return len(self.loader)
+
+    @property
+    def sampler(self):
+        return self.loader.sampler
 
     def __iter__(self):
         return (self.prep(batch) for batch in self.loader)

@@ -4,7 +4,8 @@
     trainer.fit(model, train_batches, val_batches)
 
 The module's own hooks do the work -- training_step, configure_optimizers (AmpAdamW: unscale, skip decision, loss-scale update, lr
-schedule and AdamW in one device-side step), on_train_batch_end, validation_step / validation_epoch_end, on_save_checkpoint -- and
+schedule and AdamW in one device-side step), on_train_epoch_start (when defined: at the start of every pass over the training
+batches, `trainer.train_dataloader` set), on_train_batch_end, validation_step / validation_epoch_end, on_save_checkpoint -- and
 the trainer serves what they expect from Lightning: `module.trainer`, `global_step`, `local_rank`, `log`.  Gradients are averaged over
 ranks with dist.allreduce_mean_grads before the step, so every rank takes the same skip decision.
 
@@ -149,9 +150,12 @@ class Trainer:
 
     def fit(self, model, train_batches, val_batches=None):
         self._setup(model)
+        self.train_dataloader = train_batches      # what a module's on_train_epoch_start reaches the sampler through
         graph = static = None
         micro = 0
         while self.global_step < self.max_steps:
+            if hasattr(model, "on_train_epoch_start"):
+                model.on_train_epoch_start()
             seen = 0
             for idx, batch in enumerate(train_batches):
                 seen += 1

@@ -20,9 +20,10 @@ directories with source / target / mask files) and torch's DataLoader, exactly l
 --multiview: the call sequence of the reference's test_multiview_inpainting.py (77-233) for the multi-view task model
 (inpainting_ldm.multiview_ref_inpainting_ldm.RefInpaintLDM over MultiViewUnetModel): 5-D batches [B, v, H, W, 3], log_images samples all
 (b v) canvases jointly and returns the target view; the mask of canvas 0 of every sample pastes the known pixels back, a
-[reference | target] canvas keeps its target half (`evalglue.compose_prediction_multiview`, reference 141-170).  Its dataset
-(dataloaders/inpainting_crossview_dataset.py) is outside this build, so the mode runs on `--synthetic N` batches with that
-batch contract: one prompt list per view, txt[view][batch].
+[reference | target] canvas keeps its target half (`evalglue.compose_prediction_multiview`, reference 141-170).  --test_path DIR is read
+through `leftrefill_amd.dropin.dataloaders.inpainting_crossview_dataset.InpaintingMultiViewDataset` in `val` mode, built as the reference builds
+it (test_multiview_inpainting.py:111-114: folders named by a number with target / source / source_1.. and mask.png; `test_limit`
+482); without it the mode runs on `--synthetic N` batches with that batch contract: one prompt list per view, txt[view][batch].
 
 --device_metrics: PSNR, SSIM, the finite check and the PNG's bytes come from one HIP kernel pass per batch
 (`evalglue.device_metrics*`, read back once) in place of the eager composite / crop / interpolate / psnr01 launches, the fp32
@@ -30,7 +31,8 @@ read-backs and the per-image float64 scipy SSIM on the host; printed lines, metr
 integer --test_size / --metric_size ratio.
 
 --device_prep (with --test_path): the loader only decodes; area resize, the [source | target] canvas, the mask (thresholded at > 127: a
-{0, 255} mask file gives the same mask) and the [-1, 1] mapping of a batch are one launch of csrc/batch_prep.hip.
+{0, 255} mask file gives the same mask) and the [-1, 1] mapping of a batch are one launch of csrc/batch_prep.hip -- under --multiview
+all B x V canvases of a batch in that one launch.
 
 --device_lpips (with --device_metrics and --lpips_weights): the LPIPS line comes from `evalglue.DeviceLPIPS.score*` -- the HIP AlexNet
 of csrc/lpips.hip on the whole batch, the composite formed inside its first convolution -- and joins the batch's one read-back; the
@@ -99,6 +101,27 @@ def dataset_batches(path, batch_size, size, model, device_prep=False):
     return DataLoader(ds, batch_size=batch_size, shuffle=False)
 
 
+def multiview_batches(path, batch_size, size, model, device_prep=False):
+    """The reference's multi-view loader + DataLoader (test_multiview_inpainting.py:111-114); device_prep as in `dataset_batches`, with
+    one tile per view, or two under concat_target."""
+    from torch.utils.data import DataLoader
+    from leftrefill_amd.dropin.dataloaders.inpainting_crossview_dataset import InpaintingMultiViewDataset
+    from leftrefill_amd import dataprep
+    data_cfg = dict(getattr(model, "data_cfg", None) or {}, test_limit=482)
+    data_cfg.pop("img_size", None)
+    ds = InpaintingMultiViewDataset(path, img_size=size, pair_path=None, mask_path=path, mode="val", raw=device_prep,
+                                    deep_prompt=(getattr(model, "cond_cfg", None) or {}).get("deep_prompt", False), **data_cfg)
+    bad = [p for p in ds.pairs if not (os.path.basename(p).isdigit() and glob.glob(os.path.join(p, "target.*")))]
+    if bad or not len(ds):      # refused, not skipped: a wrong folder must not score a subset
+        raise SystemExit(f"--multiview --test_path {path}: {len(bad)} of {len(ds)} entries are no multi-view folders (named by a number, "
+                         f"holding target / source / source_1.. images and mask.png), e.g. {bad[:1]}; without a dataset, --synthetic N "
+                         "builds batches of the same contract")
+    if not device_prep:
+        return DataLoader(ds, batch_size=batch_size, shuffle=False)
+    loader = DataLoader(ds, batch_size=batch_size, shuffle=False, collate_fn=dataprep.collate_raw)
+    return dataprep.DevicePrepLoader(loader, dataprep.DevicePrep(size, 2 if ds.concat_target else 1, "cuda"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model_path", type=str, required=True)
@@ -126,8 +149,6 @@ def main():
     a = ap.parse_args()
     if a.device_lpips and not (a.device_metrics and a.lpips_weights):
         raise SystemExit("--device_lpips requires --device_metrics and --lpips_weights")
-    if a.multiview and a.test_path:
-        raise SystemExit("--multiview reads --synthetic batches only: the cross-view dataset loader is outside this build (SURVEY 2a)")
 
     import leftrefill_amd.dropin as dropin
     dropin.install()
@@ -142,7 +163,9 @@ def main():
         print(model.load_state_dict(load_state_dict(a.pretrained), strict=False))
     model = model.to("cuda").eval()
     os.makedirs(a.output_path, exist_ok=True)
-    if a.multiview:
+    if a.multiview and a.test_path:
+        batches = multiview_batches(a.test_path, a.batch_size, a.test_size, model, a.device_prep)
+    elif a.multiview:
         concat = bool(getattr(model, "concat_target", False))
         views = model.view_num - 1 if concat else model.view_num
         vlen = int((getattr(model, "cond_cfg", None) or {}).get("view_token_len", 0)) if (getattr(model, "cond_cfg", None) or {}).get("view_prompt", True) else 0

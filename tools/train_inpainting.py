@@ -8,14 +8,19 @@ The training config names `model_config`, `resume_path` (backbone weights), `opt
 and `batch_size`, as the reference's check_points/*/training_config.yaml does.  Checkpoints go to
 <save_path>/<exp_name>/ckpts/last.ckpt; --restore continues from it (the default when it exists, unless --no_restore).
 
-Data: --dataset inpainting builds the `dataloaders.inpainting_dataset.InpaintingDataset` drop-in (the reference's single-image training
-set) from the config's `image_path` and `train_mask_path` (the irregular and the segmentation mask list) and the model's data section;
---dataset module:Class builds `Class(**data_cfg)`; --synthetic N trains on N generated batches with the evaluation harness' batch
-contract (tools/run_inpainting.py).  The cross-view datasets are outside this build.
---device_prep (with --dataset inpainting): the loader's workers only decode and plan; resize, crop, flips, masks and the [-1, 1]
-mapping of a whole batch are one HIP kernel launch (leftrefill_amd/dataprep.py, csrc/batch_prep.hip).
---val (with --dataset inpainting): the `val`-mode dataset over `val_image_path` / `val_mask_path` (`test_limit` images, batches of
-`val_batch_size`, default 4; `test_limit` from the model's data section, else the training config) is validated every `val_check_interval` steps (a fraction: of an epoch) and its metrics printed.
+Data: --dataset crossview builds what the shipped prompt tokens were trained on: `leftrefill_amd.dropin.dataloaders.inpainting_crossview_dataset.
+InpaintingCrossViewDataset` over the config's `image_path` (the image dictionary), `train_pair` and `train_mask_path` and the model's
+data section ([reference | target] canvases, view masks, matching-based masks, ...), drawn by `BalancedRandomSampler`
+(`n_sample_per_scene` pairs of every scene per epoch, this rank's share; the trainer's epoch hook reseeds it) -- the model's own
+`train_dataloader` / `val_dataloader`, as in the reference.  --dataset inpainting builds the `dataloaders.inpainting_dataset.
+InpaintingDataset` drop-in (the reference's single-image training set) from the config's `image_path` and `train_mask_path` (the
+irregular and the segmentation mask list) and the model's data section; --dataset module:Class builds `Class(**data_cfg)`;
+--synthetic N trains on N generated batches with the evaluation harness' batch contract (tools/run_inpainting.py).
+--device_prep (with --dataset inpainting | crossview): the loader's workers only decode and plan; resize, crop, flips, masks and the
+[-1, 1] mapping of a whole batch are one HIP kernel launch (leftrefill_amd/dataprep.py, csrc/batch_prep.hip).
+--val (with --dataset inpainting | crossview): the `val`-mode dataset over `val_image_path` / `val_mask_path` (`test_limit` images,
+batches of `val_batch_size`, default 4; `test_limit` from the model's data section, else the training config) is validated every
+`val_check_interval` steps (a fraction: of an epoch) and its metrics printed.
 """
 import argparse
 import importlib
@@ -26,6 +31,40 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def device_route(loader, device_prep, size, tiles, device):
+    """With device_prep, the loader's raw batches finished by a DevicePrep of its own; else the loader."""
+    from leftrefill_amd import dataprep
+    return dataprep.DevicePrepLoader(loader, dataprep.DevicePrep(size, tiles, device)) if device_prep else loader
+
+
+def record_draws(sampler):
+    """Every epoch's indices as the sampler hands them out from now on, one list per epoch, appended to the returned list."""
+    epochs, draw = [], type(sampler).__iter__
+
+    class Recording(type(sampler)):
+        def __iter__(self):
+            epochs.append(list(draw(self)))
+            return iter(epochs[-1])
+
+    sampler.__class__ = Recording
+    return epochs
+
+
+def crossview_loaders(config, model, device_prep, val, workers, device):
+    """(training batches, validation batches or None) of the image-pair dataset: the model's own train_dataloader / val_dataloader
+    (reference ref_inpainting_ldm.py:99-117), whose sampler takes rank and replica count from the model; two tiles per canvas."""
+    size = int(model.img_size)
+    model.cfg = dict(config, cross_view_inpainting=True)
+    loaders = [device_route(model.train_dataloader(raw=device_prep, num_workers=workers), device_prep, size, 2, device), None]
+    if val:
+        val_bs = int(config.get("val_batch_size", 4))
+        held = model.val_dataloader(raw=device_prep, num_workers=min(4, workers), batch_size=val_bs)
+        if len(held) == 0:      # drop_last (as the reference has it) would leave no batch and validation nothing to average
+            raise SystemExit(f"--val: {len(held.dataset)} validation pairs are fewer than val_batch_size = {val_bs}")
+        loaders[1] = device_route(held, device_prep, size, 2, device)
+    return loaders
 
 
 def inpainting_loaders(config, model, batch_size, device_prep, val, workers, device):
@@ -41,7 +80,7 @@ def inpainting_loaders(config, model, batch_size, device_prep, val, workers, dev
     kw = dict(num_workers=workers, collate_fn=dataprep.collate_raw, pin_memory=True) if device_prep else dict(num_workers=workers)
 
     def wrap(loader):
-        return dataprep.DevicePrepLoader(loader, dataprep.DevicePrep(size, 1, device)) if device_prep else loader
+        return device_route(loader, device_prep, size, 1, device)
 
     train = InpaintingDataset(image_list=config["image_path"], mask_path=list(config["train_mask_path"]), mode="train", test_limit=test_limit,
                               **common)
@@ -67,17 +106,18 @@ def main():
     ap.add_argument("--restore", action="store_true")
     ap.add_argument("--no_restore", action="store_true")
     ap.add_argument("--synthetic", type=int, default=0, help="train on N generated batches")
-    ap.add_argument("--dataset", type=str, default=None, help="`inpainting`, or module:Class of a map-style training dataset")
-    ap.add_argument("--device_prep", action="store_true", help="assemble batches on the device from raw decoded images (--dataset inpainting)")
-    ap.add_argument("--val", action="store_true", help="validate on the config's val_image_path / val_mask_path (--dataset inpainting)")
+    ap.add_argument("--dataset", type=str, default=None, help="`crossview`, `inpainting`, or module:Class of a map-style training dataset")
+    ap.add_argument("--device_prep", action="store_true", help="assemble batches on the device from raw decoded images (--dataset inpainting | crossview)")
+    ap.add_argument("--val", action="store_true", help="validate on the config's val_image_path / val_mask_path (--dataset inpainting | crossview)")
     ap.add_argument("--num_workers", type=int, default=8, help="loader workers, at most 8")
     ap.add_argument("--seed", type=int, default=None, help="seed python's, numpy's and torch's generators")
     ap.add_argument("--log_every_n_steps", type=int, default=50)
     ap.add_argument("--loss_file", type=str, default=None, help="write every step's loss as a JSON list when the run ends")
+    ap.add_argument("--index_file", type=str, default=None, help="write the sampler's indices, one list per epoch, as JSON when the run ends (--dataset crossview)")
     ap.add_argument("--hip_graph", action="store_true", help="replay the whole step as one hipGraph (fixed shapes)")
     a = ap.parse_args()
-    if (a.device_prep or a.val) and a.dataset != "inpainting":
-        raise SystemExit("--device_prep and --val need --dataset inpainting")
+    if (a.device_prep or a.val) and a.dataset not in ("inpainting", "crossview"):
+        raise SystemExit("--device_prep and --val need --dataset inpainting or --dataset crossview")
     if a.seed is not None:
         import random
         import numpy as np
@@ -108,12 +148,16 @@ def main():
     if a.restore and resume is None:
         raise FileNotFoundError(last)
     bs = int(config.get("batch_size", 1))
-    val_data = val_every = None
-    if a.dataset == "inpainting":
-        data, val_data = inpainting_loaders(config, model, bs, a.device_prep, a.val, min(8, max(0, a.num_workers)), f"cuda:{rank}")
-        if val_data is not None:
-            every = config.get("val_check_interval", 1.0)
-            val_every = max(1, int(every * len(data))) if isinstance(every, float) else int(every)
+    trainer = Trainer(max_steps=int(config["max_steps"]), accumulate_grad_batches=int(config.get("accumulate_grad_batches") or 1),
+                      log_every_n_steps=a.log_every_n_steps, precision=16 if a.fp16 else ("bf16" if a.bf16 else 32), default_root_dir=root,
+                      resume_from_checkpoint=resume, hip_graph=a.hip_graph, local_rank=rank)
+    model.trainer = trainer      # the model's loaders read their rank here
+    val_data = None
+    workers = min(8, max(0, a.num_workers))
+    if a.dataset == "crossview":
+        data, val_data = crossview_loaders(config, model, a.device_prep, a.val, workers, f"cuda:{rank}")
+    elif a.dataset == "inpainting":
+        data, val_data = inpainting_loaders(config, model, bs, a.device_prep, a.val, workers, f"cuda:{rank}")
     elif a.dataset:
         mod, cls = a.dataset.split(":")
         data = torch.utils.data.DataLoader(getattr(importlib.import_module(mod), cls)(**dict(model.data_cfg)), batch_size=bs, shuffle=True,
@@ -121,15 +165,20 @@ def main():
     elif a.synthetic:
         data = list(synthetic_batches(a.synthetic, bs, int(model.img_size), seed=rank))
     else:
-        raise SystemExit("give --synthetic N, --dataset inpainting or --dataset module:Class")
-    trainer = Trainer(max_steps=int(config["max_steps"]), accumulate_grad_batches=int(config.get("accumulate_grad_batches") or 1),
-                      val_check_interval=val_every, log_every_n_steps=a.log_every_n_steps, precision=16 if a.fp16 else ("bf16" if a.bf16 else 32), default_root_dir=root,
-                      resume_from_checkpoint=resume, hip_graph=a.hip_graph, local_rank=rank)
+        raise SystemExit("give --synthetic N, --dataset crossview, --dataset inpainting or --dataset module:Class")
+    drawn = record_draws(data.sampler) if a.index_file and a.dataset == "crossview" else None
+    if val_data is not None:
+        every = config.get("val_check_interval", 1.0)
+        trainer.val_check_interval = max(1, int(every * len(data))) if isinstance(every, float) else int(every)
     trainer.fit(model, data, val_data)
     if a.loss_file and rank == 0:
         import json
         with open(a.loss_file, "w") as f:
             json.dump(torch.stack(trainer.loss_history).tolist(), f)      # one read-back, after the run
+    if drawn is not None and rank == 0:
+        import json
+        with open(a.index_file, "w") as f:
+            json.dump(drawn, f)
     print("saved", last)
 
 
