@@ -687,6 +687,53 @@ typedef struct lr_prep_job {
 int lr_batch_prep(const uint8_t* arena, int64_t arena_bytes, const lr_prep_job* jobs, const lr_prep_job* jobs_host, int n_jobs, int S,
                   int tiles, int B, float* image, float* masked_image, float* mask, lr_stream_t s);
 
+/* ---- assembling a novel-view-synthesis batch from raw RGBA renders: composite on white, 8-bit bilinear resize, alpha occupancy,
+ *      elliptic dilation, stroke / file masks and the [-1, 1] mapping in one launch (added under ABI 30 like lr_batch_prep: one new
+ *      symbol, nothing renumbered or re-typed; a library without it fails to bind) -------------------------------------------------------
+ * replaces: the per-sample host work of the Objaverse loader --
+ *             `imread(UNCHANGED) / 255.`, alpha == 0 -> white, `* 255.` to uint8, `cv2.resize(im, (S, S))`   dataloaders/obj_nvs_dataset.py:117-129
+ *             `cv2.resize(alpha > 0, (S, S), INTER_AREA) > 0`, `cv2.dilate(mask, MORPH_ELLIPSE k x k)`, `clip(mask + strokes, 0, 1)`,
+ *             the ones mask, the fixed mask file, [cond | target], `/ 127.5 - 1`, `* (mask < 0.5)`, the white right half    :130-189
+ *           in this tree leftrefill_amd/nvsprep.py (run_nvs_plan_numpy), whose numpy statement is the yardstick.
+ * arena: the batch's raw bytes on the device, 16-byte aligned and a multiple of 16 long; every render (uint8 [h][w][4] RGBA) and
+ * plane (uint8 [S][S]) starts at a 16-byte-aligned offset (LR_E_ALIGN).  jobs: B lr_nvs_job on the device, one per sample,
+ * jobs_host the same table in host memory -- every offset, size, k and span is checked there before the launch.
+ * A job is the S x 2S canvas [cond | target] of sample `sample`:
+ *   image, both tiles: a pixel of alpha 0 becomes RGB 255, every other keeps its bytes; then to S x S in integer arithmetic --
+ *   h == w == S: copy; h == w == 2S: (a + b + c + d + 2) >> 2 over each 2 x 2 block; else, per axis of n cells,
+ *   f = (float)((d + 0.5) * ((double)n / S) - 0.5), s = floor(f), f -= s, (s < 0: s = 0, f = 0; s >= n - 1: s = n - 1, f = 0), taps
+ *   s and min(s + 1, n - 1), a0 = rint((1.f - f) * 2048), a1 = rint(f * 2048), R = S0 a0 + S1 a1 along the row,
+ *   out = (((b0 (R0 >> 4)) >> 16) + ((b1 (R1 >> 4)) >> 16) + 2) >> 2 down the column; then v / 127.5f - 1.  A render smaller than S on
+ *   either axis is LR_E_UNSUPPORTED.
+ *   mask, target tile (the cond tile's is 0):
+ *     LR_NVS_MODE_ALPHA: occupancy(i, j) = any alpha > 0 over the product of the axes' area taps (per axis: scale = n / S,
+ *       f1 = d scale, f2 = f1 + scale, s1 = ceil(f1), s2 = min(floor(f2), n - 1), s1 = min(s1, s2); cells s1 .. s2 - 1, cell s1 - 1
+ *       iff s1 - f1 > 1e-3, cell s2 iff f2 - s2 > 1e-3), dilated by the k x k element whose row e has ones in columns
+ *       [lo[e], hi[e]), anchor (k / 2, k / 2): dst(y, x) = OR src(y + e - k / 2, x + j - k / 2), outside ignored; 1 <= k <=
+ *       LR_NVS_MAX_DILATE, lo[e] < hi[e] <= k (larger k: LR_E_UNSUPPORTED); OR-ed with plane > 0 where plane_off >= 0.
+ *     LR_NVS_MODE_ONES: 1.   LR_NVS_MODE_FILE: (float)(plane / 255.0), not thresholded.
+ *   masked_image = image * (mask < 0.5 ? 1.f : 0.f); with LR_NVS_REF_WHITE the target tile's is 1.f * (mask < 0.5 ? 1.f : 0.f).
+ * image, masked_image [B][S][2S][3], mask [B][S][2S][1] fp32.  S <= LR_NVS_MAX_SIZE.
+ * One launch, workgroups own (sample, tile, band of output rows); plain stores, no atomics, nothing read back: capturable. */
+#define LR_NVS_MODE_ALPHA 0
+#define LR_NVS_MODE_ONES 1
+#define LR_NVS_MODE_FILE 2
+#define LR_NVS_REF_WHITE 1
+#define LR_NVS_MAX_SIZE 512
+#define LR_NVS_MAX_DILATE 32
+typedef struct lr_nvs_job {
+  int64_t cond_off, target_off;   /* byte offsets into the arena, multiples of 16 */
+  int64_t plane_off;              /* -1: none */
+  int32_t cond_h, cond_w, target_h, target_w;
+  int32_t mode;                   /* LR_NVS_MODE_* */
+  int32_t k;                      /* side of the dilation element (LR_NVS_MODE_ALPHA) */
+  int32_t flags;                  /* LR_NVS_REF_WHITE */
+  int32_t sample;
+  uint8_t lo[LR_NVS_MAX_DILATE], hi[LR_NVS_MAX_DILATE];
+} lr_nvs_job;
+int lr_nvs_prep(const uint8_t* arena, int64_t arena_bytes, const lr_nvs_job* jobs, const lr_nvs_job* jobs_host, int B, int S,
+                float* image, float* masked_image, float* mask, lr_stream_t s);
+
 /* ---- bfloat16 twins: same signatures and semantics as the fp16 entry points above, every lr_half is bfloat16 bits -------- */
 int lr_groupnorm_stats_bf16(const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, float* partials,
     lr_stream_t s);

@@ -110,6 +110,13 @@ class PrepJob(ctypes.Structure):
                [(n, ctypes.c_int32) for n in ("outpaint_col", "flags", "sample", "tile")]
 
 
+class NvsJob(ctypes.Structure):
+    """struct lr_nvs_job (include/leftrefill_hip.h); leftrefill_amd.nvsprep.JOB_DTYPE is its numpy image."""
+    _fields_ = [("cond_off", c_int64), ("target_off", c_int64), ("plane_off", c_int64)] + \
+               [(n, ctypes.c_int32) for n in ("cond_h", "cond_w", "target_h", "target_w", "mode", "k", "flags", "sample")] + \
+               [("lo", ctypes.c_uint8 * 32), ("hi", ctypes.c_uint8 * 32)]
+
+
 class OptimTensor(ctypes.Structure):
     """struct lr_optim_tensor (include/leftrefill_hip.h)."""
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("numel", ctypes.c_int64),
@@ -205,6 +212,8 @@ SIGNATURES = {
     "lr_lpips_alex": [ctypes.POINTER(LpipsArgs), c_void_p],
     # added under ABI 30 as well: batch assembly from raw decoded images (csrc/batch_prep.hip)
     "lr_batch_prep": [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    # added under ABI 30 as well: NVS batch assembly from raw RGBA renders (csrc/nvs_prep.hip)
+    "lr_nvs_prep": [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
 }
 INT64_RETURNS = ("lr_gemm_workspace_bytes", "lr_lpips_workspace_bytes")
 

@@ -348,5 +348,9 @@ class DevicePrepLoader:
     def sampler(self):
         return self.loader.sampler
 
+    @property
+    def dataset(self):
+        return self.loader.dataset
+
     def __iter__(self):
         return (self.prep(batch) for batch in self.loader)

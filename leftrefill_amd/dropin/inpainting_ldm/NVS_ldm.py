@@ -9,8 +9,10 @@ configs/nvs_training_config.yaml) on the MI355X build.
 `NVSLDM` (107-298): conditioning glue (get_input with the refinement branch, unconditional prompts incl. deep prompts), `log_images`,
 `log_multi_cond_images` (K conditionings through DDIMSampler.ddim_multi_sampling) and `sample_log`; the parameter groups its
 optimizer owns (`trainable_parameters`, reference 314-337); `validation_step` / `validation_epoch_end` (374-412): the right half of
-the RAW prediction (no paste: "whole image test", 380-381) scored by the HIP metrics kernel (evalglue.device_metrics).  The other
-Lightning hooks, dataloaders and LoRA injection (299-372, 414-435) stay out of scope.  The shipped configs use the plain UNetModel with `use_sep: False` and no refinement; the
+the RAW prediction (no paste: "whole image test", 380-381) scored by the HIP metrics kernel (evalglue.device_metrics).  
+`train_dataloader` / `val_dataloader` (348-372) build the Objaverse dataset (dropin dataloaders/obj_nvs_dataset.py; the DTU branches
+raise: the reference tree ships no such modules) and `on_train_batch_end` (299-306) is the mask warm-up.  The progress-bar hook and
+LoRA injection (308-312, 414-435) stay out of scope.  The shipped configs use the plain UNetModel with `use_sep: False` and no refinement; the
 class is kept a drop-in for checkpoints / configs that turn them on.
 """
 import torch
@@ -197,6 +199,44 @@ class NVSLDM(LatentInpaintDiffusion):
 
     def validation_epoch_end(self, outputs):
         return evalglue.validation_epoch_mean(self, outputs)
+
+    # ---- data (reference 299-306, 348-372) ----------------------------------------------------------------------------------------------
+    def _objaverse(self, listfile, mode, raw):
+        if not self.data_cfg.get("obj_dataset"):
+            raise NotImplementedError("the DTU novel-view datasets (data_config.obj_dataset: False) are no part of the reference tree; "
+                                      "this build has the Objaverse dataset only")
+        from leftrefill_amd.dropin.dataloaders.obj_nvs_dataset import NVS_OBJDataset
+        return NVS_OBJDataset(datapath=self.cfg["datapath"], listfile=self.cfg[listfile], mode=mode, img_size=self.img_size, raw=raw,
+                              **self.data_cfg)
+
+    @staticmethod
+    def _loader_kw(raw, workers):
+        from leftrefill_amd import nvsprep
+        return dict(num_workers=workers, collate_fn=nvsprep.collate_nvs_raw, pin_memory=True) if raw else dict(num_workers=workers)
+
+    def train_dataloader(self, raw=False, num_workers=8):
+        """raw=True: the loader hands out `nvsprep.collate_nvs_raw` batches for an `nvsprep.NVSDevicePrep`."""
+        from torch.utils.data import DataLoader
+        return DataLoader(self._objaverse("train_list", "train", raw), batch_size=self.cfg["batch_size"], shuffle=True,
+                          **self._loader_kw(raw, num_workers))
+
+    def val_dataloader(self, raw=False, num_workers=4, batch_size=4):
+        from torch.utils.data import DataLoader
+        return DataLoader(self._objaverse("val_list", "val", raw), batch_size=batch_size, shuffle=False, drop_last=True,
+                          **self._loader_kw(raw, num_workers))
+
+    def on_train_batch_end(self, *args, **kwargs):
+        """The mask warm-up (reference 299-306): over `warmup_mask_steps` steps the training dataset's `complete_mask_rate` rises
+        linearly from its configured value to 1.  The dataset is the one reached through `trainer.train_dataloader`; loader workers
+        hold copies of it and see the new rate when they are re-created -- at the next epoch --, as in the reference."""
+        hook = getattr(super(), "on_train_batch_end", None)
+        if hook is not None:
+            hook(*args, **kwargs)
+        if self.warmup_mask_steps > 0 and self.mask_steps <= self.warmup_mask_steps:
+            dataset = self.trainer.train_dataloader.dataset
+            dataset.complete_mask_rate = min(1.0, self.complete_mask_rate +
+                                             (self.mask_steps / self.warmup_mask_steps * (1.0 - self.complete_mask_rate)))
+            self.mask_steps += 1
 
     # ---- training (reference 314-345, 418-435) -------------------------------------------------------------------------------------------
     def configure_optimizers(self):

@@ -1,0 +1,245 @@
+"""tests/golden/nvs_dataset.npz: the reference's Objaverse NVS dataset, run by the reference's own control flow.  CPU only.
+
+    python tools/make_golden_nvs_dataset.py --reference DIR
+
+The reference's dataloaders/obj_nvs_dataset.py imports OpenCV, which is absent here.  This tool puts a small functional stand-in
+into sys.modules["cv2"] -- `imread` through PIL (BGRA with IMREAD_UNCHANGED, else BGR), `resize` dispatching to this project's
+`resize_linear_u8` (the default interpolation) and `occupancy` (INTER_AREA; it returns the {0, 1} occupancy, which is all the
+reference keeps of the area average: it thresholds `> 0` at once), `getStructuringElement` from `ellipse_spans`, `dilate` -- and
+imports the reference module by path.  So the draw order and count, every branch decision, the composite, the bounding box, the PIL
+strokes, the canvas and the pose in the file are the reference's; only the four OpenCV primitives are restated.
+
+It builds a small seeded tree in a temporary directory (`write_tree`, which the tests use to rebuild it from the file): objects of
+NVIEWS RGBA renders each -- 64 x 64 (the 2 x 2 box at S = 32), 48 x 40 (the general bilinear, both axes non-integer), 32 x 32 (the
+copy) and one object without any alpha --, noise in every RGB byte (also under alpha 0), objects that touch a border or a corner in
+some views, camera matrices, list files, and S x S grey mask files with levels around 127 / 128.  Recorded: the inputs and the layout;
+for each of SETTINGS the finished items of a seeded sequence, their poses and prompts, and the next random.random() /
+np.random.random() after it (which pins the draw count); the tally of reference branches hit (asserted complete: `BRANCH_LINES`).
+
+An item is stored as uint8 levels of image and mask; the tool asserts that this loses nothing: image == levels / 127.5 - 1 in
+float32, mask == float32(mask_levels / 255.), masked_image == (image, or [cond | white] under use_ref_mask) * (mask < 0.5)
+(`unpack_items` restores them with those expressions).
+"""
+import argparse
+import importlib.util
+import json
+import os
+import random
+import sys
+import tempfile
+import types
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+OUT = os.path.join(ROOT, "tests", "golden", "nvs_dataset.npz")
+S, NVIEWS = 32, 4
+TOKEN_MAP = dict(left_token="<left>", right_token="<right>", task_token="<views>", real_token="<scene>")
+SP = dict(repeat_sp_token=3, sp_token="<special-token>")
+OBJECTS = [("obj_box", 64, 64, "blob"), ("obj_general", 48, 40, "blob"), ("obj_copy", 32, 32, "blob"), ("obj_empty", 32, 32, "empty")]
+BASE = dict(datapath="@objects", listfile="@train.txt", img_size=S, nviews=NVIEWS, pts_size=[3, 6], width_range=[32, 96])
+SETTINGS = {      # name -> (constructor keywords, seed, item indices)
+    "train_enlarge": (dict(BASE, mode="train", dilate_size=[3, 9], mask_enlarge=[0.05, 0.2], token_map=TOKEN_MAP), 31, [0, 1, 2, 3, 0, 1, 2]),
+    "train_rate": (dict(BASE, mode="train", dilate_size=[10, 25], complete_mask_rate=0.4, deep_prompt=True, **SP), 32, [0, 1, 2, 0, 1, 2, 3, 1]),
+    "train_small_k": (dict(BASE, mode="train", dilate_size=[1, 2], **SP), 33, [0, 1, 2]),
+    "val_file": (dict(BASE, mode="val", listfile="@val.txt", mask_file_path="@masks", mask_type="fix", **SP), 34, [0, 1, 2]),
+    "val_file_ref": (dict(BASE, mode="val", listfile="@val.txt", mask_file_path="@masks", mask_type="fix", use_ref_mask=True, **SP), 35, [0, 1, 2]),
+    "val_complete": (dict(BASE, mode="val", listfile="@val.txt", mask_type="complete", token_map=TOKEN_MAP), 36, [0, 1]),
+    "val_alpha_ref": (dict(BASE, mode="val", listfile="@val.txt", dilate_size=[26, 32], use_ref_mask=True, token_map=TOKEN_MAP), 37, [0, 1, 2, 3]),
+}
+# reference line -> branch name: every one must be executed by the recorded sequences
+BRANCH_LINES = {57: "prompt: repeated token", 61: "prompt: per layer", 77: "prompt: drawn template", 79: "prompt: first template",
+                113: "views: sampled", 115: "views: fixed", 136: "mask file of the cond view", 138: "mask file of the target view",
+                141: "complete mask", 144: "complete_mask_rate", 150: "no alpha: ones", 156: "box enlarged", 177: "dilated | strokes",
+                185: "white right half", 189: "masked image"}
+
+
+# ---- the tree -----------------------------------------------------------------------------------------------------------------------
+def make_inputs():
+    """Arrays and layout of the tree, seeded."""
+    rng = np.random.RandomState(2025)
+    fx, png, npy = {}, {}, {}
+    for name, h, w, kind in OBJECTS:
+        for v in range(NVIEWS):
+            rgba = rng.randint(0, 256, (h, w, 4), dtype=np.uint8)
+            alpha = np.zeros((h, w), np.uint8)
+            if kind == "blob":      # views 0 .. 3: inside, on the top-left corner, on the bottom and right borders, two small far pieces
+                boxes = [[(h // 4, h // 2, w // 3, w // 3 + max(4, w // 4))], [(0, h // 3, 0, w // 4)], [(h - h // 5, h, w // 2, w)],
+                         [(1, 3, w - 2, w), (h - 7, h - 4, 2, 5)]][v]
+                for ya, yb, xa, xb in boxes:
+                    alpha[ya:yb, xa:xb] = rng.choice(np.array([1, 2, 128, 254, 255], np.uint8), size=(yb - ya, xb - xa))
+            rgba[:, :, 3] = alpha
+            fx[f"{name}_{v}"] = rgba
+            png[f"objects/{name}/{v:03d}.png"] = f"{name}_{v}"
+            rt = np.concatenate([np.linalg.qr(rng.normal(size=(3, 3)))[0], rng.normal(size=(3, 1)) * 1.5], axis=1)
+            fx[f"{name}_{v}_rt"] = rt
+            npy[f"objects/{name}/{v:03d}.npy"] = f"{name}_{v}_rt"
+            if v in (0, 2):      # the fixed masks of the val views: blocks of grey levels on both sides of the 0.5 test
+                levels = np.array([0, 0, 1, 126, 127, 128, 129, 255, 255], dtype=np.uint8)
+                fx[f"{name}_{v}_mask"] = np.kron(rng.choice(levels, size=(S // 4, S // 4)), np.ones((4, 4), np.uint8))
+                png[f"masks/{name}/{v:03d}.png"] = f"{name}_{v}_mask"
+    names = [o[0] for o in OBJECTS]
+    fx["layout"] = np.array(json.dumps(dict(png=png, npy=npy, lists={"train.txt": names, "val.txt": names})))
+    return fx
+
+
+def write_tree(root, fx):
+    """Write the tree the arrays and the `layout` of `fx` (the tool's inputs, or the loaded fixture) describe under `root`."""
+    from PIL import Image
+    layout = json.loads(str(fx["layout"]))
+    for rel, key in layout["png"].items():
+        os.makedirs(os.path.dirname(os.path.join(root, rel)), exist_ok=True)
+        Image.fromarray(np.asarray(fx[key])).save(os.path.join(root, rel))
+    for rel, key in layout["npy"].items():
+        np.save(os.path.join(root, rel), np.asarray(fx[key]))
+    for rel, names in layout["lists"].items():
+        with open(os.path.join(root, rel), "w") as f:
+            f.write("".join(n + "\n" for n in names))
+
+
+def resolve(kwargs, root):
+    """Constructor keywords with "@name" entries turned into paths under root."""
+    return {k: os.path.join(root, v[1:]) if isinstance(v, str) and v.startswith("@") else v for k, v in kwargs.items()}
+
+
+def run_sequence(cls, kwargs, seed, indices, root, **extra):
+    """Seed both generators, build `cls(**kwargs)`, take the items in order; (items, next random.random(), next np.random.random())."""
+    ds = cls(**resolve(kwargs, root), **extra)
+    random.seed(seed)
+    np.random.seed(seed)
+    items = [ds[i] for i in indices]
+    return items, random.random(), np.random.random()
+
+
+def ref_white(kwargs):
+    return kwargs["mode"] != "train" and bool(kwargs.get("use_ref_mask", False))
+
+
+# ---- items <-> arrays ---------------------------------------------------------------------------------------------------------------
+def masked_of(image, mask, white):
+    if white:
+        image = np.concatenate([image[:, :image.shape[1] // 2], np.ones_like(image[:, image.shape[1] // 2:])], axis=1)
+    return image * (mask < 0.5)
+
+
+def pack_items(items, white):
+    """uint8 levels of image and mask, poses and JSON prompts of finished items, after asserting that this loses nothing."""
+    levels, mask_levels, poses = [], [], []
+    for it in items:
+        image, mask, masked = np.asarray(it["image"]), np.asarray(it["mask"]), np.asarray(it["masked_image"])
+        u8 = np.rint((image.astype(np.float64) + 1.0) * 127.5).astype(np.uint8)
+        f32 = u8.astype(np.float32) / 127.5 - 1.0
+        assert image.dtype == np.float32 and np.array_equal(f32, image), "image is not levels / 127.5 - 1 in float32"
+        m8 = np.rint(mask.astype(np.float64) * 255.0).astype(np.uint8)
+        m32 = (m8 / 255).astype(np.float32)
+        assert np.array_equal(m32, mask) and not m8[:, :m8.shape[1] // 2].any(), "mask is not float32(levels / 255.), or not 0 on the left"
+        assert masked.dtype == np.float32 and masked.tobytes() == masked_of(f32, m32, white).tobytes(), "masked_image"
+        levels.append(u8)
+        mask_levels.append(m8[:, :, 0])
+        poses.append(np.asarray(it["rel_pose"], dtype=np.float32))
+    txt = [[str(t) for t in it["txt"]] if isinstance(it["txt"], (list, tuple)) else str(it["txt"]) for it in items]
+    return np.stack(levels), np.stack(mask_levels), np.stack(poses), json.dumps(txt)
+
+
+def unpack_items(levels, mask_levels, poses, txt, white):
+    """The float32 items `pack_items` stored."""
+    items = []
+    for u8, m8, pose, t in zip(levels, mask_levels, poses, json.loads(str(txt))):
+        image = u8.astype(np.float32) / 127.5 - 1.0
+        mask = (m8 / 255).astype(np.float32)[:, :, None]
+        items.append(dict(image=image, mask=mask, masked_image=masked_of(image, mask, white), rel_pose=pose, txt=t))
+    return items
+
+
+# ---- the reference ------------------------------------------------------------------------------------------------------------------
+def cv2_standin():
+    from PIL import Image
+    from leftrefill_amd import nvsprep
+    cv2 = types.ModuleType("cv2")
+    cv2.IMREAD_UNCHANGED, cv2.IMREAD_COLOR, cv2.INTER_LINEAR, cv2.INTER_AREA, cv2.MORPH_ELLIPSE = -1, 1, 1, 3, 2
+
+    def element(k):
+        el = np.zeros((k, k), np.uint8)
+        for e, (lo, hi) in enumerate(nvsprep.ellipse_spans(k)):
+            el[e, lo:hi] = 1
+        return el
+
+    def imread(path, flag=1):
+        if flag == cv2.IMREAD_UNCHANGED:
+            img = Image.open(path)
+            assert img.mode == "RGBA", img.mode
+            return np.array(img)[:, :, [2, 1, 0, 3]].copy()      # BGRA
+        return np.array(Image.open(path).convert("RGB"))[:, :, ::-1].copy()      # BGR
+
+    def resize(img, dsize, interpolation=1):
+        assert dsize[0] == dsize[1]
+        if interpolation == cv2.INTER_AREA:
+            assert img.ndim == 2
+            return nvsprep.occupancy(img, dsize[0]).astype(img.dtype)
+        assert interpolation == cv2.INTER_LINEAR and img.dtype == np.uint8 and img.ndim == 3
+        return nvsprep.resize_linear_u8(np.ascontiguousarray(img), dsize[0])
+
+    def structuring(shape, ksize):
+        assert shape == cv2.MORPH_ELLIPSE and ksize[0] == ksize[1]
+        return element(ksize[0])
+
+    def dilate(src, kernel, iterations=1):
+        k = kernel.shape[0]
+        assert iterations == 1 and np.array_equal(kernel, element(k)) and np.isin(src, (0, 1)).all()
+        return nvsprep.dilate(src > 0, k).astype(src.dtype)
+
+    cv2.imread, cv2.resize, cv2.getStructuringElement, cv2.dilate = imread, resize, structuring, dilate
+    return cv2
+
+
+def import_reference(ref_dir):
+    path = os.path.join(ref_dir, "dataloaders", "obj_nvs_dataset.py")
+    sys.modules["cv2"] = cv2_standin()
+    spec = importlib.util.spec_from_file_location("reference_obj_nvs_dataset", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod, path
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reference", default=os.environ.get("LEFTREFILL_REFERENCE"), help="checkout of the reference project")
+    ap.add_argument("--out", default=OUT)
+    a = ap.parse_args()
+    if not a.reference:
+        raise SystemExit("give --reference DIR (or LEFTREFILL_REFERENCE)")
+    ref, ref_file = import_reference(a.reference)
+    fx = make_inputs()
+    tally = {name: 0 for name in BRANCH_LINES.values()}
+
+    def tracer(frame, event, arg):
+        if frame.f_code.co_filename != ref_file:
+            return None
+        if event == "line" and frame.f_lineno in BRANCH_LINES:
+            tally[BRANCH_LINES[frame.f_lineno]] += 1
+        return tracer
+
+    out = dict(fx)
+    with tempfile.TemporaryDirectory() as root:
+        write_tree(root, fx)
+        sys.settrace(tracer)
+        try:
+            for name, (kwargs, seed, indices) in SETTINGS.items():
+                items, nxt, np_nxt = run_sequence(ref.NVS_OBJDataset, kwargs, seed, indices, root)
+                assert all(it["image"].shape == (S, 2 * S, 3) and it["mask"].shape == (S, 2 * S, 1) for it in items)
+                out[f"{name}/levels"], out[f"{name}/mask_levels"], out[f"{name}/rel_pose"], out[f"{name}/txt"] = \
+                    pack_items(items, ref_white(kwargs))
+                out[f"{name}/next"] = np.array([nxt, np_nxt])
+        finally:
+            sys.settrace(None)
+    missed = [name for name, n in tally.items() if n == 0]
+    assert not missed, f"branches the sequences never took: {missed}"
+    out["spec"] = np.array(json.dumps(dict(settings=SETTINGS, branch_tally=tally)))
+    np.savez_compressed(a.out, **out)
+    print(json.dumps(tally, indent=1))
+    print(f"wrote {a.out}: {os.path.getsize(a.out) / 1024:.0f} KiB")
+
+
+if __name__ == "__main__":
+    main()

@@ -16,9 +16,13 @@ data section ([reference | target] canvases, view masks, matching-based masks, .
 InpaintingDataset` drop-in (the reference's single-image training set) from the config's `image_path` and `train_mask_path` (the
 irregular and the segmentation mask list) and the model's data section; --dataset module:Class builds `Class(**data_cfg)`;
 --synthetic N trains on N generated batches with the evaluation harness' batch contract (tools/run_inpainting.py).
---device_prep (with --dataset inpainting | crossview): the loader's workers only decode and plan; resize, crop, flips, masks and the
+--dataset objaverse builds the Objaverse novel-view dataset (`leftrefill_amd.dropin.dataloaders.obj_nvs_dataset.NVS_OBJDataset`) for an
+`NVSLDM` model config from the training config's `datapath`, `train_list`, `val_list` and `batch_size` and the model's data section --
+the model's own `train_dataloader` / `val_dataloader`; with --device_prep a batch of raw RGBA renders is finished by one
+`lr_nvs_prep` launch (leftrefill_amd/nvsprep.py, csrc/nvs_prep.hip).
+--device_prep (with --dataset inpainting | crossview | objaverse): the loader's workers only decode and plan; resize, crop, flips, masks and the
 [-1, 1] mapping of a whole batch are one HIP kernel launch (leftrefill_amd/dataprep.py, csrc/batch_prep.hip).
---val (with --dataset inpainting | crossview): the `val`-mode dataset over `val_image_path` / `val_mask_path` (`test_limit` images,
+--val (with --dataset inpainting | crossview | objaverse): the `val`-mode dataset over `val_image_path` / `val_mask_path` (objaverse: `val_list`;`test_limit` images,
 batches of `val_batch_size`, default 4; `test_limit` from the model's data section, else the training config) is validated every
 `val_check_interval` steps (a fraction: of an epoch) and its metrics printed.
 """
@@ -67,6 +71,28 @@ def crossview_loaders(config, model, device_prep, val, workers, device):
     return loaders
 
 
+def objaverse_loaders(config, model, device_prep, val, workers, device):
+    """(training batches, validation batches or None) of the Objaverse NVS dataset: NVSLDM's own train_dataloader / val_dataloader
+    (reference NVS_ldm.py:348-372) over the config's `datapath`, `train_list`, `val_list` and `batch_size`; with device_prep the loaders
+    collate raw RGBA renders and an NVSDevicePrep per loader finishes the batches (leftrefill_amd/nvsprep.py, csrc/nvs_prep.hip)."""
+    from leftrefill_amd import dataprep, nvsprep
+    if not hasattr(model, "_objaverse"):
+        raise SystemExit("--dataset objaverse needs a model config whose target is inpainting_ldm.NVS_ldm.NVSLDM")
+    size = int(model.img_size)
+
+    def wrap(loader):
+        return dataprep.DevicePrepLoader(loader, nvsprep.NVSDevicePrep(size, device)) if device_prep else loader
+
+    loaders = [wrap(model.train_dataloader(raw=device_prep, num_workers=workers)), None]
+    if val:
+        val_bs = int(config.get("val_batch_size", 4))
+        held = model.val_dataloader(raw=device_prep, num_workers=min(4, workers), batch_size=val_bs)
+        if len(held) == 0:      # drop_last (as the reference has it) would leave no batch and validation nothing to average
+            raise SystemExit(f"--val: {len(held.dataset)} validation objects are fewer than val_batch_size = {val_bs}")
+        loaders[1] = wrap(held)
+    return loaders
+
+
 def inpainting_loaders(config, model, batch_size, device_prep, val, workers, device):
     """(training batches, validation batches or None) of the single-image dataset, as the reference's train_dataloader builds it
     (ref_inpainting_ldm.py:109-111); with device_prep the loaders collate raw bytes and a DevicePrep per loader finishes the batches."""
@@ -106,9 +132,9 @@ def main():
     ap.add_argument("--restore", action="store_true")
     ap.add_argument("--no_restore", action="store_true")
     ap.add_argument("--synthetic", type=int, default=0, help="train on N generated batches")
-    ap.add_argument("--dataset", type=str, default=None, help="`crossview`, `inpainting`, or module:Class of a map-style training dataset")
-    ap.add_argument("--device_prep", action="store_true", help="assemble batches on the device from raw decoded images (--dataset inpainting | crossview)")
-    ap.add_argument("--val", action="store_true", help="validate on the config's val_image_path / val_mask_path (--dataset inpainting | crossview)")
+    ap.add_argument("--dataset", type=str, default=None, help="`crossview`, `inpainting`, `objaverse`, or module:Class of a map-style training dataset")
+    ap.add_argument("--device_prep", action="store_true", help="assemble batches on the device from raw decoded images (--dataset inpainting | crossview | objaverse)")
+    ap.add_argument("--val", action="store_true", help="validate on the config's val_image_path / val_mask_path, or val_list (--dataset inpainting | crossview | objaverse)")
     ap.add_argument("--num_workers", type=int, default=8, help="loader workers, at most 8")
     ap.add_argument("--seed", type=int, default=None, help="seed python's, numpy's and torch's generators")
     ap.add_argument("--log_every_n_steps", type=int, default=50)
@@ -116,8 +142,8 @@ def main():
     ap.add_argument("--index_file", type=str, default=None, help="write the sampler's indices, one list per epoch, as JSON when the run ends (--dataset crossview)")
     ap.add_argument("--hip_graph", action="store_true", help="replay the whole step as one hipGraph (fixed shapes)")
     a = ap.parse_args()
-    if (a.device_prep or a.val) and a.dataset not in ("inpainting", "crossview"):
-        raise SystemExit("--device_prep and --val need --dataset inpainting or --dataset crossview")
+    if (a.device_prep or a.val) and a.dataset not in ("inpainting", "crossview", "objaverse"):
+        raise SystemExit("--device_prep and --val need --dataset inpainting, --dataset crossview or --dataset objaverse")
     if a.seed is not None:
         import random
         import numpy as np
@@ -156,6 +182,8 @@ def main():
     workers = min(8, max(0, a.num_workers))
     if a.dataset == "crossview":
         data, val_data = crossview_loaders(config, model, a.device_prep, a.val, workers, f"cuda:{rank}")
+    elif a.dataset == "objaverse":
+        data, val_data = objaverse_loaders(config, model, a.device_prep, a.val, workers, f"cuda:{rank}")
     elif a.dataset == "inpainting":
         data, val_data = inpainting_loaders(config, model, bs, a.device_prep, a.val, workers, f"cuda:{rank}")
     elif a.dataset:
@@ -165,7 +193,7 @@ def main():
     elif a.synthetic:
         data = list(synthetic_batches(a.synthetic, bs, int(model.img_size), seed=rank))
     else:
-        raise SystemExit("give --synthetic N, --dataset crossview, --dataset inpainting or --dataset module:Class")
+        raise SystemExit("give --synthetic N, --dataset crossview, --dataset inpainting, --dataset objaverse or --dataset module:Class")
     drawn = record_draws(data.sampler) if a.index_file and a.dataset == "crossview" else None
     if val_data is not None:
         every = config.get("val_check_interval", 1.0)
