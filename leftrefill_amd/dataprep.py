@@ -1,6 +1,7 @@
 """Batch assembly from raw decoded images: the per-sample decisions as a plan of plain scalars, its execution on the host in numpy
 (`run_plan_numpy`, the yardstick) and on the device (`collate_raw` + `DevicePrep`: one arena copy, one job-table copy, one
-`lr_batch_prep` launch per batch, csrc/batch_prep.hip).
+`lr_batch_prep` launch per batch, csrc/batch_prep.hip).  The arena packer, the buffer policy, the uploads and the loader wiring are
+rawbatch.py's, shared with nvsprep.py.
 
 A plan is `{"img_size": S, "tiles": [tile, ...], "txt": prompt}`; the canvas is `len(tiles)` tiles of S x S side by side (the
 single-image training sample has one, the evaluation canvas [source | target] two).  A tile is
@@ -33,15 +34,13 @@ import warnings
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, rawbatch
+from .rawbatch import DevicePrepLoader  # noqa: F401  (its home is rawbatch; importable from here as before)
 from .dropin.dataloaders.test_dataset import _area_weights, resize_nearest
 
 FLIP_IMAGE, FLIP_MASK, ZERO_MASK, HOST = 1, 2, 4, 8      # LR_PREP_* of include/leftrefill_hip.h
 MAX_SIZE, ROW_BYTES = 512, 24576                         # LR_PREP_MAX_SIZE, LR_PREP_ROW_BYTES
-# numpy image of struct lr_prep_job
-JOB_DTYPE = np.dtype([("img_off", "<i8"), ("mask_off", "<i8", (2,)), ("img_h", "<i4"), ("img_w", "<i4"), ("rh", "<i4"), ("rw", "<i4"),
-                      ("y0", "<i4"), ("x0", "<i4"), ("mask_h", "<i4", (2,)), ("mask_w", "<i4", (2,)), ("outpaint_col", "<i4"),
-                      ("flags", "<i4"), ("sample", "<i4"), ("tile", "<i4")])
+JOB_DTYPE = np.dtype(_lib.PrepJob)                       # numpy image of struct lr_prep_job
 assert JOB_DTYPE.itemsize == ctypes.sizeof(_lib.PrepJob) == 80
 
 
@@ -216,11 +215,9 @@ def collate_raw(items, pin=None):
     (so offsets are unaligned), and the lr_prep_job table, one job per tile.  A sample with a tile the kernel does not take is marked
     LR_PREP_HOST and carried along in `host`; `txt` is collated as the DataLoader would.  Multi-view plans (`views`) become B·V samples
     of the table, sample b's view v at index b V + v, over sample b's one set of sources; the batch then carries `views` = V and `idx`.
-    pin: keep arena and table in page-locked memory (default: when a GPU is present and this is not a loader worker -- in a worker
-    leave it to `DataLoader(pin_memory=True)`)."""
-    from torch.utils.data import default_collate, get_worker_info
-    if pin is None:
-        pin = get_worker_info() is None and torch.cuda.is_available()
+    pin: keep arena and table in page-locked memory (default: `rawbatch.default_pin`)."""
+    from torch.utils.data import default_collate
+    pin = rawbatch.default_pin(pin)
     if not all(isinstance(it, tuple) and len(it) == 2 and isinstance(it[0], dict) and ("tiles" in it[0] or "views" in it[0]) for it in items):
         raise TypeError("collate_raw takes (plan, raw) items: build the dataset with raw=True (dataloaders.inpainting_dataset."
                         "InpaintingDataset, dataloaders.raw_pairs.TestInpaintingDataset, dataloaders.inpainting_crossview_dataset's "
@@ -230,7 +227,7 @@ def collate_raw(items, pin=None):
     jobs = np.zeros(len(items) * views * tiles, dtype=JOB_DTYPE)
     jobs["mask_off"] = -1
     jobs["outpaint_col"] = -1
-    placed, host, off = [], [], 0
+    arena, host = rawbatch.Arena(1), []
     for b, (plan, raw) in enumerate(items):
         canvases = plan_canvases(plan)
         assert plan["img_size"] == size and ("views" in plan) == multi and len(canvases) == views and \
@@ -238,16 +235,11 @@ def collate_raw(items, pin=None):
         on_host = any(tile_needs_host(t, raw, size) for c in canvases for t in c)
         if on_host:
             host.append((b, plan, raw))
-        where = {}
+        where = {}      # a source is placed once per sample
 
         def place(i):
-            nonlocal off
             if i not in where:
-                arr = np.ascontiguousarray(raw[i])
-                assert arr.dtype == np.uint8, "raw sources are uint8"
-                where[i] = off
-                placed.append((off, arr))
-                off += arr.size
+                where[i] = arena.add(raw[i])
             return where[i]
 
         for v, canvas in enumerate(canvases):
@@ -268,15 +260,7 @@ def collate_raw(items, pin=None):
                     for q, m in enumerate(tile["masks"]):
                         assert raw[m].ndim == 2, "mask sources are [h, w]"
                         job["mask_off"][q], job["mask_h"][q], job["mask_w"][q] = place(m), raw[m].shape[0], raw[m].shape[1]
-    n = max(16, -(-off // 16) * 16)
-    arena = torch.empty(n, dtype=torch.uint8, pin_memory=bool(pin))
-    table = torch.empty(jobs.nbytes, dtype=torch.uint8, pin_memory=bool(pin))
-    view = arena.numpy()
-    for o, arr in placed:
-        view[o:o + arr.size] = arr.reshape(-1)
-    view[off:] = 0
-    table.numpy()[:] = jobs.view(np.uint8).reshape(-1)
-    out = dict(arena=arena, jobs=table, img_size=size, tiles=tiles, batch=len(items), host=host,
+    out = dict(arena=arena.tensor(pin), jobs=rawbatch.table_tensor(jobs, pin), img_size=size, tiles=tiles, batch=len(items), host=host,
                txt=default_collate([plan["txt"] for plan, _ in items]))
     if multi:
         out.update(views=views, idx=default_collate([plan["idx"] for plan, _ in items]))
@@ -288,69 +272,32 @@ def job_table(batch):
     return batch["jobs"].numpy().view(JOB_DTYPE)
 
 
-class DevicePrep:
-    """collate_raw's batch -> `dict(image, masked_image, mask, txt)` on the device: one copy of the arena, one of the job table, one
-    lr_batch_prep launch.  The arena, table and output buffers are kept and grow only when a batch needs more, so a fixed-shape loop
-    allocates nothing per step -- and the returned tensors are views of those buffers: the next call overwrites them."""
+class DevicePrep(rawbatch.DevicePrepBase):
+    """collate_raw's batch -> `dict(image, masked_image, mask, txt)` on the device by one lr_batch_prep launch (buffers and views:
+    `rawbatch.DevicePrepBase`); a sample marked LR_PREP_HOST is prepared by `run_plan_numpy` and copied in; a multi-view batch comes
+    back as [B, V, ...] views with its `idx`."""
+    entry = "lr_batch_prep"
 
     def __init__(self, img_size, tiles=1, device="cuda"):
-        self.img_size, self.tiles, self.device = int(img_size), int(tiles), torch.device(device)
-        self.arena = self.jobs = self.image = self.masked_image = self.mask = None
+        super().__init__(img_size, tiles, device)
         self.warned = False
 
-    @staticmethod
-    def _grown(buf, n, device):
-        return buf if buf is not None and buf.numel() >= n else torch.empty(n, dtype=torch.uint8, device=device)
+    def dims(self, N):
+        return N * self.tiles, self.img_size, self.tiles, N
 
-    def __call__(self, batch):
-        S, T, B, V = self.img_size, self.tiles, batch["batch"], batch.get("views")
-        assert (batch["img_size"], batch["tiles"]) == (S, T), "the batch was planned for another canvas"
-        N = B * (V or 1)      # canvases: the kernel's samples
-        lib = _lib.load()
-        self.arena = self._grown(self.arena, batch["arena"].numel(), self.device)
-        self.jobs = self._grown(self.jobs, batch["jobs"].numel(), self.device)
-        if self.image is None or self.image.shape[0] < N:
-            self.image = torch.empty(N, S, T * S, 3, device=self.device)
-            self.masked_image = torch.empty(N, S, T * S, 3, device=self.device)
-            self.mask = torch.empty(N, S, T * S, 1, device=self.device)
-        n_bytes, n_jobs = batch["arena"].numel(), N * T
-        self.arena[:n_bytes].copy_(batch["arena"], non_blocking=True)
-        self.jobs[:batch["jobs"].numel()].copy_(batch["jobs"], non_blocking=True)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            _lib.check(lib.lr_batch_prep(self.arena.data_ptr(), n_bytes, self.jobs.data_ptr(), batch["jobs"].data_ptr(), n_jobs, S, T, N,
-                                         self.image.data_ptr(), self.masked_image.data_ptr(), self.mask.data_ptr(), stream), "batch_prep")
+    def finish(self, batch, out):
+        V = batch.get("views")
         for b, plan, raw in batch["host"]:
             if not self.warned:
                 self.warned = True
                 warnings.warn("DevicePrep: a sample enlarges its source (or is wider than the kernel's row buffer) and is prepared "
                               "on the host; further such samples are routed silently")
             done = run_plan_numpy(plan, raw)
-            for k, dst in (("image", self.image), ("masked_image", self.masked_image), ("mask", self.mask)):
+            for k in ("image", "masked_image", "mask"):
                 src = torch.from_numpy(np.ascontiguousarray(done[k]))
-                (dst[b] if V is None else dst[b * V:(b + 1) * V]).copy_(src)
-        if V is None:
-            return dict(image=self.image[:B], masked_image=self.masked_image[:B], mask=self.mask[:B], txt=batch["txt"])
-        shape = lambda t: t[:N].view(B, V, *t.shape[1:])
-        return dict(image=shape(self.image), masked_image=shape(self.masked_image), mask=shape(self.mask), txt=batch["txt"], idx=batch["idx"])
-
-
-class DevicePrepLoader:
-    """A re-iterable of device batches: every batch of `loader` (collate_fn=collate_raw) through `prep`."""
-
-    def __init__(self, loader, prep):
-        self.loader, self.prep = loader, prep
-
-    def __len__(self):
-        return len(self.loader)
-
-    @property
-    def sampler(self):
-        return self.loader.sampler
-
-    @property
-    def dataset(self):
-        return self.loader.dataset
-
-    def __iter__(self):
-        return (self.prep(batch) for batch in self.loader)
+                (out[k][b] if V is None else out[k][b * V:(b + 1) * V]).copy_(src)
+        if V is not None:
+            for k in ("image", "masked_image", "mask"):
+                out[k] = out[k].view(-1, V, *out[k].shape[1:])
+            out["idx"] = batch["idx"]
+        return out

@@ -108,6 +108,12 @@ class InpaintingCrossViewDataset(Dataset):
     def __len__(self):
         return len(self.pairs)
 
+    collate_raw = staticmethod(dataprep.collate_raw)      # collate_fn of the raw=True items (rawbatch.loader)
+
+    def device_prep(self, device="cuda"):
+        """What finishes the collated raw batches on the device: [left | right], two tiles per canvas."""
+        return dataprep.DevicePrep(self.img_size, 2, device)
+
     def _resize(self, img):
         """(resize decisions, crop record) of one image: `plan_resize_train` in train mode, the direct resize otherwise."""
         S = self.img_size
@@ -205,6 +211,12 @@ class InpaintingMultiViewDataset(Dataset):
 
     def __len__(self):
         return len(self.pairs)
+
+    collate_raw = staticmethod(dataprep.collate_raw)      # collate_fn of the raw=True items (rawbatch.loader)
+
+    def device_prep(self, device="cuda"):
+        """What finishes the collated raw batches on the device: one tile per view, [reference | target] under concat_target."""
+        return dataprep.DevicePrep(self.img_size, 2 if self.concat_target else 1, device)
 
     def get_prompt(self):
         """One prompt per view (per canvas under concat_target): the repeated special token, then that view's direction tokens."""

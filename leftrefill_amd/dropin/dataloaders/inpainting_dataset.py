@@ -70,6 +70,12 @@ class InpaintingDataset(Dataset):
     def __len__(self):
         return len(self.image_list)
 
+    collate_raw = staticmethod(dataprep.collate_raw)      # collate_fn of the raw=True items (rawbatch.loader)
+
+    def device_prep(self, device="cuda"):
+        """What finishes the collated raw batches on the device: one tile per canvas."""
+        return dataprep.DevicePrep(self.img_size, 1, device)
+
     def templates(self):
         t = self.token_map
         left, right, task, real = t["left_token"], t["right_token"], t["task_token"], t["real_token"]

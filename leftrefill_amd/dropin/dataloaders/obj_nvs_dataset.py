@@ -86,6 +86,12 @@ class NVS_OBJDataset(Dataset):
     def __len__(self):
         return len(self.metas)
 
+    collate_raw = staticmethod(nvsprep.collate_nvs_raw)      # collate_fn of the raw=True items (rawbatch.loader)
+
+    def device_prep(self, device="cuda"):
+        """What finishes the collated raw batches on the device: [cond | target]."""
+        return nvsprep.NVSDevicePrep(self.img_size, device)
+
     def cartesian_to_spherical(self, xyz):
         xy = xyz[:, 0] ** 2 + xyz[:, 1] ** 2
         z = np.sqrt(xy + xyz[:, 2] ** 2)

@@ -18,7 +18,7 @@ class is kept a drop-in for checkpoints / configs that turn them on.
 import torch
 import torch.nn as nn
 
-from leftrefill_amd import engine, evalglue
+from leftrefill_amd import engine, evalglue, rawbatch
 from ldm.models.diffusion.ddim import DDIMSampler
 from ldm.models.diffusion.ddpm import LatentInpaintDiffusion
 from ldm.modules.diffusionmodules.openaimodel import UNetModel
@@ -209,21 +209,15 @@ class NVSLDM(LatentInpaintDiffusion):
         return NVS_OBJDataset(datapath=self.cfg["datapath"], listfile=self.cfg[listfile], mode=mode, img_size=self.img_size, raw=raw,
                               **self.data_cfg)
 
-    @staticmethod
-    def _loader_kw(raw, workers):
-        from leftrefill_amd import nvsprep
-        return dict(num_workers=workers, collate_fn=nvsprep.collate_nvs_raw, pin_memory=True) if raw else dict(num_workers=workers)
+    def train_dataloader(self, raw=False, num_workers=8, device=None):
+        """raw=True: the loader hands out `nvsprep.collate_nvs_raw` batches; with a device, an `nvsprep.NVSDevicePrep` there finishes
+        them (`rawbatch.loader`)."""
+        return rawbatch.loader(self._objaverse("train_list", "train", raw), raw, device, batch_size=self.cfg["batch_size"], shuffle=True,
+                               num_workers=num_workers)
 
-    def train_dataloader(self, raw=False, num_workers=8):
-        """raw=True: the loader hands out `nvsprep.collate_nvs_raw` batches for an `nvsprep.NVSDevicePrep`."""
-        from torch.utils.data import DataLoader
-        return DataLoader(self._objaverse("train_list", "train", raw), batch_size=self.cfg["batch_size"], shuffle=True,
-                          **self._loader_kw(raw, num_workers))
-
-    def val_dataloader(self, raw=False, num_workers=4, batch_size=4):
-        from torch.utils.data import DataLoader
-        return DataLoader(self._objaverse("val_list", "val", raw), batch_size=batch_size, shuffle=False, drop_last=True,
-                          **self._loader_kw(raw, num_workers))
+    def val_dataloader(self, raw=False, num_workers=4, batch_size=4, device=None):
+        return rawbatch.loader(self._objaverse("val_list", "val", raw), raw, device, batch_size=batch_size, shuffle=False, drop_last=True,
+                               num_workers=num_workers)
 
     def on_train_batch_end(self, *args, **kwargs):
         """The mask warm-up (reference 299-306): over `warmup_mask_steps` steps the training dataset's `complete_mask_rate` rises

@@ -6,14 +6,14 @@ inpainting_ldm/ref_inpainting_ldm.py:30-81) and the attributes callers read (`co
 `validation_epoch_end` (119-157): PSNR / SSIM of the pasted right half come from one HIP kernel (evalglue.device_metrics), LPIPS from
 `loss_fn_alex` when one is set; the optimizer and checkpoint hooks (83-96, 164-173) over leftrefill_amd.optim; and the dataloaders
 (99-117) with the epoch hook (159-161).  `train_dataloader` / `val_dataloader` take `raw=True` for loaders that collate raw decoded
-images for `dataprep.DevicePrep` (tools/train_inpainting.py --device_prep).
+images and `device=` for the dataset's own `DevicePrep` to finish them there (`rawbatch.loader`; tools/train_inpainting.py --device_prep).
 
 Stated deviation: `on_train_epoch_start` sets the sampler's epoch on every rank.  The reference does so only for world_size == 1,
 against its own comment ("we have to set epoch manually if using ddp"); under DDP its ranks would repeat epoch 0's draw for ever.
 """
 import torch
 
-from leftrefill_amd import evalglue
+from leftrefill_amd import evalglue, rawbatch
 
 from ldm.models.diffusion.ddim import DDIMSampler
 from ldm.models.diffusion.ddpm import LatentInpaintDiffusion
@@ -127,12 +127,9 @@ class RefInpaintLDM(LatentInpaintDiffusion):
         return evalglue.validation_epoch_mean(self, outputs)
 
     # ---- data: the loaders of reference 99-117 and the epoch hook of 159-161 ------------------------------------------------------------------
-    def _loader_kw(self, raw, workers):
-        from leftrefill_amd import dataprep
-        return dict(num_workers=workers, collate_fn=dataprep.collate_raw, pin_memory=True) if raw else dict(num_workers=workers)
-
-    def train_dataloader(self, raw=False, num_workers=8):
-        from torch.utils.data import DataLoader
+    def train_dataloader(self, raw=False, num_workers=8, device=None):
+        """raw=True: the loader hands out `dataprep.collate_raw` batches; with a device, a `dataprep.DevicePrep` there finishes them
+        (`rawbatch.loader`)."""
         if self.cfg.get('cross_view_inpainting'):
             from leftrefill_amd.dropin.dataloaders.inpainting_crossview_dataset import BalancedRandomSampler, InpaintingCrossViewDataset
             train_dataset = InpaintingCrossViewDataset(image_path=self.cfg['image_path'], pair_path=self.cfg['train_pair'],
@@ -141,14 +138,13 @@ class RefInpaintLDM(LatentInpaintDiffusion):
             sampler = BalancedRandomSampler(train_dataset.image_dict, train_dataset.pairs,
                                             n_sample_per_scene=self.cfg['n_sample_per_scene'],
                                             rank=self.local_rank, num_replicas=self.world_size)
-            return DataLoader(train_dataset, batch_size=self.cfg['batch_size'], sampler=sampler, **self._loader_kw(raw, num_workers))
+            return rawbatch.loader(train_dataset, raw, device, batch_size=self.cfg['batch_size'], sampler=sampler, num_workers=num_workers)
         from dataloaders.inpainting_dataset import InpaintingDataset
         train_dataset = InpaintingDataset(image_list=self.cfg['image_path'], mask_path=self.cfg['train_mask_path'],
                                           annotation=self.cfg.get('annotation'), mode='train', img_size=self.img_size, raw=raw, **self.data_cfg)
-        return DataLoader(train_dataset, batch_size=self.cfg['batch_size'], shuffle=True, **self._loader_kw(raw, num_workers))
+        return rawbatch.loader(train_dataset, raw, device, batch_size=self.cfg['batch_size'], shuffle=True, num_workers=num_workers)
 
-    def val_dataloader(self, raw=False, num_workers=4, batch_size=4):
-        from torch.utils.data import DataLoader
+    def val_dataloader(self, raw=False, num_workers=4, batch_size=4, device=None):
         from leftrefill_amd.dropin.dataloaders.inpainting_crossview_dataset import InpaintingCrossViewDataset
         data_cfg = dict(self.data_cfg)
         if 'test_limit' in self.cfg:      # the reference's model configs carry it in their data section; a training config may too
@@ -156,7 +152,7 @@ class RefInpaintLDM(LatentInpaintDiffusion):
         val_dataset = InpaintingCrossViewDataset(image_path=self.cfg['val_image_path'], pair_path=None,
                                                  mask_path=self.cfg['val_mask_path'], mode='val', img_size=self.img_size,
                                                  deep_prompt=self.cond_cfg.get('deep_prompt', False), raw=raw, **data_cfg)
-        return DataLoader(val_dataset, batch_size=batch_size, shuffle=False, drop_last=True, **self._loader_kw(raw, num_workers))
+        return rawbatch.loader(val_dataset, raw, device, batch_size=batch_size, shuffle=False, drop_last=True, num_workers=num_workers)
 
     def on_train_epoch_start(self):
         if self.cfg and self.cfg.get('cross_view_inpainting'):      # on every rank (the reference: only without DDP, see above)

@@ -1,6 +1,7 @@
 """Novel-view-synthesis batches from raw RGBA renders: the arithmetic of the Objaverse dataset (reference dataloaders/obj_nvs_dataset.py
 109-189) stated once in numpy -- the host route and the yardstick --, its plan, and the device route (`collate_nvs_raw` +
-`NVSDevicePrep`: one arena copy, one job-table copy, one `lr_nvs_prep` launch per batch, csrc/nvs_prep.hip).
+`NVSDevicePrep`: one arena copy, one job-table copy, one `lr_nvs_prep` launch per batch, csrc/nvs_prep.hip; the arena packer, the
+buffer policy, the uploads and the loader wiring are rawbatch.py's, shared with dataprep.py).
 
 The reference leans on four OpenCV primitives.  OpenCV is absent here, so they are RESTATED below and these statements are the
 definition; they are not pinned against OpenCV itself:
@@ -29,16 +30,13 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, rawbatch
 
 ALPHA, ONES, FILE = 0, 1, 2                  # LR_NVS_MODE_* of include/leftrefill_hip.h
 REF_WHITE = 1                                # LR_NVS_REF_WHITE
 MAX_SIZE, MAX_DILATE = 512, 32               # LR_NVS_MAX_SIZE, LR_NVS_MAX_DILATE
 MODES = {"alpha": ALPHA, "ones": ONES, "file": FILE}
-# numpy image of struct lr_nvs_job
-JOB_DTYPE = np.dtype([("cond_off", "<i8"), ("target_off", "<i8"), ("plane_off", "<i8"), ("cond_h", "<i4"), ("cond_w", "<i4"),
-                      ("target_h", "<i4"), ("target_w", "<i4"), ("mode", "<i4"), ("k", "<i4"), ("flags", "<i4"), ("sample", "<i4"),
-                      ("lo", "u1", (MAX_DILATE,)), ("hi", "u1", (MAX_DILATE,))])
+JOB_DTYPE = np.dtype(_lib.NvsJob)            # numpy image of struct lr_nvs_job
 assert JOB_DTYPE.itemsize == ctypes.sizeof(_lib.NvsJob) == 120
 
 
@@ -186,15 +184,14 @@ def collate_nvs_raw(items, pin=None):
     """DataLoader collate_fn for `NVS_OBJDataset(raw=True)`: a list of (plan, raw) -> one byte arena holding every render and plane at a
     16-byte-aligned offset, the lr_nvs_job table (one job per sample, the element's spans of `ellipse_spans(k)` included), `txt`
     collated as the DataLoader would and `rel_pose` float32 [B, 4].  pin: as `dataprep.collate_raw`."""
-    from torch.utils.data import default_collate, get_worker_info
-    if pin is None:
-        pin = get_worker_info() is None and torch.cuda.is_available()
+    from torch.utils.data import default_collate
+    pin = rawbatch.default_pin(pin)
     if not all(isinstance(it, tuple) and len(it) == 2 and isinstance(it[0], dict) and "mode" in it[0] for it in items):
         raise TypeError("collate_nvs_raw takes (plan, raw) items: build dataloaders.obj_nvs_dataset.NVS_OBJDataset with raw=True")
     size = items[0][0]["img_size"]
     jobs = np.zeros(len(items), dtype=JOB_DTYPE)
     jobs["plane_off"] = -1
-    placed, off = [], 0
+    arena = rawbatch.Arena(16)
     for b, (plan, raw) in enumerate(items):
         assert plan["img_size"] == size, "one canvas shape per batch"
         job = jobs[b]
@@ -203,29 +200,18 @@ def collate_nvs_raw(items, pin=None):
             assert arr.dtype == np.uint8 and arr.ndim == 3 and arr.shape[2] == 4, "renders are uint8 [h, w, 4]"
             if arr.shape[0] < size or arr.shape[1] < size:
                 raise NotImplementedError(f"a {arr.shape[0]} x {arr.shape[1]} render is smaller than img_size = {size}")
-            job[name + "_off"], job[name + "_h"], job[name + "_w"] = off, arr.shape[0], arr.shape[1]
-            placed.append((off, arr))
-            off += -(-arr.size // 16) * 16
+            job[name + "_off"], job[name + "_h"], job[name + "_w"] = arena.add(arr), arr.shape[0], arr.shape[1]
         if plan["plane"] is not None:
             arr = raw[plan["plane"]]
             assert arr.dtype == np.uint8 and arr.shape == (size, size), "the plane is uint8 [S, S]"
-            job["plane_off"] = off
-            placed.append((off, arr))
-            off += -(-arr.size // 16) * 16
+            job["plane_off"] = arena.add(arr)
         if plan["mode"] == "alpha":
             job["k"] = plan["k"]
             if 1 <= plan["k"] <= MAX_DILATE:      # a larger element is the entry's to refuse
                 spans = ellipse_spans(plan["k"])
                 job["lo"][:plan["k"]], job["hi"][:plan["k"]] = spans[:, 0], spans[:, 1]
-    n = max(16, off)
-    arena = torch.empty(n, dtype=torch.uint8, pin_memory=bool(pin))
-    table = torch.empty(jobs.nbytes, dtype=torch.uint8, pin_memory=bool(pin))
-    view = arena.numpy()
-    view[:] = 0
-    for o, arr in placed:
-        view[o:o + arr.size] = np.ascontiguousarray(arr).reshape(-1)
-    table.numpy()[:] = jobs.view(np.uint8).reshape(-1)
-    return dict(arena=arena, jobs=table, img_size=size, batch=len(items), txt=default_collate([plan["txt"] for plan, _ in items]),
+    return dict(arena=arena.tensor(pin), jobs=rawbatch.table_tensor(jobs, pin), img_size=size, batch=len(items),
+                txt=default_collate([plan["txt"] for plan, _ in items]),
                 rel_pose=torch.tensor([plan["rel_pose"] for plan, _ in items], dtype=torch.float32).reshape(len(items), 4))
 
 
@@ -234,37 +220,22 @@ def job_table(batch):
     return batch["jobs"].numpy().view(JOB_DTYPE)
 
 
-class NVSDevicePrep:
-    """collate_nvs_raw's batch -> `dict(image, masked_image, mask, rel_pose, txt)` on the device: one copy of the arena, one of the job
-    table, one lr_nvs_prep launch.  Buffers are kept and grow only when a batch needs more; the returned tensors are views of them
-    and the next call overwrites them."""
+class NVSDevicePrep(rawbatch.DevicePrepBase):
+    """collate_nvs_raw's batch -> `dict(image, masked_image, mask, rel_pose, txt)` on the device by one lr_nvs_prep launch (buffers and
+    views: `rawbatch.DevicePrepBase`); the canvas is the two tiles [cond | target], and `rel_pose` has a grow-only buffer of its own."""
+    entry = "lr_nvs_prep"
 
     def __init__(self, img_size, device="cuda"):
-        self.img_size, self.device = int(img_size), torch.device(device)
-        self.arena = self.jobs = self.image = self.masked_image = self.mask = self.rel_pose = None
+        super().__init__(img_size, 2, device)
+        self.rel_pose = None
 
-    @staticmethod
-    def _grown(buf, n, device):
-        return buf if buf is not None and buf.numel() >= n else torch.empty(n, dtype=torch.uint8, device=device)
+    def allocate(self, N):
+        super().allocate(N)
+        self.rel_pose = torch.empty(N, 4, device=self.device)
 
-    def __call__(self, batch):
-        S, B = self.img_size, batch["batch"]
-        assert batch["img_size"] == S, "the batch was planned for another canvas"
-        lib = _lib.load()
-        n_bytes = batch["arena"].numel()
-        self.arena = self._grown(self.arena, n_bytes, self.device)
-        self.jobs = self._grown(self.jobs, batch["jobs"].numel(), self.device)
-        if self.image is None or self.image.shape[0] < B:
-            self.image = torch.empty(B, S, 2 * S, 3, device=self.device)
-            self.masked_image = torch.empty(B, S, 2 * S, 3, device=self.device)
-            self.mask = torch.empty(B, S, 2 * S, 1, device=self.device)
-            self.rel_pose = torch.empty(B, 4, device=self.device)
-        self.arena[:n_bytes].copy_(batch["arena"], non_blocking=True)
-        self.jobs[:batch["jobs"].numel()].copy_(batch["jobs"], non_blocking=True)
-        self.rel_pose[:B].copy_(batch["rel_pose"], non_blocking=True)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            _lib.check(lib.lr_nvs_prep(self.arena.data_ptr(), n_bytes, self.jobs.data_ptr(), batch["jobs"].data_ptr(), B, S,
-                                       self.image.data_ptr(), self.masked_image.data_ptr(), self.mask.data_ptr(), stream), "nvs_prep")
-        return dict(image=self.image[:B], masked_image=self.masked_image[:B], mask=self.mask[:B], rel_pose=self.rel_pose[:B],
-                    txt=batch["txt"])
+    def dims(self, N):
+        return N, self.img_size
+
+    def finish(self, batch, out):
+        out["rel_pose"] = self.rel_pose[:batch["batch"]].copy_(batch["rel_pose"], non_blocking=True)
+        return out

@@ -3,6 +3,7 @@ REFERENCE's dataset returned (tests/golden/nvs_dataset.npz, see test_nvsdata_cpu
 (nvsprep.run_nvs_plan_numpy) at the smallest shapes where the kernel can go wrong, bit for bit -- the arithmetic is integer up to the
 final float mapping, so there is no tolerance anywhere; the entry's refusals; and the training CLI end to end with and without
 --device_prep."""
+import functools
 import json
 import os
 import sys
@@ -15,13 +16,13 @@ import leftrefill_amd.dropin as dropin
 
 dropin.install()
 from leftrefill_amd import _lib, nvsprep  # noqa: E402
+from rawdata_helpers import KEYS, device_batch, same_bits as _same_bits  # noqa: E402
 from test_nvsdata_cpu import Fixture  # noqa: E402
 from tools import make_golden_nvs_dataset as G  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 S = G.S
-KEYS = ("image", "masked_image", "mask")
 KS = (1, 2, 8, 25, 32)
 
 
@@ -30,17 +31,7 @@ def fixture(tmp_path_factory):
     return Fixture(tmp_path_factory.mktemp("nvs_tree"))
 
 
-def _device(prep, items):
-    out = prep(nvsprep.collate_nvs_raw(items))
-    torch.cuda.synchronize()
-    return {k: (v.cpu().clone() if torch.is_tensor(v) else v) for k, v in out.items()}
-
-
-def _same_bits(got, want, what):
-    for k in KEYS:
-        g = got[k].numpy()
-        assert g.dtype == np.float32 and g.shape == want[k].shape, (what, k, g.shape, want[k].shape)
-        assert g.tobytes() == want[k].tobytes(), (what, k, int((g != want[k]).sum()), "values differ")
+_device = functools.partial(device_batch, nvsprep.collate_nvs_raw)
 
 
 @pytest.mark.parametrize("name", sorted(G.SETTINGS))
@@ -138,6 +129,28 @@ def test_ones_strokes_file_planes_and_the_white_right_half():
     out = _device(nvsprep.NVSDevicePrep(size), [items[4]])
     kept = out["masked_image"][0].numpy()[:, size:][grey == 127]
     assert (out["masked_image"][0].numpy()[:, size:][grey == 128] == 0).all() and (kept != 0).all()
+
+
+def test_a_smaller_batch_reuses_every_buffer():
+    """NVSDevicePrep's side of test_gpu_dataprep.py's buffer test: three samples, one per resize path (32 x 32: the box, 16 x 16: the
+    copy, 23 x 19: the bilinear), mode alpha with k = 3 and a stroke plane on one of them; then one sample through the same object."""
+    size = 16
+    rng = np.random.RandomState(17)
+    strokes = (rng.rand(size, size) < 0.1).astype(np.uint8)
+    items = [(_plan(size, k=3), [_render(rng, 32, 32, "noise"), _render(rng, 32, 32, "blob")]),
+             (_plan(size, k=3, plane=2), [_render(rng, 16, 16, "noise"), _render(rng, 16, 16, "corners"), strokes]),
+             (_plan(size, k=3), [_render(rng, 23, 19, "noise"), _render(rng, 23, 19, "blob")])]
+    prep = nvsprep.NVSDevicePrep(size)
+    buffers = lambda: [getattr(prep, n).data_ptr() for n in ("arena", "jobs", "image", "masked_image", "mask", "rel_pose")]  # noqa: E731
+    out = _device(prep, items)
+    assert out["image"].shape == (3, size, 2 * size, 3) and out["rel_pose"].shape == (3, 4)
+    for b, item in enumerate(items):
+        _same_bits({k: out[k][b] for k in KEYS}, nvsprep.run_nvs_plan_numpy(*item), f"first call [{b}]")
+    ptrs = buffers()
+    out = _device(prep, items[2:])      # a smaller batch: nothing is reallocated
+    assert ptrs == buffers()
+    assert out["image"].shape[0] == out["rel_pose"].shape[0] == 1
+    _same_bits({k: out[k][0] for k in KEYS}, nvsprep.run_nvs_plan_numpy(*items[2]), "second call")
 
 
 def _raw_call(batch, size, mutate):

@@ -3,6 +3,7 @@ items the REFERENCE's datasets returned (tests/golden/pair_datasets.npz, see tes
 area average within 1e-6 of a rounding tie (asserted on the CPU), so there is no tie allowance here -- and the two CLIs end to end with
 and without --device_prep.  These are the first cases to drive the kernel with windows and flips on both tiles at once, a mask on the
 left tile, a 256 x 256 mask source shrunk to S = 32, outpaint_col = 0 and B·V samples in one launch."""
+import functools
 import json
 import os
 import subprocess
@@ -16,13 +17,13 @@ import leftrefill_amd.dropin as dropin
 
 dropin.install()
 from leftrefill_amd import dataprep  # noqa: E402
+from rawdata_helpers import KEYS, device_batch, same_bits as _same_bits  # noqa: E402
 from test_pairdata_cpu import Fixture  # noqa: E402
 from tools import make_golden_pair_datasets as G  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 S = G.S
-KEYS = ("image", "masked_image", "mask")
 
 
 @pytest.fixture(scope="module")
@@ -30,17 +31,7 @@ def fixture(tmp_path_factory):
     return Fixture(tmp_path_factory.mktemp("pair_tree"))
 
 
-def _device(prep, items):
-    out = prep(dataprep.collate_raw(items))
-    torch.cuda.synchronize()
-    return {k: (v.cpu().clone() if torch.is_tensor(v) else v) for k, v in out.items()}
-
-
-def _same_bits(got, want, what):
-    for k in KEYS:
-        g = got[k].numpy()
-        assert g.dtype == np.float32 and g.shape == want[k].shape, (what, k, g.shape, want[k].shape)
-        assert g.tobytes() == want[k].tobytes(), (what, k, int((g != want[k]).sum()), "values differ")
+_device = functools.partial(device_batch, dataprep.collate_raw)
 
 
 @pytest.mark.parametrize("name", sorted(G.SETTINGS))

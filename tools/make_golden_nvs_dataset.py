@@ -21,10 +21,8 @@ float32, mask == float32(mask_levels / 255.), masked_image == (image, or [cond |
 (`unpack_items` restores them with those expressions).
 """
 import argparse
-import importlib.util
 import json
 import os
-import random
 import sys
 import tempfile
 import types
@@ -33,6 +31,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools.golden_common import branch_tally, import_reference, resolve, run_sequence  # noqa: E402, F401  (the tests reach them as G.*)
 OUT = os.path.join(ROOT, "tests", "golden", "nvs_dataset.npz")
 S, NVIEWS = 32, 4
 TOKEN_MAP = dict(left_token="<left>", right_token="<right>", task_token="<views>", real_token="<scene>")
@@ -96,20 +95,6 @@ def write_tree(root, fx):
     for rel, names in layout["lists"].items():
         with open(os.path.join(root, rel), "w") as f:
             f.write("".join(n + "\n" for n in names))
-
-
-def resolve(kwargs, root):
-    """Constructor keywords with "@name" entries turned into paths under root."""
-    return {k: os.path.join(root, v[1:]) if isinstance(v, str) and v.startswith("@") else v for k, v in kwargs.items()}
-
-
-def run_sequence(cls, kwargs, seed, indices, root, **extra):
-    """Seed both generators, build `cls(**kwargs)`, take the items in order; (items, next random.random(), next np.random.random())."""
-    ds = cls(**resolve(kwargs, root), **extra)
-    random.seed(seed)
-    np.random.seed(seed)
-    items = [ds[i] for i in indices]
-    return items, random.random(), np.random.random()
 
 
 def ref_white(kwargs):
@@ -193,15 +178,6 @@ def cv2_standin():
     return cv2
 
 
-def import_reference(ref_dir):
-    path = os.path.join(ref_dir, "dataloaders", "obj_nvs_dataset.py")
-    sys.modules["cv2"] = cv2_standin()
-    spec = importlib.util.spec_from_file_location("reference_obj_nvs_dataset", path)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod, path
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", default=os.environ.get("LEFTREFILL_REFERENCE"), help="checkout of the reference project")
@@ -209,30 +185,18 @@ def main():
     a = ap.parse_args()
     if not a.reference:
         raise SystemExit("give --reference DIR (or LEFTREFILL_REFERENCE)")
-    ref, ref_file = import_reference(a.reference)
+    ref, ref_file = import_reference(a.reference, "obj_nvs_dataset", cv2_standin())
     fx = make_inputs()
-    tally = {name: 0 for name in BRANCH_LINES.values()}
-
-    def tracer(frame, event, arg):
-        if frame.f_code.co_filename != ref_file:
-            return None
-        if event == "line" and frame.f_lineno in BRANCH_LINES:
-            tally[BRANCH_LINES[frame.f_lineno]] += 1
-        return tracer
-
     out = dict(fx)
     with tempfile.TemporaryDirectory() as root:
         write_tree(root, fx)
-        sys.settrace(tracer)
-        try:
+        with branch_tally(ref_file, BRANCH_LINES) as tally:
             for name, (kwargs, seed, indices) in SETTINGS.items():
                 items, nxt, np_nxt = run_sequence(ref.NVS_OBJDataset, kwargs, seed, indices, root)
                 assert all(it["image"].shape == (S, 2 * S, 3) and it["mask"].shape == (S, 2 * S, 1) for it in items)
                 out[f"{name}/levels"], out[f"{name}/mask_levels"], out[f"{name}/rel_pose"], out[f"{name}/txt"] = \
                     pack_items(items, ref_white(kwargs))
                 out[f"{name}/next"] = np.array([nxt, np_nxt])
-        finally:
-            sys.settrace(None)
     missed = [name for name, n in tally.items() if n == 0]
     assert not missed, f"branches the sequences never took: {missed}"
     out["spec"] = np.array(json.dumps(dict(settings=SETTINGS, branch_tally=tally)))

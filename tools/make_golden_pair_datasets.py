@@ -20,11 +20,9 @@ An item is stored as uint8 levels and packed mask bits; the tool asserts that th
 float32, mask in {0, 1}, masked_image == image * (mask < 0.5) (`unpack_items` restores them with those expressions).
 """
 import argparse
-import importlib.util
 import json
 import os
 import pickle
-import random
 import sys
 import tempfile
 import types
@@ -33,6 +31,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools.golden_common import branch_tally, import_reference, resolve, run_sequence  # noqa: E402, F401  (the tests reach them as G.*)
 OUT = os.path.join(ROOT, "tests", "golden", "pair_datasets.npz")
 S = 32
 TOKEN_MAP = dict(left_token="<left>", right_token="<right>", task_token="<views>", real_token="<scene>")
@@ -186,21 +185,6 @@ def write_tree(root, fx):
         pickle.dump([dict(source=s, target=t) for s, t in layout["pairs"]], f)
 
 
-def resolve(kwargs, root):
-    """Constructor keywords with "@name" entries turned into paths under root."""
-    at = lambda v: os.path.join(root, v[1:]) if isinstance(v, str) and v.startswith("@") else v
-    return {k: [at(x) for x in v] if isinstance(v, list) else at(v) for k, v in kwargs.items()}
-
-
-def run_sequence(cls, kwargs, seed, indices, root):
-    """Seed both generators, build `cls(**kwargs)`, take the items in order; (items, next random.random(), next np.random.random())."""
-    ds = cls(**resolve(kwargs, root))
-    random.seed(seed)
-    np.random.seed(seed)
-    items = [ds[i] for i in indices]
-    return items, random.random(), np.random.random()
-
-
 # ---- items <-> arrays ---------------------------------------------------------------------------------------------------------------
 def pack_items(items):
     """uint8 levels, packed mask bits and JSON prompts of finished items, after asserting that this loses nothing."""
@@ -251,15 +235,6 @@ def cv2_standin():
     return cv2
 
 
-def import_reference(ref_dir):
-    path = os.path.join(ref_dir, "dataloaders", "inpainting_crossview_dataset.py")
-    sys.modules["cv2"] = cv2_standin()
-    spec = importlib.util.spec_from_file_location("reference_inpainting_crossview_dataset", path)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod, path
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", default=os.environ.get("LEFTREFILL_REFERENCE"), help="checkout of the reference project")
@@ -267,29 +242,17 @@ def main():
     a = ap.parse_args()
     if not a.reference:
         raise SystemExit("give --reference DIR (or LEFTREFILL_REFERENCE)")
-    ref, ref_file = import_reference(a.reference)
+    ref, ref_file = import_reference(a.reference, "inpainting_crossview_dataset", cv2_standin())
     fx = make_inputs()
-    tally = {name: 0 for name in BRANCH_LINES.values()}
-
-    def tracer(frame, event, arg):
-        if frame.f_code.co_filename != ref_file:
-            return None
-        if event == "line" and frame.f_lineno in BRANCH_LINES:
-            tally[BRANCH_LINES[frame.f_lineno]] += 1
-        return tracer
-
     out = dict(fx)
     with tempfile.TemporaryDirectory() as root:
         write_tree(root, fx)
-        sys.settrace(tracer)
-        try:
+        with branch_tally(ref_file, BRANCH_LINES) as tally:
             for name, (kwargs, seed, indices) in SETTINGS.items():
                 items, nxt, np_nxt = run_sequence(ref.InpaintingCrossViewDataset, kwargs, seed, indices, root)
                 assert all(it["image"].shape == (S, 2 * S, 3) and it["image"].dtype == np.float32 for it in items)
                 out[f"{name}/levels"], out[f"{name}/mask_bits"], out[f"{name}/txt"] = pack_items(items)
                 out[f"{name}/next"] = np.array([nxt, np_nxt])
-        finally:
-            sys.settrace(None)
         for name, (kwargs, seed, indices) in MV_SETTINGS.items():
             items, nxt, np_nxt = run_sequence(ref.InpaintingMultiViewDataset, kwargs, seed, indices, root)
             out[f"{name}/levels"], out[f"{name}/mask_bits"], out[f"{name}/txt"] = pack_items(items)

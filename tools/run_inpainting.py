@@ -84,29 +84,23 @@ def synthetic_mv_batches(n, batch_size, size, views, concat, view_token_len, sp_
 
 
 def dataset_batches(path, batch_size, size, model, device_prep=False):
-    """The reference's loader + DataLoader (test_inpainting.py:118-120).  device_prep: the loader hands over raw decoded images and the
-    [source | target] canvases of a batch are assembled by one HIP kernel launch (leftrefill_amd/dataprep.py)."""
-    from torch.utils.data import DataLoader
-    from dataloaders.test_dataset import TestInpaintingDataset
+    """The reference's loader + DataLoader (test_inpainting.py:118-120), through the subclass that adds the `raw` keyword (its default
+    items are that loader's).  device_prep: items are (plan, raw) and the [source | target] canvases of a batch are assembled by one
+    HIP kernel launch (leftrefill_amd/dataprep.py)."""
+    from dataloaders.raw_pairs import TestInpaintingDataset
+    from leftrefill_amd import rawbatch
     cond_cfg = getattr(model, "cond_cfg", None) or {}
     data_cfg = dict(getattr(model, "data_cfg", None) or {})
     data_cfg.pop("img_size", None)
-    if device_prep:      # the same loader with the `raw` keyword: items are (plan, raw)
-        from dataloaders.raw_pairs import TestInpaintingDataset as RawDataset
-        from leftrefill_amd import dataprep
-        ds = RawDataset(path, img_size=size, deep_prompt=cond_cfg.get("deep_prompt", False), raw=True, **data_cfg)
-        loader = DataLoader(ds, batch_size=batch_size, shuffle=False, collate_fn=dataprep.collate_raw)
-        return dataprep.DevicePrepLoader(loader, dataprep.DevicePrep(size, 2, "cuda"))
-    ds = TestInpaintingDataset(path, img_size=size, deep_prompt=cond_cfg.get("deep_prompt", False), **data_cfg)
-    return DataLoader(ds, batch_size=batch_size, shuffle=False)
+    ds = TestInpaintingDataset(path, img_size=size, deep_prompt=cond_cfg.get("deep_prompt", False), raw=device_prep, **data_cfg)
+    return rawbatch.loader(ds, device_prep, "cuda", batch_size=batch_size, shuffle=False)
 
 
 def multiview_batches(path, batch_size, size, model, device_prep=False):
     """The reference's multi-view loader + DataLoader (test_multiview_inpainting.py:111-114); device_prep as in `dataset_batches`, with
     one tile per view, or two under concat_target."""
-    from torch.utils.data import DataLoader
+    from leftrefill_amd import rawbatch
     from leftrefill_amd.dropin.dataloaders.inpainting_crossview_dataset import InpaintingMultiViewDataset
-    from leftrefill_amd import dataprep
     data_cfg = dict(getattr(model, "data_cfg", None) or {}, test_limit=482)
     data_cfg.pop("img_size", None)
     ds = InpaintingMultiViewDataset(path, img_size=size, pair_path=None, mask_path=path, mode="val", raw=device_prep,
@@ -116,10 +110,7 @@ def multiview_batches(path, batch_size, size, model, device_prep=False):
         raise SystemExit(f"--multiview --test_path {path}: {len(bad)} of {len(ds)} entries are no multi-view folders (named by a number, "
                          f"holding target / source / source_1.. images and mask.png), e.g. {bad[:1]}; without a dataset, --synthetic N "
                          "builds batches of the same contract")
-    if not device_prep:
-        return DataLoader(ds, batch_size=batch_size, shuffle=False)
-    loader = DataLoader(ds, batch_size=batch_size, shuffle=False, collate_fn=dataprep.collate_raw)
-    return dataprep.DevicePrepLoader(loader, dataprep.DevicePrep(size, 2 if ds.concat_target else 1, "cuda"))
+    return rawbatch.loader(ds, device_prep, "cuda", batch_size=batch_size, shuffle=False)
 
 
 def main():

@@ -37,12 +37,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def device_route(loader, device_prep, size, tiles, device):
-    """With device_prep, the loader's raw batches finished by a DevicePrep of its own; else the loader."""
-    from leftrefill_amd import dataprep
-    return dataprep.DevicePrepLoader(loader, dataprep.DevicePrep(size, tiles, device)) if device_prep else loader
-
-
 def record_draws(sampler):
     """Every epoch's indices as the sampler hands them out from now on, one list per epoch, appended to the returned list."""
     epochs, draw = [], type(sampler).__iter__
@@ -56,68 +50,35 @@ def record_draws(sampler):
     return epochs
 
 
-def crossview_loaders(config, model, device_prep, val, workers, device):
-    """(training batches, validation batches or None) of the image-pair dataset: the model's own train_dataloader / val_dataloader
-    (reference ref_inpainting_ldm.py:99-117), whose sampler takes rank and replica count from the model; two tiles per canvas."""
-    size = int(model.img_size)
-    model.cfg = dict(config, cross_view_inpainting=True)
-    loaders = [device_route(model.train_dataloader(raw=device_prep, num_workers=workers), device_prep, size, 2, device), None]
+def model_loaders(config, model, device_prep, val, workers, device, items):
+    """(training batches, validation batches or None) from the model's own train_dataloader / val_dataloader (reference
+    ref_inpainting_ldm.py:99-117, NVS_ldm.py:348-372); with device_prep they collate raw decoded images and the dataset's own device
+    prep finishes the batches on `device` (leftrefill_amd/rawbatch.py).  items: what a validation item is called in a message."""
+    loaders = [model.train_dataloader(raw=device_prep, num_workers=workers, device=device), None]
     if val:
         val_bs = int(config.get("val_batch_size", 4))
-        held = model.val_dataloader(raw=device_prep, num_workers=min(4, workers), batch_size=val_bs)
-        if len(held) == 0:      # drop_last (as the reference has it) would leave no batch and validation nothing to average
-            raise SystemExit(f"--val: {len(held.dataset)} validation pairs are fewer than val_batch_size = {val_bs}")
-        loaders[1] = device_route(held, device_prep, size, 2, device)
-    return loaders
-
-
-def objaverse_loaders(config, model, device_prep, val, workers, device):
-    """(training batches, validation batches or None) of the Objaverse NVS dataset: NVSLDM's own train_dataloader / val_dataloader
-    (reference NVS_ldm.py:348-372) over the config's `datapath`, `train_list`, `val_list` and `batch_size`; with device_prep the loaders
-    collate raw RGBA renders and an NVSDevicePrep per loader finishes the batches (leftrefill_amd/nvsprep.py, csrc/nvs_prep.hip)."""
-    from leftrefill_amd import dataprep, nvsprep
-    if not hasattr(model, "_objaverse"):
-        raise SystemExit("--dataset objaverse needs a model config whose target is inpainting_ldm.NVS_ldm.NVSLDM")
-    size = int(model.img_size)
-
-    def wrap(loader):
-        return dataprep.DevicePrepLoader(loader, nvsprep.NVSDevicePrep(size, device)) if device_prep else loader
-
-    loaders = [wrap(model.train_dataloader(raw=device_prep, num_workers=workers)), None]
-    if val:
-        val_bs = int(config.get("val_batch_size", 4))
-        held = model.val_dataloader(raw=device_prep, num_workers=min(4, workers), batch_size=val_bs)
-        if len(held) == 0:      # drop_last (as the reference has it) would leave no batch and validation nothing to average
-            raise SystemExit(f"--val: {len(held.dataset)} validation objects are fewer than val_batch_size = {val_bs}")
-        loaders[1] = wrap(held)
+        loaders[1] = model.val_dataloader(raw=device_prep, num_workers=min(4, workers), batch_size=val_bs, device=device)
+        if len(loaders[1]) == 0:      # drop_last (as the reference has it) would leave no batch and validation nothing to average
+            raise SystemExit(f"--val: {len(loaders[1].dataset)} validation {items} are fewer than val_batch_size = {val_bs}")
     return loaders
 
 
 def inpainting_loaders(config, model, batch_size, device_prep, val, workers, device):
     """(training batches, validation batches or None) of the single-image dataset, as the reference's train_dataloader builds it
     (ref_inpainting_ldm.py:109-111); with device_prep the loaders collate raw bytes and a DevicePrep per loader finishes the batches."""
-    from torch.utils.data import DataLoader
     from dataloaders.inpainting_dataset import InpaintingDataset
-    from leftrefill_amd import dataprep
-    size = int(model.img_size)
+    from leftrefill_amd import rawbatch
     data_cfg = dict(model.data_cfg)      # the reference's model configs carry `test_limit` here (ref_inpainting_ldm.py:109-117 pass it on)
     test_limit = int(data_cfg.pop("test_limit", config.get("test_limit", 200)))
-    common = dict(img_size=size, raw=device_prep, **data_cfg)
-    kw = dict(num_workers=workers, collate_fn=dataprep.collate_raw, pin_memory=True) if device_prep else dict(num_workers=workers)
-
-    def wrap(loader):
-        return device_route(loader, device_prep, size, 1, device)
-
-    train = InpaintingDataset(image_list=config["image_path"], mask_path=list(config["train_mask_path"]), mode="train", test_limit=test_limit,
-                              **common)
-    loaders = [wrap(DataLoader(train, batch_size=batch_size, shuffle=True, drop_last=True, **kw)), None]
+    common = dict(img_size=int(model.img_size), raw=device_prep, test_limit=test_limit, **data_cfg)
+    train = InpaintingDataset(image_list=config["image_path"], mask_path=list(config["train_mask_path"]), mode="train", **common)
+    loaders = [rawbatch.loader(train, device_prep, device, batch_size=batch_size, shuffle=True, drop_last=True, num_workers=workers), None]
     if val:
-        held = InpaintingDataset(image_list=config["val_image_path"], mask_path=config["val_mask_path"], mode="val", test_limit=test_limit,
-                                 **common)
+        held = InpaintingDataset(image_list=config["val_image_path"], mask_path=config["val_mask_path"], mode="val", **common)
         val_bs = int(config.get("val_batch_size", 4))
         if len(held) < val_bs:      # drop_last (as the reference has it) would leave no batch and validation nothing to average
             raise SystemExit(f"--val: {len(held)} validation images are fewer than val_batch_size = {val_bs}")
-        loaders[1] = wrap(DataLoader(held, batch_size=val_bs, shuffle=False, drop_last=True, **kw))
+        loaders[1] = rawbatch.loader(held, device_prep, device, batch_size=val_bs, shuffle=False, drop_last=True, num_workers=workers)
     return loaders
 
 
@@ -180,10 +141,13 @@ def main():
     model.trainer = trainer      # the model's loaders read their rank here
     val_data = None
     workers = min(8, max(0, a.num_workers))
-    if a.dataset == "crossview":
-        data, val_data = crossview_loaders(config, model, a.device_prep, a.val, workers, f"cuda:{rank}")
-    elif a.dataset == "objaverse":
-        data, val_data = objaverse_loaders(config, model, a.device_prep, a.val, workers, f"cuda:{rank}")
+    if a.dataset == "crossview":      # the sampler takes rank and replica count from the model
+        model.cfg = dict(config, cross_view_inpainting=True)
+        data, val_data = model_loaders(config, model, a.device_prep, a.val, workers, f"cuda:{rank}", "pairs")
+    elif a.dataset == "objaverse":      # over the config's `datapath`, `train_list`, `val_list` and `batch_size`
+        if not hasattr(model, "_objaverse"):
+            raise SystemExit("--dataset objaverse needs a model config whose target is inpainting_ldm.NVS_ldm.NVSLDM")
+        data, val_data = model_loaders(config, model, a.device_prep, a.val, workers, f"cuda:{rank}", "objects")
     elif a.dataset == "inpainting":
         data, val_data = inpainting_loaders(config, model, bs, a.device_prep, a.val, workers, f"cuda:{rank}")
     elif a.dataset:
