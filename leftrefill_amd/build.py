@@ -18,6 +18,9 @@ SOURCES = ["norm.hip", "elementwise.hip", "gemm_conv.hip", "conv_halo.hip", "att
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 # attention: keep MFMA accumulators in VGPRs -- the softmax VALU stream reads every S^T value and rescales O, and
 # AGPR accumulators cost ~150 v_accvgpr_read/write per 64-key tile.
+# xattn_block640.hip is deliberately NOT listed: its kernels need up to 512 registers per lane and keep about half of them as AGPRs
+# (PRE: 256 VGPRs + 256 AGPRs); the VGPR form would confine the MFMA operands to the 256 VGPRs.  That is also why it stays a
+# translation unit of its own next to xattn_block.hip (shared code: csrc/chain_common.h).
 EXTRA = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "xattn_block.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "ffn_block.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "stin_block.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "rowlin.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "attention_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 

@@ -52,6 +52,15 @@ static inline int lr_launch_status() {
   return e == hipSuccess ? 0 : (int)e;
 }
 
+// Launch of a kernel with dynamic LDS above the default limit: the per-device attribute (slot `attr_done`, one per kernel instance),
+// the launch, its status.
+template <typename P>
+static inline int lr_launch_dyn(void (*kernel)(P), unsigned long long* attr_done, dim3 grid, dim3 block, size_t smem, hipStream_t st, const P& p) {
+  if (lr_attr_needed(attr_done)) hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  hipLaunchKernelGGL(kernel, grid, block, smem, st, p);
+  return lr_launch_status();
+}
+
 __device__ __forceinline__ float lr_silu(float x) { return x / (1.0f + __expf(-x)); }
 
 // erf-form GELU, as F.gelu default (attention.py:58).  erf by Abramowitz-Stegun 7.1.26 (|abs err| <= 1.5e-7, far below

@@ -33,6 +33,34 @@
 #define FF_DEPTH 2            // MFMA groups a fragment read runs ahead of its use (3 measured the same)
 #define FF_MAX_H 2048          // hidden units whose bias rows fit the LDS region behind the ring
 
+// The 10-step "output tile group" loop of a ring piece: the fragments of group g + DEPTH are read while group g multiplies (DEPTH + 1
+// register sets), and `sched_barrier(0)` pins   [ds_reads of a later group] | [MFMAs of this group (independent accumulators), hook] |
+// -- left to itself hipcc orders each product as one dependent accumulator chain with every fragment read one MFMA before its use
+// (~100 cycles per MFMA instead of ~17).  mfma(g, f): the group's MFMAs on its fragments f[]; hook(g): one LDS-DMA issue (or nothing).
+// (step C and POST below; the cross-attention kernels have their own inline copies of this loop shape.)
+// ff_tile_groups: a [(5 NF) x 16 rows x 64 k] piece at Os (output tiles tile0 .. of a [n][64 k] weight piece) -- group g = k half g / 5,
+// f[q] = output tile tile0 + NF (g % 5) + q.
+template <typename T, int NF, int DEPTH, typename MFMA, typename HOOK>
+__device__ __forceinline__ void ff_tile_groups(const XaFrag<T>& frag, const char* Os, int tile0, int fr, int fq, MFMA&& mfma, HOOK&& hook) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  vec8<T> fa[DEPTH + 1][NF];
+  auto rd = [&](int g, vec8<T> (&f)[NF]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int q = 0; q < NF; ++q) f[q] = frag(Os, (tile0 + NF * (g % 5) + q) * 16 + fr, 4 * (g / 5) + fq);
+  };
+#pragma unroll
+  for (int d = 0; d < DEPTH; ++d) rd(d, fa[d]);
+#pragma unroll
+  for (int g = 0; g < 10; ++g) {
+    if (g + DEPTH < 10) rd(g + DEPTH, fa[(g + DEPTH) % (DEPTH + 1)]);
+    __builtin_amdgcn_sched_barrier(0);
+    mfma(g, fa[g % (DEPTH + 1)]);
+    hook(g);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#endif
+}
+
 struct FfnParams {
   const void* x; const void* w1; const float* b1; const void* w2; const float* b2; void* out; float* st_out;
   const void* post_w; const float* post_b; const void* post_resid; float* gs_out;      // POST (see the kernel)
@@ -69,38 +97,22 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_block_kernel(const FfnParams P
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int pr = w >> 1, role = w & 1;   // wave pair (32 rows) and which half of the work this wave does for it
   const int fr = lane & 15, fq = lane >> 4;
-  int bid = blockIdx.x;
-  {
-    const int q = P.nblocks >> 3, r = P.nblocks & 7, xcd = bid & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int bid = xa_xcd_remap(blockIdx.x, P.nblocks);
   const int m_p0 = bid * FF_ROWS + pr * 32;      // first row of the pair
   const int H2 = 2 * P.H;
   char* xch = smem + 3 * FF_SLOT + FF_PAR_BYTES + pr * 4096;      // the pair's hand-off area [chunk 2][row tile 2][lane 64][16 B]
   FF_STAMP(0);
 
-  // ---- the pair's 32 rows in B-operand form (both waves hold them): lane (fr, fq), row tile rt holds
-  //      x[m_p0 + 16 rt + fr][64 t5 + 32 u + 8 fq .. + 7]  (weight fragment of lane group fq = chunk 4 u + fq: conflict-free reads,
-  //      see xattn_block.hip)
+  // ---- the pair's 32 rows in B-operand form (both waves hold them; xa_load_rows)
   vec8<T> xf[2][KL][2];
 #pragma unroll
-  for (int rt = 0; rt < 2; ++rt) {
-    const T* xrow = reinterpret_cast<const T*>(P.x) + (size_t)(m_p0 + 16 * rt + fr) * C + 8 * fq;
-#pragma unroll
-    for (int t5 = 0; t5 < KL; ++t5)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) xf[rt][t5][u] = *reinterpret_cast<const vec8<T>*>(xrow + 64 * t5 + 32 * u);
-  }
-  for (int i = t; i < (H2 + (POST ? 2 : 1) * C) / 4; i += FF_THREADS) {      // biases -> LDS (no register loads inside the loop below)
-    const float* src = i < H2 / 4 ? P.b1 + 4 * i : i < (H2 + C) / 4 ? P.b2 + 4 * (i - H2 / 4) : P.post_b + 4 * (i - (H2 + C) / 4);
-    *reinterpret_cast<f32x4*>(par + 4 * i) = *reinterpret_cast<const f32x4*>(src);
-  }
+  for (int rt = 0; rt < 2; ++rt) xa_load_rows<T, KL>(xf[rt], reinterpret_cast<const T*>(P.x) + (size_t)(m_p0 + 16 * rt + fr) * C + 8 * fq);
+  xa_stage_bias<FF_THREADS>(par, {{P.b1, H2}, {P.b2, C}, {P.post_b, POST ? C : 0}}, t);      // (no register loads inside the loop below)
 
   // ---- weight ring
   const __amdgpu_buffer_rsrc_t rs1 = uniform_rsrc(P.w1, (size_t)H2 * C * 2);
   const __amdgpu_buffer_rsrc_t rs2 = uniform_rsrc(P.w2, (size_t)C * P.H * 2);
-  const int lrow = w * 8 + (lane >> 3);
-  const int lchunk = (lane & 7) ^ ((lrow >> 1) & 7);
+  const int lrow = xa_ring_row(w, lane), lchunk = xa_ring_chunk(lane, lrow);      // (chain_common.h)
   auto issue_w1 = [&](int slot, int c, int i) __attribute__((always_inline)) {   // rows 64 c .. + 63 of W1 as 5 sub-tiles [64 x 64 k]
     const unsigned v0 = (unsigned)(((c * 64 + lrow) * C + lchunk * 8) * 2);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, (lptr_t)(smem + slot * FF_SLOT + (i * 64 + w * 8) * 128), 16, v0, i * 128, 0, 0);
@@ -118,29 +130,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_block_kernel(const FfnParams P
 #pragma unroll
   for (int rt = 0; rt < 2; ++rt) {
     __builtin_amdgcn_sched_barrier(0);      // one row tile at a time (register pressure)
-    float s = 0.f;
-#pragma unroll
-    for (int t5 = 0; t5 < KL; ++t5)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s += (float)xf[rt][t5][u][i];
-    const float mean = xa_row4_sum(s) * (1.0f / C);
-    float q2 = 0.f;
-#pragma unroll
-    for (int t5 = 0; t5 < KL; ++t5)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { const float d = (float)xf[rt][t5][u][i] - mean; q2 = fmaf(d, d, q2); }
-    const float rstd = rsqrtf(xa_row4_sum(q2) * (1.0f / C) + P.eps);
-    const float nmr = -mean * rstd;
-#pragma unroll
-    for (int t5 = 0; t5 < KL; ++t5)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) xf[rt][t5][u][i] = (T)fmaf((float)xf[rt][t5][u][i], rstd, nmr);
+    xa_layernorm_rows<T, KL, true>(xf[rt], P.eps);      // (TOUCH: without it this kernel spills 27 .. 39 registers)
   }
 
   FF_STAMP(1);
@@ -148,10 +138,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_block_kernel(const FfnParams P
 #pragma unroll
   for (int j = 0; j < NTW; ++j) { acc[j][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[j][1] = acc[j][0]; }
   const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-  const int sw = (fr >> 1) & 7;
-  auto frag = [&](const char* base, int row, int chunk) -> vec8<T> {
-    return *reinterpret_cast<const vec8<T>*>(base + row * 128 + ((chunk ^ sw) << 4));
-  };
+  const XaFrag<T> frag(fr);
 #define FF_FENCE() __builtin_amdgcn_sched_barrier(0)
   // This wave's half of chunk c (32 hidden units): tiles (u, g) of units 16 role .. 16 role + 15 for both row tiles -- every W1
   // fragment read from LDS feeds TWO MFMAs.  The gated result goes to the pair's hand-off area as 4 halves per lane and row tile;
@@ -217,27 +204,18 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_block_kernel(const FfnParams P
         for (int rt = 0; rt < 2; ++rt) hb[rt] = *reinterpret_cast<const vec8<T>*>(xch + ((cb * 2 + rt) * 64 + lane) * 16);
       };
       rd_h(0);
-      vec8<T> fa[FF_DEPTH + 1][2];
       // group g: k-step (chunk) g / 5, output tiles 2 (g % 5), + 1 of this wave's 10
-      auto rd = [&](int g, vec8<T> (&f)[2]) __attribute__((always_inline)) {
+      ff_tile_groups<T, 2, FF_DEPTH>(frag, Os, role * NTW, fr, fq,
+        [&](int g, vec8<T> (&f)[2]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int q = 0; q < 2; ++q) f[q] = frag(Os, (role * NTW + 2 * (g % 5) + q) * 16 + fr, 4 * (g / 5) + fq);
-      };
+          for (int q = 0; q < 2; ++q)
 #pragma unroll
-      for (int d = 0; d < FF_DEPTH; ++d) rd(d, fa[d]);
-#pragma unroll
-      for (int g = 0; g < 10; ++g) {
-        if (g + FF_DEPTH < 10) rd(g + FF_DEPTH, fa[(g + FF_DEPTH) % (FF_DEPTH + 1)]);
-        FF_FENCE();
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-          for (int rt = 0; rt < 2; ++rt)
-            acc[2 * (g % 5) + q][rt] = lr_mfma16(fa[g % (FF_DEPTH + 1)][q], hb[rt], acc[2 * (g % 5) + q][rt]);
-        if (more && g < KL) issue_w1(1, 2 * j + 3, g);
-        if (g == 4) rd_h(1);
-        FF_FENCE();
-      }
+            for (int rt = 0; rt < 2; ++rt) acc[2 * (g % 5) + q][rt] = lr_mfma16(f[q], hb[rt], acc[2 * (g % 5) + q][rt]);
+        },
+        [&](int g) __attribute__((always_inline)) {
+          if (more && g < KL) issue_w1(1, 2 * j + 3, g);
+          if (g == 4) rd_h(1);
+        });
     }
   }
   if constexpr (POST) {
@@ -297,25 +275,14 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_block_kernel(const FfnParams P
     for (int pc = 0; pc < KL; ++pc) {
       if (pc == 0) xa_wait_vmcnt<10>(); else if (pc + 1 < KL) xa_wait_vmcnt<5>(); else xa_wait_vmcnt<0>();
       __builtin_amdgcn_s_barrier();
-      const char* Os = smem + (pc % 3) * FF_SLOT;
-      vec8<T> fa[2][2];
-      auto rd = [&](int g, vec8<T> (&f)[2]) __attribute__((always_inline)) {
+      ff_tile_groups<T, 2, 1>(frag, smem + (pc % 3) * FF_SLOT, role * NTW, fr, fq,
+        [&](int g, vec8<T> (&f)[2]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int q = 0; q < 2; ++q) f[q] = frag(Os, (role * NTW + 2 * (g % 5) + q) * 16 + fr, 4 * (g / 5) + fq);
-      };
-      rd(0, fa[0]);
+          for (int q = 0; q < 2; ++q)
 #pragma unroll
-      for (int g = 0; g < 10; ++g) {
-        if (g + 1 < 10) rd(g + 1, fa[(g + 1) & 1]);
-        FF_FENCE();
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-          for (int rt = 0; rt < 2; ++rt)
-            acc[2 * (g % 5) + q][rt] = lr_mfma16(fa[g & 1][q], ball[2 * pc + g / 5][rt], acc[2 * (g % 5) + q][rt]);
-        if (pc >= 1 && pc + 2 < KL && g < KL) issue_wp((pc + 2) % 3, pc + 2, g);
-        FF_FENCE();
-      }
+            for (int rt = 0; rt < 2; ++rt) acc[2 * (g % 5) + q][rt] = lr_mfma16(f[q], ball[2 * pc + g / 5][rt], acc[2 * (g % 5) + q][rt]);
+        },
+        [&](int g) __attribute__((always_inline)) { if (pc >= 1 && pc + 2 < KL && g < KL) issue_wp((pc + 2) % 3, pc + 2, g); });
     }
   }
 #undef FF_FENCE
@@ -443,13 +410,8 @@ static int ffn_block_t(const lr_ffn_args* a, lr_stream_t s) {
     P.gp_hw = a->gn_hw; P.gp_chunks = a->gn_hw / FF_ROWS;
   }
   static unsigned long long attr_done[2] = {0, 0};
-  if (lr_attr_needed(&attr_done[post])) {
-    hipFuncSetAttribute(post ? reinterpret_cast<const void*>(ffn_block_kernel<T, true>) : reinterpret_cast<const void*>(ffn_block_kernel<T, false>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  }
-  if (post) hipLaunchKernelGGL((ffn_block_kernel<T, true>), dim3(P.nblocks), dim3(FF_THREADS), smem, (hipStream_t)s, P);
-  else hipLaunchKernelGGL((ffn_block_kernel<T, false>), dim3(P.nblocks), dim3(FF_THREADS), smem, (hipStream_t)s, P);
-  return lr_launch_status();
+  return lr_launch_dyn(post ? ffn_block_kernel<T, true> : ffn_block_kernel<T, false>, &attr_done[post], dim3(P.nblocks), dim3(FF_THREADS), smem,
+                       (hipStream_t)s, P);
 }
 
 extern "C" int lr_ffn_block_f16(const lr_ffn_args* a, lr_stream_t s) { return ffn_block_t<f16>(a, s); }

@@ -13,6 +13,8 @@
 // step, no fill / drain between pieces; a piece's four accumulator tiles are emitted (bias, gate, 16 bits, permlane swap, 16-byte stores)
 // WHILE the next piece multiplies.  Weight bytes through the LDS are the same as the tiled GEMM's (every block streams its slice once per
 // 128 rows); what goes away are the per-tile bubbles.
+// (The kernels keep their own copies of the row load, LayerNorm, GroupNorm-on-load and ring addressing that chain_common.h states for
+// the other chain kernels: with the shared helpers two shapes measured outside the parent's runs, profiles/chain_helpers_bench.json.)
 #include "chain_common.h"
 
 #define RL_ROWS 128
@@ -473,10 +475,7 @@ template <typename T, bool GEGLU, bool LN, bool GN>
 static int rowlin4_launch(const RowlinParams& P, hipStream_t st) {
   const size_t smem = 3 * R4_SLOT + (size_t)(RL_MAX_SLICE + (GN ? 2 * 640 + 64 : 0)) * sizeof(float);      // <= 77 KB: two blocks per CU
   static unsigned long long attr_done = 0;
-  if (lr_attr_needed(&attr_done))
-    hipFuncSetAttribute(reinterpret_cast<const void*>(rowlin4_kernel<T, GEGLU, LN, GN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL((rowlin4_kernel<T, GEGLU, LN, GN>), dim3((P.M / R4_ROWS) * P.ny), dim3(R4_THREADS), smem, st, P);
-  return lr_launch_status();
+  return lr_launch_dyn(rowlin4_kernel<T, GEGLU, LN, GN>, &attr_done, dim3((P.M / R4_ROWS) * P.ny), dim3(R4_THREADS), smem, st, P);
 }
 
 // column slices of the 4-wave form: ~two blocks per CU, dividing the number of 32-row pieces, at least 3 pieces per block
@@ -510,10 +509,7 @@ template <typename T, int C, bool GEGLU, bool LN, bool GN = false>
 static int rowlin_launch(const RowlinParams& P, hipStream_t st) {
   const size_t smem = 3 * RL_SLOT + (size_t)(RL_MAX_SLICE + (GN ? 2 * C + 64 : 0)) * sizeof(float);
   static unsigned long long attr_done = 0;
-  if (lr_attr_needed(&attr_done))
-    hipFuncSetAttribute(reinterpret_cast<const void*>(rowlin_kernel<T, C, GEGLU, LN, GN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL((rowlin_kernel<T, C, GEGLU, LN, GN>), dim3((P.M / (C == 320 ? 2 * RL_ROWS : RL_ROWS)) * P.ny), dim3(RL_THREADS), smem, st, P);
-  return lr_launch_status();
+  return lr_launch_dyn(rowlin_kernel<T, C, GEGLU, LN, GN>, &attr_done, dim3((P.M / (C == 320 ? 2 * RL_ROWS : RL_ROWS)) * P.ny), dim3(RL_THREADS), smem, st, P);
 }
 
 template <typename T>

@@ -48,6 +48,27 @@ extern "C" void lr_stin_set_trace(void* p) { g_si_trace = (unsigned long long*)p
 #define SI_STAMP(k) do { } while (0)
 #endif
 
+// xa_gn_tables' scale / shift tables (chain_common.h) applied to one set of B-operand rows
+template <typename T, int KL>
+__device__ __forceinline__ void xa_gn_apply_rows(vec8<T> (&xf)[KL][2], const float* tabA, const float* tabB, int fq) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  tabA += 8 * fq; tabB += 8 * fq;      // this lane's eight channels of every 32
+#pragma unroll
+  for (int t5 = 0; t5 < KL; ++t5)
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int c0 = 64 * t5 + 32 * u;
+      const f32x4 a0 = *reinterpret_cast<const f32x4*>(tabA + c0), a1 = *reinterpret_cast<const f32x4*>(tabA + c0 + 4);
+      const f32x4 b0 = *reinterpret_cast<const f32x4*>(tabB + c0), b1 = *reinterpret_cast<const f32x4*>(tabB + c0 + 4);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        xf[t5][u][i] = (T)fmaf((float)xf[t5][u][i], a0[i], b0[i]);
+        xf[t5][u][4 + i] = (T)fmaf((float)xf[t5][u][4 + i], a1[i], b1[i]);
+      }
+    }
+#endif
+}
+
 template <typename T, bool GN>
 __global__ __launch_bounds__(SI_THREADS) void stin_block_kernel(const StinParams P) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -66,17 +87,11 @@ __global__ __launch_bounds__(SI_THREADS) void stin_block_kernel(const StinParams
   // ---- the wave's 32 rows as two B-operand sets: lane (fr, fq), set rs holds x[m_w0 + 16 rs + fr][64 t5 + 32 u + 8 fq .. + 7]
   vec8<T> xf[2][KL][2];
 #pragma unroll
-  for (int rs = 0; rs < 2; ++rs) {
-    const T* xrow = reinterpret_cast<const T*>(P.x) + (size_t)(m_w0 + 16 * rs + fr) * C + 8 * fq;
-#pragma unroll
-    for (int t5 = 0; t5 < KL; ++t5)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) xf[rs][t5][u] = *reinterpret_cast<const vec8<T>*>(xrow + 64 * t5 + 32 * u);
-  }
+  for (int rs = 0; rs < 2; ++rs) xa_load_rows<T, KL>(xf[rs], reinterpret_cast<const T*>(P.x) + (size_t)(m_w0 + 16 * rs + fr) * C + 8 * fq);
   for (int i = t; i < (C + P.NQ) / 4; i += SI_THREADS) {      // bias rows -> LDS (no register loads inside the piece loop)
     const float* src = i < C / 4 ? P.bp + 4 * i : P.bqkv + 4 * (i - C / 4);
     *reinterpret_cast<f32x4*>(par + 4 * i) = *reinterpret_cast<const f32x4*>(src);
-  }
+  }      // (inline, not xa_stage_bias: its segment loop changes this kernel's code far beyond the prologue; profiles/chain_helpers_trials.txt)
   if constexpr (GN) {
     // the block's 256 rows lie in ONE sample (gn_hw % 256 == 0): its scale / shift tables, then the rows are normalised in place and
     // rounded to 16 bits -- the tensor lr_groupnorm_apply_n would have written, bit for bit, without the round trip through memory
@@ -84,36 +99,21 @@ __global__ __launch_bounds__(SI_THREADS) void stin_block_kernel(const StinParams
     float* tabB = tabA + C;
     xa_gn_tables(P.gn_part, P.gn_chunks, (blockIdx.x * SI_ROWS) / P.gn_hw, P.gn_hw, C, P.gn_gamma, P.gn_beta, P.gn_eps, tabA, tabB, tabB + C, t, SI_THREADS);
 #pragma unroll
-    for (int rs = 0; rs < 2; ++rs)
-#pragma unroll
-      for (int t5 = 0; t5 < KL; ++t5)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int c0 = 64 * t5 + 32 * u + 8 * fq;
-          const f32x4 a0 = *reinterpret_cast<const f32x4*>(tabA + c0), a1 = *reinterpret_cast<const f32x4*>(tabA + c0 + 4);
-          const f32x4 b0 = *reinterpret_cast<const f32x4*>(tabB + c0), b1 = *reinterpret_cast<const f32x4*>(tabB + c0 + 4);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            xf[rs][t5][u][i] = (T)fmaf((float)xf[rs][t5][u][i], a0[i], b0[i]);
-            xf[rs][t5][u][4 + i] = (T)fmaf((float)xf[rs][t5][u][4 + i], a1[i], b1[i]);
-          }
-        }
+    for (int rs = 0; rs < 2; ++rs) xa_gn_apply_rows<T, KL>(xf[rs], tabA, tabB, fq);
   }
 
   // ---- weight ring: piece s < 5 = rows 64 s .. of Wp, piece s >= 5 = rows 64 (s - 5) .. of Wqkv; 5 LDS-DMA instructions of 1 KiB per wave
   const __amdgpu_buffer_rsrc_t rsP = uniform_rsrc(P.wp, (size_t)C * C * 2);
   const __amdgpu_buffer_rsrc_t rsQ = uniform_rsrc(P.wqkv, (size_t)P.NQ * C * 2);
-  const int lrow = w * 8 + (lane >> 3);                      // row of a 64-row sub-tile this lane fills
-  const int lchunk = (lane & 7) ^ ((lrow >> 1) & 7);         // source-side swizzle
+  const int lrow = xa_ring_row(w, lane), lchunk = xa_ring_chunk(lane, lrow);      // row of a 64-row sub-tile this lane fills, its chunk (chain_common.h)
   const unsigned vrow = (unsigned)((lrow * C + lchunk * 8) * 2);
-  const unsigned OOB = 0x80000000u;
   // sub-tile i of rows 64 n .. of Wp -> slot
   auto issue_p = [&](int slot, int n, int i) __attribute__((always_inline)) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsP, (lptr_t)(smem + slot * SI_SLOT + (i * 64 + w * 8) * 128), 16, vrow, n * 64 * C * 2 + i * 128, 0, 0);
   };
   // sub-tile i of rows 64 n .. of Wqkv -> slot (live = false: out-of-range offset, zeros nobody reads -- keeps the counted waits uniform)
   auto issue_q = [&](int slot, int n, int i, bool live = true) __attribute__((always_inline)) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsQ, (lptr_t)(smem + slot * SI_SLOT + (i * 64 + w * 8) * 128), 16, live ? vrow : OOB,
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsQ, (lptr_t)(smem + slot * SI_SLOT + (i * 64 + w * 8) * 128), 16, live ? vrow : XA_OOB,
                                              n * 64 * C * 2 + i * 128, 0, 0);
   };
   const int nq = P.NQ / 64;                // pieces of the second stage: a multiple of 3, so every piece's slot is a compile-time constant
@@ -129,10 +129,7 @@ __global__ __launch_bounds__(SI_THREADS) void stin_block_kernel(const StinParams
 #pragma unroll
   for (int i = 0; i < KL; ++i) issue_p(1, PP(1), i);
 
-  const int sw = (fr >> 1) & 7;
-  auto frag = [&](const char* base, int row, int chunk) -> vec8<T> {
-    return *reinterpret_cast<const vec8<T>*>(base + row * 128 + ((chunk ^ sw) << 4));
-  };
+  const XaFrag<T> frag(fr);
   const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
 #define SI_FENCE() __builtin_amdgcn_sched_barrier(0)
 // timing experiments of developer variants (tools/build_variant.sh x -DSI_DBG_NODMA ...): results are garbage, only the clock matters
@@ -220,49 +217,11 @@ __global__ __launch_bounds__(SI_THREADS) void stin_block_kernel(const StinParams
   xa_wait_vmcnt<0>();
   SI_STAMP(63);
 #pragma unroll
-  for (int rs = 0; rs < 2; ++rs) {
-    const T* xrow = x1 + (size_t)(m_w0 + 16 * rs + fr) * C + 8 * fq;
-#pragma unroll
-    for (int t5 = 0; t5 < KL; ++t5)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) xf[rs][t5][u] = *reinterpret_cast<const vec8<T>*>(xrow + 64 * t5 + 32 * u);
-  }
+  for (int rs = 0; rs < 2; ++rs) xa_load_rows<T, KL>(xf[rs], x1 + (size_t)(m_w0 + 16 * rs + fr) * C + 8 * fq);
 #pragma unroll
   for (int rs = 0; rs < 2; ++rs) {
     __builtin_amdgcn_sched_barrier(0);      // one row set at a time (register pressure)
-    float sm = 0.f;
-#pragma unroll
-    for (int t5 = 0; t5 < KL; ++t5)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) sm += (float)xf[rs][t5][u][i];
-    const float mean = xa_row4_sum(sm) * (1.0f / C);
-    // (each pass converts the 16-bit values again: the opaque touch keeps hipcc from holding 160 converted floats across the passes,
-    // which spilled 15 registers to scratch)
-#pragma unroll
-    for (int t5 = 0; t5 < KL; ++t5)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) asm volatile("" : "+v"(xf[rs][t5][u]));
-    float q2 = 0.f;
-#pragma unroll
-    for (int t5 = 0; t5 < KL; ++t5)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { const float d = (float)xf[rs][t5][u][i] - mean; q2 = fmaf(d, d, q2); }
-    const float rstd = rsqrtf(xa_row4_sum(q2) * (1.0f / C) + P.eps);
-    const float nmr = -mean * rstd;
-#pragma unroll
-    for (int t5 = 0; t5 < KL; ++t5)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) asm volatile("" : "+v"(xf[rs][t5][u]));
-#pragma unroll
-    for (int t5 = 0; t5 < KL; ++t5)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) xf[rs][t5][u][i] = (T)fmaf((float)xf[rs][t5][u][i], rstd, nmr);
+    xa_layernorm_rows<T, KL, true>(xf[rs], P.eps);
   }
 
   // ================= stage 2: qkv = xn Wqkv^T + bqkv, 64 columns per piece ================================================
@@ -322,16 +281,8 @@ static int stin_block_t(const lr_stin_args* a, lr_stream_t s) {
 #endif
   const size_t smem = 3 * SI_SLOT + (size_t)(SI_C + a->NQ + 2 * SI_C + 64) * sizeof(float);
   static unsigned long long attr_done[2] = {0, 0};
-  if (gn) {
-    if (lr_attr_needed(&attr_done[1]))
-      hipFuncSetAttribute(reinterpret_cast<const void*>(stin_block_kernel<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL((stin_block_kernel<T, true>), dim3(a->M / SI_ROWS), dim3(SI_THREADS), smem, (hipStream_t)s, P);
-  } else {
-    if (lr_attr_needed(&attr_done[0]))
-      hipFuncSetAttribute(reinterpret_cast<const void*>(stin_block_kernel<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL((stin_block_kernel<T, false>), dim3(a->M / SI_ROWS), dim3(SI_THREADS), smem, (hipStream_t)s, P);
-  }
-  return lr_launch_status();
+  return lr_launch_dyn(gn ? stin_block_kernel<T, true> : stin_block_kernel<T, false>, &attr_done[gn], dim3(a->M / SI_ROWS), dim3(SI_THREADS), smem,
+                       (hipStream_t)s, P);
 }
 
 extern "C" int lr_stin_block_f16(const lr_stin_args* a, lr_stream_t s) { return stin_block_t<f16>(a, s); }

@@ -25,6 +25,9 @@
 // in registers with a two-pass mean / variance (no producer statistics needed).
 // Epilogue: out^T + bias -> fp16 -> wave-private LDS rows -> whole 16-byte pieces: + residual (x, L2-hot), store, and the
 // per-row (sum, sumsq) of the rounded output for the LayerNorm folded into the GEGLU projection that follows.
+// The device code below is the kernel's own copy of the blocks that chain_common.h states for the other chain kernels (row load,
+// LayerNorm, ring addressing, softmax, epilogue): with the shared helpers the plain kernel measured outside its parent's runs
+// (profiles/chain_helpers_bench.json), so it shares only XattnParams, the host fill and the launch helper.
 #include "chain_common.h"
 #include <type_traits>
 
@@ -35,18 +38,6 @@
 #define XA_SLOT 40960
 #define XA_PITCH 656          // bytes per staged output row (640 + 16: the 16 rows of a wave start in distinct banks)
 #define XA_VT_OFF 16384       // V^T sub-tiles inside the K|V slot
-
-struct XattnParams {
-  const void* x; const void* wq; const float* bq; const void* k; const void* vt; const void* wo; const float* bo;
-  void* out; float* st_out;
-  const void* pre_a; const void* pre_w; const float* pre_b;      // PRE: x1 = pre_a pre_w^T + pre_b + x runs in front (see below)
-  int M, HW, Lc, ldk, nblocks;
-  float eps, c;               // c = scale * log2(e)
-  unsigned k_bytes, vt_bytes;
-#ifdef LR_XATTN_TRACE
-  unsigned long long* trace;   // developer build only: shader-clock stamps [block][8 waves][24] (tools/trace_xattn.py)
-#endif
-};
 
 #ifdef LR_XATTN_TRACE
 #define XA_STAMP(k) do { if (P.trace && lane == 0) P.trace[((size_t)blockIdx.x * 8 + w) * 24 + (k)] = __builtin_readcyclecounter(); } while (0)
@@ -500,34 +491,17 @@ static int xattn_block_t(const lr_xattn_args* a, lr_stream_t s) {
     if (((uintptr_t)a->pre_a | (uintptr_t)a->pre_w | (uintptr_t)a->pre_b) & 15) return LR_E_ALIGN;
   }
   if (wide) return lr_xattn640_launch(a, std::is_same<T, bf16>::value ? 1 : 0, s);
-  const int B = a->M / a->HW;
-  const int64_t kb = (int64_t)B * a->Lc * a->ldk * 2, vb = (int64_t)B * XA_HEADS * 2 * 64 * 128;
-  if (kb >= ((int64_t)1 << 31) || vb >= ((int64_t)1 << 31)) return LR_E_UNSUPPORTED;
   XattnParams P;
-  P.x = a->x; P.wq = a->wq; P.bq = a->bq; P.k = a->k; P.vt = a->vt; P.wo = a->wo; P.bo = a->bo; P.out = a->out;
-  P.st_out = a->stats_out;
-  P.M = a->M; P.HW = a->HW; P.Lc = a->Lc; P.ldk = a->ldk; P.nblocks = a->M / XA_ROWS;
-  P.eps = a->ln_eps; P.c = a->scale * 1.44269504088896340736f;
-  P.k_bytes = (unsigned)kb; P.vt_bytes = (unsigned)vb;
+  if (int e = xattn_fill_params(P, a, XA_ROWS, XA_HEADS)) return e;
 #ifdef LR_XATTN_TRACE
   P.trace = g_xa_trace;
 #endif
   const size_t smem = 3 * XA_SLOT + 3 * XA_C * sizeof(float);
-  const bool six = a->Lc > 80, pre = a->pre_a != nullptr;
-  P.pre_a = a->pre_a; P.pre_w = a->pre_w; P.pre_b = a->pre_b;
-  const void* fns[4] = {reinterpret_cast<const void*>(xattn_block_kernel<T, 5, false>), reinterpret_cast<const void*>(xattn_block_kernel<T, 6, false>),
-                        reinterpret_cast<const void*>(xattn_block_kernel<T, 5, true>), reinterpret_cast<const void*>(xattn_block_kernel<T, 6, true>)};
+  static constexpr void (*fns[4])(XattnParams) = {xattn_block_kernel<T, 5, false>, xattn_block_kernel<T, 6, false>,
+                                                  xattn_block_kernel<T, 5, true>, xattn_block_kernel<T, 6, true>};
   static unsigned long long attr_done[4] = {0, 0, 0, 0};
-  const int v = (pre ? 2 : 0) + (six ? 1 : 0);
-  if (lr_attr_needed(&attr_done[v])) {
-    hipFuncSetAttribute(fns[v], hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  }
-  const dim3 grid(P.nblocks), block(XA_THREADS);
-  if (v == 0) hipLaunchKernelGGL((xattn_block_kernel<T, 5, false>), grid, block, smem, (hipStream_t)s, P);
-  else if (v == 1) hipLaunchKernelGGL((xattn_block_kernel<T, 6, false>), grid, block, smem, (hipStream_t)s, P);
-  else if (v == 2) hipLaunchKernelGGL((xattn_block_kernel<T, 5, true>), grid, block, smem, (hipStream_t)s, P);
-  else hipLaunchKernelGGL((xattn_block_kernel<T, 6, true>), grid, block, smem, (hipStream_t)s, P);
-  return lr_launch_status();
+  const int v = (a->pre_a ? 2 : 0) + (a->Lc > 80 ? 1 : 0);
+  return lr_launch_dyn(fns[v], &attr_done[v], dim3(P.nblocks), dim3(XA_THREADS), smem, (hipStream_t)s, P);
 }
 
 extern "C" int lr_xattn_block_f16(const lr_xattn_args* a, lr_stream_t s) { return xattn_block_t<f16>(a, s); }

@@ -7,7 +7,7 @@
 // Work split.  The chain is row-local, and the 16384 rows of level 1 fill 256 CUs only with 64-row blocks: block = 4 waves = 64 rows
 // of ONE sample, one wave per SIMD with the whole 512-register file: a wave keeps its 16 rows as B operands (80 registers), the 40
 // output tiles out^T [640 x 16] (160), and with PRE the rounded x1 as residual (80).
-// Weights stream through the same 3-slot ring of 40 KB pieces (16-byte LDS-DMA, source-side XOR swizzle, loads two pieces ahead,
+// Weights stream through the same 3-slot ring of 40 KB pieces (16-byte LDS-DMA, source-side XOR swizzle of chain_common.h, loads two pieces ahead,
 // counted vmcnt + one barrier per piece); a [64 x 640] projection slice is two pieces (k halves), Wo_h [640 x 64] two pieces (n halves),
 // K_h and V_h^T one 16 KB piece each -- six pieces per head, so the slot of every piece is a compile-time constant:
 //     Q0 -> slot 0 | Q1 -> 1 | K -> 2 | V -> 0 | O0 -> 1 | O1 -> 2          (PRE: 20 pieces of Wo1 in front, piece j -> slot (j + 1) % 3)
@@ -22,18 +22,141 @@
 #define XB_SLOT 40960
 #define XB_PITCH 1296         // bytes per staged output row (1280 + 16: the 16 rows of a wave start in distinct banks)
 
-struct Xattn640Params {
-  const void* x; const void* wq; const float* bq; const void* k; const void* vt; const void* wo; const float* bo;
-  void* out; float* st_out;
-  const void* pre_a; const void* pre_w; const float* pre_b;
-  int M, HW, Lc, ldk, nblocks;
-  float eps, c;               // c = scale * log2(e)
-  unsigned k_bytes, vt_bytes;
-};
+#if defined(__HIP_DEVICE_COMPILE__)      // (the steps of the kernel below that read better under a name; device pass only, like its body)
+// PRE finish: x1 = acc + bo1 + x, rounded to 16 bits (what the unfused path stores) and kept in xres as the final residual; LayerNorm of
+// the rounded rows in accumulator layout; the normalised rows become the q projection's B operands in accumulator order; acc = 0.
+// bias = the bo1 row in LDS + 4 fq.
+template <typename T, int NT>
+__device__ __forceinline__ void xa_pre_finish(f32x4 (&acc)[NT], vec4<T> (&xres)[NT], vec8<T> (&xf)[NT / 4][2], const float* bias, float eps) {
+  constexpr int C = 16 * NT;
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    const f32x4 bj = *reinterpret_cast<const f32x4*>(bias + j * 16);
+    vec4<T> r16;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { r16[r] = (T)(acc[j][r] + bj[r] + (float)xres[j][r]); s += (float)r16[r]; }
+    xres[j] = r16;
+  }
+  const float mean = xa_row4_sum(s) * (1.0f / C);
+  float q2 = 0.f;
+#pragma unroll
+  for (int j = 0; j < NT; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { const float d = (float)xres[j][r] - mean; q2 = fmaf(d, d, q2); }
+  const float rstd = rsqrtf(xa_row4_sum(q2) * (1.0f / C) + eps);
+  const float nmr = -mean * rstd;
+#pragma unroll
+  for (int pp = 0; pp < NT / 2; ++pp) {
+    f32x4 n0, n1;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      n0[r] = fmaf((float)xres[2 * pp][r], rstd, nmr);
+      n1[r] = fmaf((float)xres[2 * pp + 1][r], rstd, nmr);
+    }
+    xf[pp >> 1][pp & 1] = xa_pack<T>(n0, n1);
+  }
+#pragma unroll
+  for (int j = 0; j < NT; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+}
+
+// Softmax over the S^T accumulators of a row (its keys live in the four lanes fr + 16 fq), in two steps so that a kernel can issue
+// LDS-DMA between them: keys >= Lc masked, row maximum; then p = exp2(c s - c max) in place, packed to the three B operands of the
+// P V product (key order pi), returning the row sum.
+template <int NKT>
+__device__ __forceinline__ float xa_softmax_max(f32x4 (&sa)[NKT], const XattnParams& P, int fq) {
+  float mx = -INFINITY;
+#pragma unroll
+  for (int jk = 0; jk < NKT; ++jk)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (jk * 16 + 4 * fq + r >= P.Lc) sa[jk][r] = -INFINITY;
+      mx = fmaxf(mx, sa[jk][r]);
+    }
+  return xa_row4_max(mx);
+}
+template <typename T, int NKT>
+__device__ __forceinline__ float xa_softmax_exp(f32x4 (&sa)[NKT], float mx, float c, vec8<T> (&pb)[3]) {
+  const float mc = mx * c;
+  float l = 0.f;
+#pragma unroll
+  for (int jk = 0; jk < NKT; ++jk)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float p = __builtin_amdgcn_exp2f(fmaf(sa[jk][r], c, -mc));
+      sa[jk][r] = p;
+      l += p;
+    }
+  l = xa_row4_sum(l);
+  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  pb[0] = xa_pack<T>(sa[0], sa[1]);
+  pb[1] = xa_pack<T>(sa[2], sa[3]);
+  pb[2] = xa_pack<T>(sa[4], NKT > 5 ? sa[NKT - 1] : z4);
+  return l;
+}
+
+// Epilogue: (acc + bo) -> 16 bits [PRE: + the rounded x1, the same two roundings as the unfused kernels] -> this wave's 16 LDS rows
+// (PITCH bytes apart: they start in distinct banks) -> whole 16-byte pieces: [plain: + the residual x, L2-hot] store, and the per-row
+// (sum, sumsq) of the rounded output for the LayerNorm folded into the projection that follows.  bo = the bias row in LDS.
+template <typename T, int C, int PITCH, bool PRE, int NX>
+__device__ __forceinline__ void xa_xattn_epilogue(const f32x4 (&acc)[C / 16], const vec4<T> (&xres)[NX], const float* bo, char* smem,
+                                                  const XattnParams& P, int m_w0, int w, int lane) {
+  const int fr = lane & 15, fq = lane >> 4;
+  __syncthreads();                            // every wave is done with the ring
+  char* stg = smem + w * (16 * PITCH);
+#pragma unroll
+  for (int j = 0; j < C / 16; ++j) {
+    const f32x4 v = acc[j] + *reinterpret_cast<const f32x4*>(bo + j * 16 + 4 * fq);
+    vec4<T> hv;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      hv[r] = (T)v[r];
+      if constexpr (PRE) hv[r] = (T)((float)hv[r] + (float)xres[j][r]);
+    }
+    *reinterpret_cast<vec4<T>*>(stg + fr * PITCH + (j * 16 + 4 * fq) * 2) = hv;
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  const int row = lane >> 2, sub = lane & 3;
+  const T* xr = reinterpret_cast<const T*>(P.x) + (size_t)(m_w0 + row) * C;
+  T* orow = reinterpret_cast<T*>(P.out) + (size_t)(m_w0 + row) * C;
+  float s1 = 0.f, s2 = 0.f;
+  constexpr int NP = C / 32;                  // 16-byte pieces per lane (4 lanes per row)
+  uint4 rx[PRE ? 1 : NP];
+  if constexpr (!PRE) {
+#pragma unroll
+    for (int it = 0; it < NP; ++it) rx[it] = *reinterpret_cast<const uint4*>(xr + (sub + 4 * it) * 8);
+  }
+#pragma unroll
+  for (int it = 0; it < NP; ++it) {
+    const int piece = sub + 4 * it;
+    float a[8], e[8];
+    uint4 pk = *reinterpret_cast<const uint4*>(stg + row * PITCH + piece * 16);
+    lr_unpack8<T>(pk, a);
+    if constexpr (!PRE) {
+      lr_unpack8<T>(rx[it], e);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) a[i] += e[i];
+      pk = lr_pack8<T>(a);
+    }
+    *reinterpret_cast<uint4*>(orow + piece * 8) = pk;
+    lr_unpack8<T>(pk, a);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { s1 += a[i]; s2 = fmaf(a[i], a[i], s2); }
+  }
+  if (P.st_out) {
+    s1 += __shfl_xor(s1, 1, 64); s2 += __shfl_xor(s2, 1, 64);
+    s1 += __shfl_xor(s1, 2, 64); s2 += __shfl_xor(s2, 2, 64);
+    if (sub == 0) {
+      float2 o; o.x = s1; o.y = s2;
+      *reinterpret_cast<float2*>(P.st_out + (size_t)(m_w0 + row) * 2) = o;
+    }
+  }
+}
+#endif
 
 // NKT = 16-key tiles of the context (5: Lc <= 80, 6: Lc <= 96); PRE: see xattn_block.hip
 template <typename T, int NKT, bool PRE>
-__global__ __launch_bounds__(XB_THREADS) void xattn640_kernel(const Xattn640Params P) {
+__global__ __launch_bounds__(XB_THREADS) void xattn640_kernel(const XattnParams P) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int C = XB_C, NT = C / 16, KL = C / 64;   // 40 output tiles, 10 lines of 128 B per row
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -42,11 +165,7 @@ __global__ __launch_bounds__(XB_THREADS) void xattn640_kernel(const Xattn640Para
   const int t = threadIdx.x, lane = t & 63;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int fr = lane & 15, fq = lane >> 4;
-  int bid = blockIdx.x;
-  {   // XCD-aware bijective remap: consecutive row blocks (one sample's K / V) stay on one XCD's L2
-    const int q = P.nblocks >> 3, r = P.nblocks & 7, xcd = bid & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int bid = xa_xcd_remap(blockIdx.x, P.nblocks);
   const int m0 = bid * XB_ROWS;
   const int b = m0 / P.HW;
 #ifndef XB_ROTATE      // measured (profiles/r06_rotation_ab.txt): 61.9 vs 61.5 us plain, 71.1 vs 73.8 us with PRE -- within the run-to-run spread; off
@@ -58,13 +177,9 @@ __global__ __launch_bounds__(XB_THREADS) void xattn640_kernel(const Xattn640Para
 #endif
   const int m_w0 = m0 + w * 16;
 
-  // ---- this wave's 16 rows in B-operand form: lane (fr, fq) holds x[m_w0 + fr][64 t5 + 32 u + 8 fq .. + 7]
-  const T* xrow = reinterpret_cast<const T*>(PRE ? P.pre_a : P.x) + (size_t)(m_w0 + fr) * C + 8 * fq;
+  // ---- this wave's 16 rows in B-operand form (xa_load_rows)
   vec8<T> xf[KL][2];
-#pragma unroll
-  for (int t5 = 0; t5 < KL; ++t5)
-#pragma unroll
-    for (int u = 0; u < 2; ++u) xf[t5][u] = *reinterpret_cast<const vec8<T>*>(xrow + 64 * t5 + 32 * u);
+  xa_load_rows<T, KL>(xf, reinterpret_cast<const T*>(PRE ? P.pre_a : P.x) + (size_t)(m_w0 + fr) * C + 8 * fq);
   // PRE: the residual x in ACCUMULATOR layout (lane (fr, fq), tile j: x[m_w0 + fr][16 j + 4 fq .. + 3]); later the rounded x1
   vec4<T> xres[PRE ? NT : 1];
   if constexpr (PRE) {
@@ -72,14 +187,7 @@ __global__ __launch_bounds__(XB_THREADS) void xattn640_kernel(const Xattn640Para
 #pragma unroll
     for (int j = 0; j < NT; ++j) xres[j] = *reinterpret_cast<const vec4<T>*>(xd + 16 * j);
   }
-#pragma unroll
-  for (int i0 = 0; i0 < (PRE ? 3 : 2) * (C / 4); i0 += XB_THREADS) {      // biases -> LDS (the loops below issue no register loads)
-    const int i = i0 + t;
-    if (i < (PRE ? 3 : 2) * (C / 4)) {
-      const float* src = i < C / 4 ? P.bq + 4 * i : i < C / 2 ? P.bo + 4 * (i - C / 4) : P.pre_b + 4 * (i - C / 2);
-      *reinterpret_cast<f32x4*>(par + 4 * i) = *reinterpret_cast<const f32x4*>(src);
-    }
-  }
+  xa_stage_bias<XB_THREADS>(par, {{P.bq, C}, {P.bo, C}, {P.pre_b, PRE ? C : 0}}, t);
 
   // ---- weight ring: every piece is a set of 1 KiB LDS-DMA instructions, 32 rows of 128 B per block-wide round (wave w: rows 8 w .. + 7)
   const __amdgpu_buffer_rsrc_t rsQ = uniform_rsrc(P.wq, (size_t)C * C * 2);
@@ -87,21 +195,20 @@ __global__ __launch_bounds__(XB_THREADS) void xattn640_kernel(const Xattn640Para
   const __amdgpu_buffer_rsrc_t rsK = uniform_rsrc(P.k, P.k_bytes);
   const __amdgpu_buffer_rsrc_t rsV = uniform_rsrc(P.vt, P.vt_bytes);
   const __amdgpu_buffer_rsrc_t rsP = uniform_rsrc(PRE ? P.pre_w : P.wq, (size_t)C * C * 2);
-  const unsigned OOB = 0x80000000u;
-  const int lrow = w * 8 + (lane >> 3);                      // row of a 32-row round this lane fills
-  const int lchunk = (lane & 7) ^ ((lrow >> 1) & 7);         // source-side swizzle (bits 1..3 of the row: same for row + 32 i)
+  const int lrow = xa_ring_row(w, lane);                     // row of a 32-row round this lane fills
+  const int lchunk = xa_ring_chunk(lane, lrow);              // source-side swizzle (chain_common.h)
   // [64 rows x 320 k] of a [C][C] matrix (rows r0 .., columns c0 ..) as 5 sub-tiles [64 x 64 k]; instruction i = 0 .. 9: sub-tile i >> 1, row half i & 1
   // (live = false: an out-of-range offset -- zeros land in the slot, nobody reads them; keeps the loop free of branches and the counted
   // vmcnt waits uniform over the heads)
   auto issue_mat = [&](const __amdgpu_buffer_rsrc_t rs, int slot, int r0, int c0, int i, bool live = true) __attribute__((always_inline)) {
-    const unsigned v0 = live ? (unsigned)(((r0 + lrow) * C + lchunk * 8) * 2) : OOB;
+    const unsigned v0 = live ? (unsigned)(((r0 + lrow) * C + lchunk * 8) * 2) : XA_OOB;
     const int t5 = i >> 1, hh = i & 1;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t)(smem + slot * XB_SLOT + (t5 * 64 + hh * 32 + w * 8) * 128), 16, v0,
                                              (hh * 32 * C + c0 + t5 * 64) * 2, 0, 0);
   };
   auto issue_k = [&](int slot, int h, int i) __attribute__((always_inline)) {    // K_h [128 keys x 64 d]; i = 0 .. 3: keys 32 i + lrow
     const int key = i * 32 + lrow;
-    const unsigned vk = key < P.Lc ? (unsigned)((((size_t)b * P.Lc + key) * P.ldk + h * 64 + lchunk * 8) * 2) : OOB;
+    const unsigned vk = key < P.Lc ? (unsigned)((((size_t)b * P.Lc + key) * P.ldk + h * 64 + lchunk * 8) * 2) : XA_OOB;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsK, (lptr_t)(smem + slot * XB_SLOT + (i * 32 + w * 8) * 128), 16, vk, 0, 0, 0);
   };
   auto issue_v = [&](int slot, int h, int i) __attribute__((always_inline)) {    // V_h^T 2 x [64 d x 64 key slots]; i = 0 .. 3: rows 32 i + lrow of the pair
@@ -125,43 +232,17 @@ __global__ __launch_bounds__(XB_THREADS) void xattn640_kernel(const Xattn640Para
   }
 
   // ---- LayerNorm of the rows in registers (two-pass), gamma / beta live in Wq / bq
-  if constexpr (!PRE) {
-    float s = 0.f;
-#pragma unroll
-    for (int t5 = 0; t5 < KL; ++t5)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s += (float)xf[t5][u][i];
-    const float mean = xa_row4_sum(s) * (1.0f / C);
-    float q2 = 0.f;
-#pragma unroll
-    for (int t5 = 0; t5 < KL; ++t5)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { const float d = (float)xf[t5][u][i] - mean; q2 = fmaf(d, d, q2); }
-    const float rstd = rsqrtf(xa_row4_sum(q2) * (1.0f / C) + P.eps);
-    const float nmr = -mean * rstd;
-#pragma unroll
-    for (int t5 = 0; t5 < KL; ++t5)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) xf[t5][u][i] = (T)fmaf((float)xf[t5][u][i], rstd, nmr);
-  }
+  if constexpr (!PRE) xa_layernorm_rows<T, KL, false>(xf, P.eps);
 
   f32x4 acc[NT];
 #pragma unroll
   for (int j = 0; j < NT; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-  const int sw = (fr >> 1) & 7;      // swizzle of every fragment row this lane reads (rows are fr + a multiple of 16)
-  auto frag = [&](const char* base, int row, int chunk) -> vec8<T> {
-    return *reinterpret_cast<const vec8<T>*>(base + row * 128 + ((chunk ^ sw) << 4));
-  };
+  const XaFrag<T> frag(fr);
 #define XB_FENCE() __builtin_amdgcn_sched_barrier(0)
   // one [64 x 320 k] piece against the B operands xb[0 .. 4][0 .. 1]: 10 k-steps of 4 MFMAs into a0 .. a3, fragment reads one step ahead,
   // one LDS-DMA instruction of a later piece after each step (dma(ks))
+  // (this and the O0 / O1 loop below stay inline: as calls of a loop template (ffn_block.hip's ff_tile_groups shape) three PRE kernels get worse; profiles/chain_helpers_trials.txt)
 #define XB_MAT_STEP(Ws, XB0, A0, A1, A2, A3, DMA)                                                                              \
   {                                                                                                                             \
     vec8<T> fa[2][4];                                                                                                           \
@@ -195,36 +276,7 @@ __global__ __launch_bounds__(XB_THREADS) void xattn640_kernel(const Xattn640Para
                   { if (j + 2 < 2 * KL) issue_mat(rsP, (j + 3) % 3, 64 * ((j + 2) >> 1), 320 * ((j + 2) & 1), ks);
                     else issue_mat(rsQ, j + 2 - 2 * KL, h0 * 64, 320 * (j + 2 - 2 * KL), ks); });
     }
-    // x1 = acc + bo1 + x, rounded to fp16 (what the unfused path stores); LayerNorm of the rounded rows; B operands in accumulator order
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const f32x4 bj = *reinterpret_cast<const f32x4*>(par + 2 * C + j * 16 + 4 * fq);
-      vec4<T> r16;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { r16[r] = (T)(acc[j][r] + bj[r] + (float)xres[j][r]); s += (float)r16[r]; }
-      xres[j] = r16;
-    }
-    const float mean = xa_row4_sum(s) * (1.0f / C);
-    float q2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { const float d = (float)xres[j][r] - mean; q2 = fmaf(d, d, q2); }
-    const float rstd = rsqrtf(xa_row4_sum(q2) * (1.0f / C) + P.eps);
-    const float nmr = -mean * rstd;
-#pragma unroll
-    for (int pp = 0; pp < NT / 2; ++pp) {
-      f32x4 n0, n1;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        n0[r] = fmaf((float)xres[2 * pp][r], rstd, nmr);
-        n1[r] = fmaf((float)xres[2 * pp + 1][r], rstd, nmr);
-      }
-      xf[pp >> 1][pp & 1] = xa_pack<T>(n0, n1);
-    }
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    xa_pre_finish<T, NT>(acc, xres, xf, par + 2 * C + 4 * fq, P.eps);
   }
 
   // The heads are independent terms of out^T: block b starts at head h0 = (b / 8) mod 10 and wraps, so the ~32 blocks an XCD runs at once
@@ -268,32 +320,11 @@ __global__ __launch_bounds__(XB_THREADS) void xattn640_kernel(const Xattn640Para
       issue_wo(1, h, 0, 2); issue_wo(1, h, 0, 3);
       XB_FENCE();
     }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int jk = 0; jk < NKT; ++jk)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        if (jk * 16 + 4 * fq + r >= P.Lc) sa[jk][r] = -INFINITY;
-        mx = fmaxf(mx, sa[jk][r]);
-      }
+    const float mx = xa_softmax_max(sa, P, fq);
     issue_wo(1, h, 0, 4); issue_wo(1, h, 0, 5); issue_wo(1, h, 0, 6);
-    mx = xa_row4_max(mx);
-    const float mc = mx * P.c;
-    float l = 0.f;
-#pragma unroll
-    for (int jk = 0; jk < NKT; ++jk)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float p = __builtin_amdgcn_exp2f(fmaf(sa[jk][r], P.c, -mc));
-        sa[jk][r] = p;
-        l += p;
-      }
-    issue_wo(1, h, 0, 7); issue_wo(1, h, 0, 8); issue_wo(1, h, 0, 9);
-    l = xa_row4_sum(l);
     vec8<T> pb[3];
-    pb[0] = xa_pack<T>(sa[0], sa[1]);
-    pb[1] = xa_pack<T>(sa[2], sa[3]);
-    pb[2] = xa_pack<T>(sa[4], NKT > 5 ? sa[NKT - 1] : z4);
+    const float l = xa_softmax_exp<T>(sa, mx, P.c, pb);
+    issue_wo(1, h, 0, 7); issue_wo(1, h, 0, 8); issue_wo(1, h, 0, 9);
 
     // ================= V: O_h^T = V_h^T P^T ============================================================================
     xa_wait_vmcnt<10>();                      // V_h^T landed (Wo_h rows 0 .. 319 in flight)
@@ -357,84 +388,21 @@ __global__ __launch_bounds__(XB_THREADS) void xattn640_kernel(const Xattn640Para
 
   // ---- epilogue: (acc + bias) -> fp16 -> this wave's 16 LDS rows -> 16-byte pieces: + x, store, row statistics
   xa_wait_vmcnt<0>();                         // (the last head's dead prefetches)
-  __syncthreads();                            // every wave is done with the ring
-  char* stg = smem + w * (16 * XB_PITCH);
-#pragma unroll
-  for (int j = 0; j < NT; ++j) {
-    const f32x4 v = acc[j] + *reinterpret_cast<const f32x4*>(par + C + j * 16 + 4 * fq);
-    vec4<T> hv;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      hv[r] = (T)v[r];
-      if constexpr (PRE) hv[r] = (T)((float)hv[r] + (float)xres[j][r]);      // + x1 (same two roundings as the unfused kernels)
-    }
-    *reinterpret_cast<vec4<T>*>(stg + fr * XB_PITCH + (j * 16 + 4 * fq) * 2) = hv;
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  const int row = lane >> 2, sub = lane & 3;
-  const T* xr = reinterpret_cast<const T*>(P.x) + (size_t)(m_w0 + row) * C;
-  T* orow = reinterpret_cast<T*>(P.out) + (size_t)(m_w0 + row) * C;
-  float s1 = 0.f, s2 = 0.f;
-  constexpr int NP = C / 32;                  // 16-byte pieces per lane (4 lanes per row)
-  uint4 rx[PRE ? 1 : NP];
-  if constexpr (!PRE) {
-#pragma unroll
-    for (int it = 0; it < NP; ++it) rx[it] = *reinterpret_cast<const uint4*>(xr + (sub + 4 * it) * 8);
-  }
-#pragma unroll
-  for (int it = 0; it < NP; ++it) {
-    const int piece = sub + 4 * it;
-    float a[8], e[8];
-    uint4 pk = *reinterpret_cast<const uint4*>(stg + row * XB_PITCH + piece * 16);
-    lr_unpack8<T>(pk, a);
-    if constexpr (!PRE) {
-      lr_unpack8<T>(rx[it], e);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) a[i] += e[i];
-      pk = lr_pack8<T>(a);
-    }
-    *reinterpret_cast<uint4*>(orow + piece * 8) = pk;
-    lr_unpack8<T>(pk, a);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { s1 += a[i]; s2 = fmaf(a[i], a[i], s2); }
-  }
-  if (P.st_out) {
-    s1 += __shfl_xor(s1, 1, 64); s2 += __shfl_xor(s2, 1, 64);
-    s1 += __shfl_xor(s1, 2, 64); s2 += __shfl_xor(s2, 2, 64);
-    if (sub == 0) {
-      float2 o; o.x = s1; o.y = s2;
-      *reinterpret_cast<float2*>(P.st_out + (size_t)(m_w0 + row) * 2) = o;
-    }
-  }
+  xa_xattn_epilogue<T, C, XB_PITCH, PRE>(acc, xres, par + C, smem, P, m_w0, w, lane);
 #endif
 }
 
 template <typename T>
 static int xattn640_t(const lr_xattn_args* a, lr_stream_t s) {
   if (a->M % XB_ROWS || a->HW % XB_ROWS || a->M % a->HW) return LR_E_UNSUPPORTED;     // a block stays inside one sample
-  const int B = a->M / a->HW;
-  const int64_t kb = (int64_t)B * a->Lc * a->ldk * 2, vb = (int64_t)B * XB_HEADS * 2 * 64 * 128;
-  if (kb >= ((int64_t)1 << 31) || vb >= ((int64_t)1 << 31)) return LR_E_UNSUPPORTED;
-  Xattn640Params P;
-  P.x = a->x; P.wq = a->wq; P.bq = a->bq; P.k = a->k; P.vt = a->vt; P.wo = a->wo; P.bo = a->bo; P.out = a->out;
-  P.st_out = a->stats_out;
-  P.M = a->M; P.HW = a->HW; P.Lc = a->Lc; P.ldk = a->ldk; P.nblocks = a->M / XB_ROWS;
-  P.eps = a->ln_eps; P.c = a->scale * 1.44269504088896340736f;
-  P.k_bytes = (unsigned)kb; P.vt_bytes = (unsigned)vb;
-  P.pre_a = a->pre_a; P.pre_w = a->pre_w; P.pre_b = a->pre_b;
+  XattnParams P;
+  if (int e = xattn_fill_params(P, a, XB_ROWS, XB_HEADS)) return e;
   const size_t smem = 3 * XB_SLOT + 3 * XB_C * sizeof(float);
-  const bool six = a->Lc > 80, pre = a->pre_a != nullptr;
-  const void* fns[4] = {reinterpret_cast<const void*>(xattn640_kernel<T, 5, false>), reinterpret_cast<const void*>(xattn640_kernel<T, 6, false>),
-                        reinterpret_cast<const void*>(xattn640_kernel<T, 5, true>), reinterpret_cast<const void*>(xattn640_kernel<T, 6, true>)};
+  static constexpr void (*fns[4])(XattnParams) = {xattn640_kernel<T, 5, false>, xattn640_kernel<T, 6, false>,
+                                                  xattn640_kernel<T, 5, true>, xattn640_kernel<T, 6, true>};
   static unsigned long long attr_done[4] = {0, 0, 0, 0};
-  const int v = (pre ? 2 : 0) + (six ? 1 : 0);
-  if (lr_attr_needed(&attr_done[v])) hipFuncSetAttribute(fns[v], hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  const dim3 grid(P.nblocks), block(XB_THREADS);
-  if (v == 0) hipLaunchKernelGGL((xattn640_kernel<T, 5, false>), grid, block, smem, (hipStream_t)s, P);
-  else if (v == 1) hipLaunchKernelGGL((xattn640_kernel<T, 6, false>), grid, block, smem, (hipStream_t)s, P);
-  else if (v == 2) hipLaunchKernelGGL((xattn640_kernel<T, 5, true>), grid, block, smem, (hipStream_t)s, P);
-  else hipLaunchKernelGGL((xattn640_kernel<T, 6, true>), grid, block, smem, (hipStream_t)s, P);
-  return lr_launch_status();
+  const int v = (a->pre_a ? 2 : 0) + (a->Lc > 80 ? 1 : 0);
+  return lr_launch_dyn(fns[v], &attr_done[v], dim3(P.nblocks), dim3(XB_THREADS), smem, (hipStream_t)s, P);
 }
 
 // called by lr_xattn_block_f16 / _bf16 (xattn_block.hip) after the shared argument checks, for C = 640 / heads = 10

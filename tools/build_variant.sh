@@ -11,15 +11,15 @@ set -e
 cd "$(dirname "$0")/.."
 name=$1; shift
 out=leftrefill_amd/lib/variants; mkdir -p $out /tmp/lrv_$name
-all=$(python -c "from leftrefill_amd import build; print(' '.join(s[:-4] for s in build.SOURCES))")
+# sources and their per-source flags, one "name flags..." line each: leftrefill_amd/build.py (SOURCES, EXTRA)
+srcs=$(python -c "from leftrefill_amd import build
+for s in build.SOURCES: print(s[:-4], *build.EXTRA.get(s, []))")
 objs=""
-for s in $all; do
+while read -r s extra; do
   if [ -n "$VARIANT_SRCS" ] && ! echo " $VARIANT_SRCS " | grep -q " $s "; then objs="$objs leftrefill_amd/build/$s.o"; continue; fi
-  extra=""
-  case $s in attention|attention_bwd|xattn_block|ffn_block|stin_block|rowlin) extra="-mllvm -amdgpu-mfma-vgpr-form";; esac
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value -DLR_DEV_VARIANTS $extra "$@" -c leftrefill_amd/csrc/$s.hip -o /tmp/lrv_$name/$s.o &
   objs="$objs /tmp/lrv_$name/$s.o"
-done
+done <<< "$srcs"
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libleftrefill_hip_$name.so $objs
 echo $out/libleftrefill_hip_$name.so
