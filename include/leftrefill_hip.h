@@ -36,6 +36,7 @@ typedef uint16_t lr_half;  /* 16-bit activation / weight element: IEEE binary16 
 #define LR_PIPE_DEFAULT 0
 #define LR_PIPE_W8_DEEP 4
 #define LR_PIPE_HALO 8
+#define LR_UP_PHASE 3      /* lr_gemm_args.up: the phase form of the nearest-2x upsample conv */
 
 /* ABI version; bump on any signature change. */
 int lr_abi_version(void);
@@ -121,7 +122,15 @@ typedef struct lr_gemm_args {
   int32_t B, H, W;          /* output grid; M = B*H*W */
   int32_t Hs, Ws;           /* source grid */
   int32_t taps, stride, up; /* up: 0 none | 1 nearest 2x | 2 zero-insertion 2x (odd source rows / columns read as 0: with
-                               flipped, transposed weights this is the input gradient of a stride-2 conv) */
+                               flipped, transposed weights this is the input gradient of a stride-2 conv)
+                               | LR_UP_PHASE (3): nearest 2x + 3x3 pad-1 conv as four 2x2 convs on the source, one per output phase
+                               (a, b) = (y & 1, x & 1): taps = 4, wt = [4][N][4 (C1 + C2)] with wt[2a + b][n][(2 dy + dx) (C1 + C2) + c] =
+                               the taps of the 3x3 kernel that read source pixel (i + a - 1 + dy, j + b - 1 + dx), summed
+                               (packing.pack_conv_up_phase); H = 2 Hs, W = 2 Ws, 4/9 of the multiplies of up = 1, results equal up to one
+                               more rounding of the merged weights.  Pipelined tiles only (tile_m 256 with tile_n 128 | 160 | 320,
+                               tile_m 128 with tile_n 128 | 160); bias, rowvec, resid, gn_stats_out (Hs Ws a multiple of the statistics
+                               row block), gn_group_out, split-K.  stride != 1, asym, geglu, ln_stats, stats_out, per-sample or
+                               piece-major weights, skip1, LR_PIPE_HALO: LR_E_UNSUPPORTED */
   int32_t asym;             /* 0: 3x3 pad 1 on every side; 1: pad only bottom/right (F.pad (0,1,0,1) + padding 0, the VAE
                                Downsample, ldm/modules/diffusionmodules/model.py:83-86) */
   const lr_half* wt; int32_t N;      /* weights [N][taps*(C1+C2)] */

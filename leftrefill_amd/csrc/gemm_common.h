@@ -49,6 +49,13 @@ struct GemmParams {
   // in-launch split-K reduce (lr_gemm_args.splitk_mode == 1): per-tile arrival counters (zero on entry, left zero); NULL = the partials
   // are reduced by splitk_reduce_kernel in a second launch
   unsigned* sk_cnt;
+  // phase form of the nearest-2x upsample + 3x3 conv (lr_gemm_args.up == 3): output pixel (2i + a, 2j + b) of phase p = 2a + b is a 2x2 conv
+  // over source pixels (i + a - 1 + dy, j + b - 1 + dx) with the phase's merged weights wt[p][N][4 (C1 + C2)].  The kernel's LOGICAL rows run
+  // over (phase, sample, i, j): phase p owns rows [p * ph_stride, p * ph_stride + ph_rows), ph_rows = B * Hs * Ws, ph_stride = ph_rows padded
+  // to ph_tiles whole row tiles (a tile never spans two phases); the epilogue maps a logical row to its output row, so M, out, resid, rowvec
+  // and the split-K partials keep their ordinary meaning.  (shw_*, sw_*): magic numbers of the divisions by Hs * Ws and by Ws.
+  int phase, ph_rows, ph_tiles, ph_stride;
+  unsigned shw_mul, shw_sh, sw_mul, sw_sh;
 #ifdef LR_GEMM_STAGGER
   int stagger;   // developer build only: shader-clock cycles the SECOND co-resident block of a CU waits before it starts (env LR_GEMM_STAGGER)
 #endif
@@ -80,6 +87,7 @@ __device__ __forceinline__ void tile_order(const GemmParams& P, int bid, int& ti
 }
 
 typedef __attribute__((address_space(3))) void* lptr_t;
+__device__ __forceinline__ unsigned lr_udiv(unsigned n, unsigned mul, unsigned sh);
 
 
 // =====================================================================================================================
@@ -157,7 +165,9 @@ __device__ __forceinline__ constexpr int weight_tile(const int wn, const int j) 
 
 // HALO (conv_halo.hip): the wave's TM row tiles are 16-pixel segments of TM consecutive image lines -- row tile i starts at
 // m_w0 + i * P.W instead of m_w0 + 16 i -- and the row-block index of gs_out is passed in (rb_halo: wave tiles numbered tile-major).
-template <int TM, int TN, int MODE, int PAR_LD, int WNW, typename T, bool HALO = false>
+// PHASE (GemmParams.phase): m_w0 is a LOGICAL row (phase, sample, i, j); every lane row is mapped to its output row (sample, 2i + a, 2j + b)
+// and the statistics row block to (sample, phase, block inside the sample's phase): the blocks of a sample stay contiguous, in a fixed order.
+template <int TM, int TN, int MODE, int PAR_LD, int WNW, typename T, bool HALO = false, bool PHASE = false>
 __device__ __forceinline__ void epilogue_units(const GemmParams& P, f32x4 (&acc)[TN][TM], const int m_w0, const int n0,
                                                const int wn, const int lane, const float* rs, const float* par,
                                                const int part, float* gsl = nullptr, const int rb_halo = 0) {
@@ -180,6 +190,22 @@ __device__ __forceinline__ void epilogue_units(const GemmParams& P, f32x4 (&acc)
   const bool fin = P.splits == 1;
   const unsigned OOB = 0x80000000u;
   const int mstep = HALO ? P.W : 16;      // distance in m between the wave's consecutive 16-row tiles
+  static_assert(!(HALO && PHASE), "the halo-tile kernel takes no upsample convs");
+  [[maybe_unused]] int ph = 0, ph_r0 = 0, ph_rb = 0;      // PHASE (wave-uniform): phase, first row inside the phase, statistics row block
+  if constexpr (PHASE) {
+    ph = m_w0 / P.ph_stride;
+    ph_r0 = m_w0 - ph * P.ph_stride;
+    const int shw = P.Hs * P.Ws, nbs = shw / (TM * 16);      // (statistics are only requested when TM * 16 divides Hs * Ws)
+    const int smp = (int)lr_udiv((unsigned)ph_r0, P.shw_mul, P.shw_sh);
+    ph_rb = (smp * 4 + ph) * nbs + (ph_r0 - smp * shw) / (TM * 16);
+  }
+  // logical row of a phase-form tile -> output row (P.M = none: a tail row of the phase)
+  [[maybe_unused]] auto phase_row = [&](const int ml) -> int {
+    const unsigned r = (unsigned)(ml - ph * P.ph_stride);
+    const unsigned b = lr_udiv(r, P.shw_mul, P.shw_sh), rem = r - b * (unsigned)(P.Hs * P.Ws);
+    const unsigned i = lr_udiv(rem, P.sw_mul, P.sw_sh), j = rem - i * (unsigned)P.Ws;
+    return r < (unsigned)P.ph_rows ? (int)(b * (unsigned)(P.H * P.W) + (2 * i + (ph >> 1)) * (unsigned)P.W + 2 * j + (ph & 1)) : P.M;
+  };
   const __amdgpu_buffer_rsrc_t rsR = uniform_rsrc(P.resid ? (const void*)P.resid : (const void*)P.out,
                                                   (P.resid && fin) ? ((size_t)(P.M - 1) * P.ld_resid + N_out) * 2 : 0);
   const __amdgpu_buffer_rsrc_t rsV = uniform_rsrc(P.rowvec ? (const void*)P.rowvec : (const void*)P.out,
@@ -211,7 +237,7 @@ __device__ __forceinline__ void epilogue_units(const GemmParams& P, f32x4 (&acc)
     return v;
   };
   auto flush_group = [&](const int n_lane, const bool pair_fq) {
-    const int rb = HALO ? rb_halo : m_w0 / (TM * 16);
+    const int rb = HALO ? rb_halo : PHASE ? ph_rb : m_w0 / (TM * 16);
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       float a = row16_sum(g1(q)), b = row16_sum(g2(q));
@@ -224,7 +250,7 @@ __device__ __forceinline__ void epilogue_units(const GemmParams& P, f32x4 (&acc)
       g1(q) = a; g2(q) = b;
     }
     if (fr == 0 && (!pair_fq || !odd) && n_lane < N_out) {
-      if (P.gs_out != nullptr && m_w0 < P.M) {
+      if (P.gs_out != nullptr && (PHASE ? ph_r0 < P.ph_rows : m_w0 < P.M)) {
         float* dst = P.gs_out + ((size_t)rb * N_out + n_lane) * 2;
 #pragma unroll
         for (int q = 0; q < 8; q += 2) {
@@ -280,12 +306,14 @@ __device__ __forceinline__ void epilogue_units(const GemmParams& P, f32x4 (&acc)
       m = m_w0 + (2 * ip + odd) * mstep + fr;
       n = no0 + emit_tile<TE, WNW>(wn, TE - 1) * 16 + ch8;
     }
+    if constexpr (PHASE) m = phase_row(m);
   };
   // sample index of row m for the per-sample row vector: one division per wave, then boundary compares
   const int b_w0 = P.rowvec ? m_w0 / P.rows_per_batch : 0;
   const bool has_res = P.resid != nullptr && fin;
   const bool both = has_res && P.rowvec != nullptr;
   auto rowvec_offset = [&](const int m, const int n, const bool ok) -> unsigned {
+    if constexpr (PHASE) return ok ? (unsigned)(((size_t)lr_udiv((unsigned)m, P.hw_mul, P.hw_sh) * P.ld_rowvec + n) * 2) : OOB;
     int b = b_w0;
     for (int lim = (b_w0 + 1) * P.rows_per_batch; m >= lim; lim += P.rows_per_batch) ++b;
     return ok ? (unsigned)(((size_t)b * P.ld_rowvec + n) * 2) : OOB;
@@ -411,10 +439,12 @@ __device__ __forceinline__ void epilogue_units(const GemmParams& P, f32x4 (&acc)
 
 // Per-group sums of a tile from the per-channel sums its waves left in LDS: gsl[row block][BN_][2] -> gp_out.  One thread
 // per group of the tile, fixed order (row blocks outer, channels inner).  Called by all threads after a block-wide barrier.
-template <int BN_, int NROWBLK, int BM_>
+// PHASE: m0 is a logical row (see GemmParams.phase); chunk = (phase, tile inside the sample's phase), gp_chunks = 4 Hs Ws / BM_ = H W / BM_.
+template <int BN_, int NROWBLK, int BM_, bool PHASE = false>
 __device__ __forceinline__ void gn_group_reduce(const GemmParams& P, const float* gsl, const int m0, const int n0, const int t) {
   const int cg = P.gp_cg;
-  if (t < BN_ / cg && m0 < P.M) {
+  [[maybe_unused]] const int ph = PHASE ? m0 / P.ph_stride : 0, ph_r0 = PHASE ? m0 - ph * P.ph_stride : 0;
+  if (t < BN_ / cg && (PHASE ? ph_r0 < P.ph_rows : m0 < P.M)) {
     const int g = n0 / cg + t;
     if (g < 32) {
       float s = 0.f, q = 0.f;
@@ -422,7 +452,12 @@ __device__ __forceinline__ void gn_group_reduce(const GemmParams& P, const float
         const float2* src = reinterpret_cast<const float2*>(gsl) + rb * BN_ + t * cg;
         for (int c = 0; c < cg; ++c) { const float2 v = src[c]; s += v.x; q += v.y; }
       }
-      const int smp = m0 / P.gp_hw, chunk = (m0 - smp * P.gp_hw) / BM_;
+      int smp = m0 / P.gp_hw, chunk = (m0 - smp * P.gp_hw) / BM_;
+      if constexpr (PHASE) {
+        const int shw = P.Hs * P.Ws;
+        smp = ph_r0 / shw;
+        chunk = ph * (shw / BM_) + (ph_r0 - smp * shw) / BM_;
+      }
       float2 o; o.x = s; o.y = q;
       *reinterpret_cast<float2*>(P.gp_out + (((size_t)smp * P.gp_chunks + chunk) * 32 + g) * 2) = o;
     }

@@ -247,7 +247,9 @@ __global__ __launch_bounds__(GEMM_THREADS, BN == 64 ? 4 : BN == 128 ? 3 : 2) voi
 //                        32 x BN/2) give every SIMD two waves to overlap ds_reads, LDS-DMA issue and MFMAs -- with the
 //                        2-stage ring of gemm_conv_kernel every K-step of these shapes waits out a full memory latency,
 //                        and a 4-wave version of this instance spent 2080 cycles per K-step for 680 cycles of MFMA.
-template <int BM2, int NW, int BN, int WMW, int NSTAGE, int MODE, typename T>
+// PH: the phase form of the nearest-2x upsample conv (GemmParams.phase): the row tiles run over (phase, sample, source pixel), the gather reads
+// the phase's 2 x 2 source taps against Hs x Ws, the weights are the phase's [N][4 C] slice and the epilogue scatters to output rows.
+template <int BM2, int NW, int BN, int WMW, int NSTAGE, int MODE, typename T, bool PH = false>
 __global__ __launch_bounds__(NW * 64) void gemm_conv_pipe_kernel(const GemmParams P) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int WNW = NW / WMW;
@@ -289,6 +291,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_conv_pipe_kernel(const GemmParam
   const int slot = lane & 7;
   const unsigned OOB = 0x80000000u;
   int tile_m = 0, tile_n = 0, m0 = 0, n0 = 0, smp = 0;
+  [[maybe_unused]] int ph = 0;      // PH: the tile's phase (2 a + b); its first row inside the phase is m0 - ph * P.ph_stride
   unsigned wvo[NB_FULL + 1];      // weight rows (fixed over K): instr i covers rows (i*NW + w)*8 + lane/8
   // gather state: per-row byte offset of the current (tap, source) segment, recomputed only when the tap or the concat
   // source changes
@@ -314,6 +317,10 @@ __global__ __launch_bounds__(NW * 64) void gemm_conv_pipe_kernel(const GemmParam
     seg_tap = -1; seg_src = -1;
     smp = P.wt_bstride ? m0 / P.rows_per_batch : 0;      // per-sample weights: the tile lies inside one sample
     rsB = uniform_rsrc(P.wt + (size_t)smp * P.wt_bstride, (size_t)P.N * P.K * 2);
+    if constexpr (PH) {
+      ph = tile_m / P.ph_tiles;
+      rsB = uniform_rsrc(P.wt + (size_t)ph * P.N * P.K, (size_t)P.N * P.K * 2);
+    }
   };
   const int Hlim = P.Hs << P.up, Wlim = P.Ws << P.up;
   const int cpt = P.c16 ? 1 : (P.C1 + P.C2) >> 6;
@@ -387,6 +394,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_conv_pipe_kernel(const GemmParam
       seg_tap = tap; seg_src = srcsel;
       int dy = 0, dx = 0;
       if (P.taps == 9 && tap < 9) { dy = tap / 3 - P.pad; dx = tap - (tap / 3) * 3 - P.pad; }
+      if constexpr (PH) { dy = (tap >> 1) + (ph >> 1) - 1; dx = (tap & 1) + (ph & 1) - 1; }
       const int cs = srcsel == 0 ? P.C1 : srcsel == 1 ? P.C2 : srcsel == 2 ? P.C3 : P.C4;
       rsA = srcsel == 0 ? uniform_rsrc((const void*)P.p1, a1_bytes) : srcsel == 1 ? uniform_rsrc((const void*)P.p2, a2_bytes)
           : srcsel == 2 ? uniform_rsrc((const void*)P.p3, a3_bytes) : uniform_rsrc((const void*)P.p4, a4_bytes);
@@ -395,6 +403,16 @@ __global__ __launch_bounds__(NW * 64) void gemm_conv_pipe_kernel(const GemmParam
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
         const int row = (i * NW + w) * 8 + (lane >> 3);
+        if constexpr (PH) {      // source pixel (y + dy, x + dx) of the row's own sample: bounds against Hs x Ws, a tail row of the phase reads zeros
+          const unsigned r = (unsigned)(m0 - ph * P.ph_stride + row);
+          const unsigned b = lr_udiv(r, P.shw_mul, P.shw_sh), rem = r - b * (unsigned)(P.Hs * P.Ws);
+          const unsigned y = lr_udiv(rem, P.sw_mul, P.sw_sh), x = rem - y * (unsigned)P.Ws;
+          const int iy = (int)y + dy, ix = (int)x + dx;
+          const bool ok = r < (unsigned)P.ph_rows && (unsigned)iy < (unsigned)P.Hs && (unsigned)ix < (unsigned)P.Ws;
+          const int chunk = slot ^ ((row >> 1) & 7);
+          avo[i] = ok ? (unsigned)(((size_t)((int)b * P.Hs * P.Ws + iy * P.Ws + ix) * cs + chunk * 8) * 2) : OOB;
+          continue;
+        }
         const unsigned m = (unsigned)(m0 + row);
         const unsigned b = lr_udiv(m, P.hw_mul, P.hw_sh), rem = m - b * (unsigned)HW;
         const unsigned y = lr_udiv(rem, P.w_mul, P.w_sh), x = rem - y * (unsigned)P.W;
@@ -590,13 +608,13 @@ __global__ __launch_bounds__(NW * 64) void gemm_conv_pipe_kernel(const GemmParam
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
     }
-    epilogue_units<TM, TN, MODE, PAR_LD, WNW, T>(P, acc, m0 + wm * (TM * 16), n0, wn, lane, rs + 2 * (wm * TM * 16), par,
-                                              tile_n * WNW + wn, gsl + wm * (BN * 2));
+    epilogue_units<TM, TN, MODE, PAR_LD, WNW, T, false, PH>(P, acc, m0 + wm * (TM * 16), n0, wn, lane, rs + 2 * (wm * TM * 16), par,
+                                                         tile_n * WNW + wn, gsl + wm * (BN * 2));
     if constexpr (MODE == 0) {
       if (gp) {      // only the LDS writes of the per-channel sums have to be visible: the epilogue's global stores stay in flight
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        gn_group_reduce<BN, WMW, BM2>(P, gsl, m0, n0, t);
+        gn_group_reduce<BN, WMW, BM2, PH>(P, gsl, m0, n0, t);
       }
     }
 #ifdef LR_DEV_VARIANTS
@@ -617,11 +635,16 @@ __global__ __launch_bounds__(NW * 64) void gemm_conv_pipe_kernel(const GemmParam
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
-template <int BM2, int NW, int BN, int WMW, int NSTAGE, int MODE, typename T>
+template <int BM2, int NW, int BN, int WMW, int NSTAGE, int MODE, typename T, bool PH = false>
 static int launch_pipe_t(const GemmParams& P0, hipStream_t st) {
   GemmParams P = P0;
   P.ntiles_n = (P.N + BN - 1) / BN;
-  const int ntm = (P.M + BM2 - 1) / BM2;
+  int ntm = (P.M + BM2 - 1) / BM2;
+  if constexpr (PH) {      // four phases of ph_tiles row tiles each: no tile spans two phases
+    P.ph_tiles = (P.ph_rows + BM2 - 1) / BM2;
+    P.ph_stride = P.ph_tiles * BM2;
+    ntm = 4 * P.ph_tiles;
+  }
   P.ntiles_m = ntm;
   // Tile order inside an XCD's contiguous range (round 5): panels of G row tiles, m-fastest inside a panel, so that the ~32 tiles an XCD
   // runs at once (one 8-wave block per CU) are G x (32 / G) row / column slices instead of 2 x 16 (n-fastest) -- wide-N GEMMs whose
@@ -647,11 +670,11 @@ static int launch_pipe_t(const GemmParams& P0, hipStream_t st) {
   const size_t smem = NSTAGE * (size_t)(BM2 + BN) * 128 + BM2 * 2 * sizeof(float) + 2 * (((BN + 63) / 64) * 64) * sizeof(float);
   static unsigned long long attr_done = 0;
   if (lr_attr_needed(&attr_done)) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_conv_pipe_kernel<BM2, NW, BN, WMW, NSTAGE, MODE, T>),
+    hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_conv_pipe_kernel<BM2, NW, BN, WMW, NSTAGE, MODE, T, PH>),
                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   }
   const int gx = P.nblocks;
-  hipLaunchKernelGGL((gemm_conv_pipe_kernel<BM2, NW, BN, WMW, NSTAGE, MODE, T>), dim3(gx, P.splits), dim3(NW * 64), smem, st, P);
+  hipLaunchKernelGGL((gemm_conv_pipe_kernel<BM2, NW, BN, WMW, NSTAGE, MODE, T, PH>), dim3(gx, P.splits), dim3(NW * 64), smem, st, P);
   return lr_launch_status();
 }
 
@@ -796,10 +819,10 @@ static int launch_gemm_t(const GemmParams& P0, hipStream_t st) {
 }
 
 // dtype dispatch (fp16 | bf16; the erf-GELU mode of the text tower is fp16 only)
-template <int BM2, int NW, int BN, int WMW, int NSTAGE, int MODE>
+template <int BM2, int NW, int BN, int WMW, int NSTAGE, int MODE, bool PH = false>
 static int launch_pipe(const GemmParams& P, hipStream_t st) {
-  if constexpr (MODE != 2) { if (P.bf16) return launch_pipe_t<BM2, NW, BN, WMW, NSTAGE, MODE, bf16>(P, st); }
-  return launch_pipe_t<BM2, NW, BN, WMW, NSTAGE, MODE, f16>(P, st);
+  if constexpr (MODE != 2) { if (P.bf16) return launch_pipe_t<BM2, NW, BN, WMW, NSTAGE, MODE, bf16, PH>(P, st); }
+  return launch_pipe_t<BM2, NW, BN, WMW, NSTAGE, MODE, f16, PH>(P, st);
 }
 template <int BN, int WMW, int NSTAGE, int MODE>
 static int launch_gemm256(const GemmParams& P, hipStream_t st) { return launch_pipe<256, 8, BN, WMW, NSTAGE, MODE>(P, st); }
@@ -819,9 +842,16 @@ static int launch_reduce(const GemmParams& P, hipStream_t st) {
 
 // split-K heuristic: only when the tile grid cannot fill the chip (256 CUs x 2 resident blocks) and K is long.
 // geglu: the GEGLU / erf-GELU epilogue modes, which are not instantiated for the 160-column tiles
-static void choose_tile(int M, int N, int geglu, int* tm, int* tn) {
+// phase: the phase form of the upsample conv (lr_gemm_args.up == LR_UP_PHASE) -- only the pipelined instances gather it: 256-row tiles where
+// they fill the chip, else the 8-wave 128-row ones (plan_pipe)
+static void choose_tile(int M, int N, int geglu, int* tm, int* tn, bool phase = false) {
   // explicit requests win; otherwise: the 256-row 8-wave kernel for large M when BN divides N, else the 128-row one
-  if (*tm == 0 && *tn == 0) {
+  if (phase) {
+    // (in-step timings, profiles/up_phase_ab.txt: 256 x 320 where those tiles fill the chip, else 160 columns; 128 rows for the small levels)
+    if (*tn == 0 && *tm != 128 && N % 320 == 0 && ((M + 255) / 256) * (N / 320) >= 224) *tn = 320;
+    if (*tn == 0) *tn = N % 160 == 0 ? 160 : 128;
+    if (*tm == 0) *tm = ((M + 255) / 256) * ((N + *tn - 1) / *tn) >= 224 ? 256 : 128;
+  } else if (*tm == 0 && *tn == 0) {
     // static fallback (the Python front end normally autotunes): the 256-row kernel needs >= ~1 block per CU
     const int t160 = ((M + 255) / 256) * ((N + 159) / 160), t128 = ((M + 255) / 256) * ((N + 127) / 128);
     if (!geglu && N % 160 == 0 && t160 >= 224) { *tm = 256; *tn = 160; }
@@ -866,6 +896,10 @@ static int choose_stages(int tm, int tn, int stages) {
   return (tn == 128 || tn == 160) ? 3 : 2;
 }
 
+static bool is_phase(const lr_gemm_args* a) { return a->up == LR_UP_PHASE; }
+// lr_gemm_args.pipe as planned: the 128-row tiles of the phase form always run on the 8-wave 4-stage instance
+static int plan_pipe(const lr_gemm_args* a, int tm) { return (is_phase(a) && tm == 128 && a->pipe == 0) ? 4 : a->pipe; }
+
 // waves along N of the instance that serves tile (tm, tn): each writes one (sum, sumsq) partial per row
 static int tile_wnw(int tm, int tn, int geglu) {
   if (tm == 128) return 2;
@@ -879,10 +913,10 @@ extern "C" int lr_gemm_plan(const lr_gemm_args* a, int32_t* plan) {
   const int M = a->B * a->H * a->W;
   const int K = a->taps * (a->C1 + (a->p2 ? a->C2 : 0)) + (a->skip1 ? a->Cs1 + (a->skip2 ? a->Cs2 : 0) : 0);
   int tn = a->tile_n, tm = a->tile_m;
-  choose_tile(M, a->N, a->geglu != 0, &tm, &tn);
+  choose_tile(M, a->N, a->geglu != 0, &tm, &tn, is_phase(a));
   plan[0] = tm; plan[1] = tn;
-  plan[2] = a->splits ? a->splits : choose_splits(M, a->N, K, tm, tn, a->geglu == 1, a->pipe);
-  plan[3] = choose_stages(tm, tn, a->pipe);
+  plan[2] = a->splits ? a->splits : choose_splits(M, a->N, K, tm, tn, a->geglu == 1, plan_pipe(a, tm));
+  plan[3] = choose_stages(tm, tn, plan_pipe(a, tm));
   return 0;
 }
 
@@ -898,11 +932,11 @@ extern "C" int lr_gemm_gn_rows(const lr_gemm_args* a) {
   if (!a) return 0;
   int tn = a->tile_n, tm = a->tile_m;
   const int M = a->B * a->H * a->W;
-  choose_tile(M, a->N, a->geglu != 0, &tm, &tn);
+  choose_tile(M, a->N, a->geglu != 0, &tm, &tn, is_phase(a));
   const int K = a->taps * (a->C1 + (a->p2 ? a->C2 : 0)) + (a->skip1 ? a->Cs1 + (a->skip2 ? a->Cs2 : 0) : 0);
-  const int splits = a->splits ? a->splits : choose_splits(M, a->N, K, tm, tn, a->geglu == 1, a->pipe);
+  const int splits = a->splits ? a->splits : choose_splits(M, a->N, K, tm, tn, a->geglu == 1, plan_pipe(a, tm));
   if (splits > 1) return RED_ROWS;     // the statistics come out of the split-K reduce kernel
-  return tile_wave_rows(tm, tn, a->geglu == 1, a->pipe);
+  return tile_wave_rows(tm, tn, a->geglu == 1, plan_pipe(a, tm));
 }
 
 // chunks per sample of gn_group_out for this call (0: the plan cannot produce per-group sums -- tile width not a whole number
@@ -916,6 +950,8 @@ static int gn_group_chunks(const lr_gemm_args* a, int tm, int tn, int splits) {
   const int rows = splits > 1 ? RED_ROWS : tm;
   const int width = splits > 1 ? 8 * RED_GROUPS : tn;
   if (width % cg || hw % rows) return 0;
+  // phase form: a row tile holds source pixels of ONE phase; it must also lie inside one sample (the chunks of a sample: 4 phases x Hs Ws / rows)
+  if (is_phase(a) && (hw != a->H * a->W || (splits == 1 && (a->Hs * a->Ws) % rows))) return 0;
   return hw / rows;
 }
 
@@ -923,16 +959,16 @@ extern "C" int lr_gemm_gn_group_chunks(const lr_gemm_args* a) {
   if (!a) return 0;
   int tn = a->tile_n, tm = a->tile_m;
   const int M = a->B * a->H * a->W;
-  choose_tile(M, a->N, a->geglu != 0, &tm, &tn);
+  choose_tile(M, a->N, a->geglu != 0, &tm, &tn, is_phase(a));
   const int K = a->taps * (a->C1 + (a->p2 ? a->C2 : 0)) + (a->skip1 ? a->Cs1 + (a->skip2 ? a->Cs2 : 0) : 0);
-  const int splits = a->splits ? a->splits : choose_splits(M, a->N, K, tm, tn, a->geglu == 1, a->pipe);
+  const int splits = a->splits ? a->splits : choose_splits(M, a->N, K, tm, tn, a->geglu == 1, plan_pipe(a, tm));
   return gn_group_chunks(a, tm, tn, splits);
 }
 
 extern "C" int lr_gemm_stats_parts(const lr_gemm_args* a) {
   if (!a) return 0;
   int tn = a->tile_n, tm = a->tile_m;
-  choose_tile(a->B * a->H * a->W, a->N, a->geglu != 0, &tm, &tn);
+  choose_tile(a->B * a->H * a->W, a->N, a->geglu != 0, &tm, &tn, is_phase(a));
   return ((a->N + tn - 1) / tn) * tile_wnw(tm, tn, a->geglu == 1);
 }
 
@@ -941,8 +977,8 @@ extern "C" int64_t lr_gemm_workspace_bytes(const lr_gemm_args* a) {
   const int M = a->B * a->H * a->W;
   const int K = a->taps * (a->C1 + (a->p2 ? a->C2 : 0)) + (a->skip1 ? a->Cs1 + (a->skip2 ? a->Cs2 : 0) : 0);
   int tn = a->tile_n, tm = a->tile_m;
-  choose_tile(M, a->N, a->geglu != 0, &tm, &tn);
-  int splits = a->splits ? a->splits : choose_splits(M, a->N, K, tm, tn, a->geglu == 1, a->pipe);
+  choose_tile(M, a->N, a->geglu != 0, &tm, &tn, is_phase(a));
+  int splits = a->splits ? a->splits : choose_splits(M, a->N, K, tm, tn, a->geglu == 1, plan_pipe(a, tm));
   return splits > 1 ? (int64_t)splits * M * a->N * (int64_t)sizeof(float) : 0;
 }
 
@@ -978,12 +1014,21 @@ extern "C" int lr_gemm_conv_f16(const lr_gemm_args* a, lr_stream_t s) {
   P.p2 = (const f16*)a->p2; P.C2 = a->p2 ? a->C2 : 0;
   P.c16 = (P.C1 == 16 && P.C2 == 0 && a->taps == 9 && a->stride == 1 && a->up == 0 && !a->asym) ? 1 : 0;
   if (P.C1 <= 0 || (!P.c16 && P.C1 % 64) || P.C2 % 64) return LR_E_ALIGN;
-  if (a->taps != 1 && a->taps != 9) return LR_E_UNSUPPORTED;
+  const bool phase = is_phase(a);
+  if (a->taps != 1 && a->taps != 9 && !(phase && a->taps == 4)) return LR_E_UNSUPPORTED;
   if (a->stride != 1 && a->stride != 2) return LR_E_UNSUPPORTED;
-  if (a->up < 0 || a->up > 2) return LR_E_UNSUPPORTED;
+  if (a->up < 0 || a->up > LR_UP_PHASE) return LR_E_UNSUPPORTED;
+  // phase form: wt = [4][N][4 (C1 + C2)], a plain stride-1 pad-1 conv epilogue (bias, row vector, residual, GroupNorm statistics, split-K)
+  if (phase && (a->taps != 4 || a->stride != 1 || a->asym || a->geglu || a->ln_stats || a->stats_out || a->wt_bstride || a->wt_pm || a->skip1 ||
+                a->pipe == LR_PIPE_HALO || a->splitk_mode != 0 || a->H != 2 * a->Hs || a->W != 2 * a->Ws ||
+                (a->gn_hw > 0 && a->gn_hw != a->H * a->W)))
+    return LR_E_UNSUPPORTED;
   if (a->B <= 0 || a->H <= 0 || a->W <= 0 || a->Hs <= 0 || a->Ws <= 0 || a->N <= 0) return LR_E_ARG;
   P.H = a->H; P.W = a->W; P.Hs = a->Hs; P.Ws = a->Ws;
-  P.taps = a->taps; P.stride = a->stride; P.up = a->up;
+  P.taps = a->taps; P.stride = a->stride; P.up = phase ? 0 : a->up;
+  P.phase = phase ? 1 : 0; P.ph_rows = a->B * a->Hs * a->Ws; P.ph_tiles = 0; P.ph_stride = 0;      // (tiles / stride: set by the launcher)
+  lr_udiv_magic((unsigned)(a->Hs * a->Ws), &P.shw_mul, &P.shw_sh);
+  lr_udiv_magic((unsigned)a->Ws, &P.sw_mul, &P.sw_sh);
   P.zins = (a->up == 2) ? 1 : 0;      // up == 2: zero-insertion upsample (dgrad of a stride-2 conv)
   if (P.zins) P.up = 1;
   P.pad = a->asym ? 0 : 1;   // asym: F.pad(x, (0,1,0,1)) + conv padding 0 (VAE Downsample)
@@ -1002,7 +1047,7 @@ extern "C" int lr_gemm_conv_f16(const lr_gemm_args* a, lr_stream_t s) {
   const int64_t lim = (int64_t)1 << 31;
   const int64_t src_rows = (int64_t)a->B * a->Hs * a->Ws;
   if (src_rows * P.C1 * 2 >= lim || src_rows * P.C2 * 2 >= lim || src_rows * P.C3 * 2 >= lim || src_rows * P.C4 * 2 >= lim ||
-      (int64_t)P.N * P.K * 2 >= lim ||
+      (int64_t)P.N * P.K * 2 * (phase ? 4 : 1) >= lim ||
       (int64_t)a->B * a->H * a->W >= lim / 2)
     return LR_E_UNSUPPORTED;
   P.rowvec = (const f16*)a->rowvec; P.ld_rowvec = a->ld_rowvec;
@@ -1026,13 +1071,14 @@ extern "C" int lr_gemm_conv_f16(const lr_gemm_args* a, lr_stream_t s) {
        (uintptr_t)P.rowvec | (uintptr_t)P.bias) & 15)
     return LR_E_ALIGN;
   int tn = a->tile_n, tm = a->tile_m;
-  choose_tile(P.M, P.N, P.geglu || P.gelu, &tm, &tn);
+  choose_tile(P.M, P.N, P.geglu || P.gelu, &tm, &tn, phase);
+  const int pipe = plan_pipe(a, tm);
   int splits = a->splits;
   if (P.c16) {      // only the pipelined 256-row instances gather 16-channel taps; three K-steps: never split
     if (tm != 256 || (a->splits > 1) || P.geglu || P.gelu || a->wt_bstride) return LR_E_UNSUPPORTED;
     splits = 1;
   }
-  if (splits == 0) splits = choose_splits(P.M, P.N, P.K, tm, tn, P.geglu, a->pipe);
+  if (splits == 0) splits = choose_splits(P.M, P.N, P.K, tm, tn, P.geglu, pipe);
   if (splits > 1 && P.geglu) return LR_E_UNSUPPORTED;
   if (splits > 1) {
     const int64_t need = (int64_t)splits * P.M * P.N * (int64_t)sizeof(float);
@@ -1067,6 +1113,8 @@ extern "C" int lr_gemm_conv_f16(const lr_gemm_args* a, lr_stream_t s) {
   P.gs_out = a->gn_stats_out;
   if (P.gs_out && (P.geglu || ((uintptr_t)P.gs_out & 15))) return LR_E_ARG;
   P.gs_store = P.gs_out != nullptr;
+  // phase form, statistics from the epilogue: a wave's row block must lie inside one sample of one phase
+  if (phase && P.gs_out && splits == 1 && (a->Hs * a->Ws) % tile_wave_rows(tm, tn, 0, pipe)) return LR_E_ARG;
   P.gp_out = a->gn_group_out; P.gp_cg = 1; P.gp_chunks = 0; P.gp_hw = 1;
   if (P.gp_out) {
     P.gp_chunks = gn_group_chunks(a, tm, tn, splits);
@@ -1088,8 +1136,8 @@ extern "C" int lr_gemm_conv_f16(const lr_gemm_args* a, lr_stream_t s) {
   hipStream_t st = (hipStream_t)s;
   int rc;
   const int mode = P.geglu ? 1 : P.gelu ? 2 : 0;
-  if (a->pipe != 0 && a->pipe != choose_stages(tm, tn, a->pipe)) return LR_E_UNSUPPORTED;
-  const bool deep = tm == 128 && choose_stages(tm, tn, a->pipe) == 4;
+  if (pipe != 0 && pipe != choose_stages(tm, tn, pipe)) return LR_E_UNSUPPORTED;
+  const bool deep = tm == 128 && choose_stages(tm, tn, pipe) == 4;
 #ifdef LR_DEV_VARIANTS
   // in-launch split-K reduce: the 8-wave instances with 160- / 320-column tiles, the whole grid resident at once (one block per CU)
   if (P.splits > 1 && a->splitk_mode == 1 && mode != 1 && (tn == 160 || tn == 320) && (tm == 256 || deep || a->pipe == LR_PIPE_HALO)) {
@@ -1104,7 +1152,14 @@ extern "C" int lr_gemm_conv_f16(const lr_gemm_args* a, lr_stream_t s) {
     if (rc || P.splits == 1 || P.sk_cnt) return rc;
     return launch_reduce(P, st);
   }
-  if (mode == 0) {
+  if (phase) {      // the pipelined instances with the phase gather (gemm_conv_pipe_kernel<.., PH = true>)
+    if (deep && tn == 128) rc = launch_pipe<128, 8, 128, 4, 4, 0, true>(P, st);
+    else if (deep && tn == 160) rc = launch_pipe<128, 8, 160, 4, 4, 0, true>(P, st);
+    else if (tm == 256 && tn == 128) rc = launch_pipe<256, 8, 128, 4, 3, 0, true>(P, st);
+    else if (tm == 256 && tn == 160) rc = launch_pipe<256, 8, 160, 4, 3, 0, true>(P, st);
+    else if (tm == 256 && tn == 320) rc = launch_pipe<256, 8, 320, 2, 2, 0, true>(P, st);
+    else return LR_E_UNSUPPORTED;
+  } else if (mode == 0) {
     if (deep && tn == 128) rc = launch_pipe<128, 8, 128, 4, 4, 0>(P, st);
     else if (deep && tn == 160) rc = launch_pipe<128, 8, 160, 4, 4, 0>(P, st);
 

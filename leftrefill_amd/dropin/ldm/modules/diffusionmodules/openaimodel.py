@@ -318,7 +318,7 @@ class UNetModel(nn.Module):
                 elif isinstance(layer, Downsample):
                     steps.append(("down", E.PackedConv(layer.op)))
                 elif isinstance(layer, Upsample):
-                    steps.append(("up", E.PackedConv(layer.conv)))
+                    steps.append(("up", E.PackedConv(layer.conv, up_phase=True)))
                 elif isinstance(layer, nn.Conv2d):
                     steps.append(("conv", E.PackedConv(layer, cin_pad=cin_pad)))
                 else:

@@ -78,8 +78,12 @@ def f32(p):
 # packed parameter records
 # ---------------------------------------------------------------------------------------------------------------
 class PackedConv:
-    def __init__(self, conv, cin_pad=None):
+    """up_phase: the conv of an Upsample layer -- its phase-form weights (packing.pack_conv_up_phase) are packed next to the 9-tap ones,
+    which the differentiable forward keeps using."""
+
+    def __init__(self, conv, cin_pad=None, up_phase=False):
         w = conv.weight.detach()
+        self.wp = packing.pack_conv_up_phase(w, cin_pad=cin_pad, dtype=compute_dtype()) if up_phase and w.shape[2:] == (3, 3) else None
         self.cout = w.shape[0]
         self.taps = w.shape[2] * w.shape[3]
         self.w = packing.pack_conv(w, cin_pad=cin_pad, dtype=compute_dtype())
@@ -317,6 +321,12 @@ def forking(x):
     return TRAIN_FORK and training(x)
 
 
+# Upsample convs in the phase form (lr_gemm_args.up = 3); LEFTREFILL_UP_PHASE=0 keeps up = 1 everywhere.  All three Upsample convs of the UNet
+# are faster in it inside the step (profiles/up_phase_ab.txt), so the choice does not depend on the shape: every process, rank and batch size
+# takes the same form (the two forms differ in rounding).
+UP_PHASE = __import__("os").environ.get("LEFTREFILL_UP_PHASE", "1") != "0"
+
+
 def conv(act: Act, pc: PackedConv, rowvec=None, resid=None, up=0, asym=False, gn_stats=False, skip=None, skip_parts=None):
     """3x3 pad-1 conv (stride 1|2, optional nearest-2x upsample; asym: pad bottom/right only) or 1x1 conv over an Act.
     gn_stats: the output feeds a GroupNorm -- let the epilogue produce its statistics (Act.gs).
@@ -332,7 +342,12 @@ def conv(act: Act, pc: PackedConv, rowvec=None, resid=None, up=0, asym=False, gn
         H, W = act.H, act.W
     want = gn_stats and gn_stats_ok(act.tok) and pc.cout == pc.w.shape[0]
     extra = {} if skip_parts is None else {"skip_parts": skip_parts}      # (training: the two layers of a skip-extended conv, for its backward)
-    y = ops.gemm_conv(act.tok, pc.w, B=act.N, H=H, W=W, Hs=act.H, Ws=act.W, taps=pc.taps, stride=pc.stride, up=up,
+    w, taps = pc.w, pc.taps
+    if (up == 1 and UP_PHASE and getattr(pc, "wp", None) is not None and not asym and skip is None
+            and not (training(act.tok) or (act.tok2 is not None and training(act.tok2)) or (resid is not None and training(resid)))):
+        # inference: nearest-2x + 3x3 as four 2x2 convs on the source (4/9 of the multiplies); the differentiable forward keeps up = 1
+        w, taps, up = pc.wp, 4, 3
+    y = ops.gemm_conv(act.tok, w, B=act.N, H=H, W=W, Hs=act.H, Ws=act.W, taps=taps, stride=pc.stride, up=up,
                       asym=asym, x2=act.tok2, bias=pc.b, rowvec=rowvec, resid=resid, want_gn_stats=want, skip=skip, **extra)
     y, gs = y if want else (y, None)
     return Act(y, act.N, H, W, gs=gs)

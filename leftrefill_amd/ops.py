@@ -273,7 +273,9 @@ def gemm_conv(x1, wt, *, B, H, W, Hs=None, Ws=None, taps=1, stride=1, up=0, asym
     returns (out, (partials [M / R, N, 2] fp32, R, gp, chunks)), or (out, None) when R does not divide the rows of a sample
     (gn_hw, default H*W); gp [samples, chunks, 32, 2] = per-GROUP sums for a consumer that normalises this tensor alone
     (group_norm_groups: no finalize launch), None when the plan cannot produce them.
-    per_sample: wt is [B, N, K] and bias [B, N] -- one weight set per sample (rows b*H*W .. of sample b), see ops.gn_fold_weights."""
+    per_sample: wt is [B, N, K] and bias [B, N] -- one weight set per sample (rows b*H*W .. of sample b), see ops.gn_fold_weights.
+    up = 3, taps = 4: the phase form of the nearest-2x upsample + 3x3 conv -- wt is [4, N, 4 (C1 + C2)] (packing.pack_conv_up_phase), B / H / W
+    the output grid and Hs / Ws the source grid as for up = 1; pipelined tiles only."""
     lib = _lib.load()
     _chk16(x1, "x1")
     _chk16(wt, "wt")
@@ -284,6 +286,8 @@ def gemm_conv(x1, wt, *, B, H, W, Hs=None, Ws=None, taps=1, stride=1, up=0, asym
     if x2 is not None:
         _chk16(x2, "x2")
         C2 = x2.shape[-1]
+    if up == 3:
+        assert wt.dim() == 3 and wt.shape[0] == 4 and wt.is_contiguous() and taps == 4 and H == 2 * Hs and W == 2 * Ws and not per_sample and not wt_pm
     if per_sample:
         assert wt.dim() == 3 and wt.shape[0] == B and taps == 1 and x2 is None and wt.is_contiguous() and not wt_pm
     if wt_pm:      # piece-major weights [K / 64, N, 64] (packing.pack_pm)
@@ -392,7 +396,8 @@ def gemm_conv(x1, wt, *, B, H, W, Hs=None, Ws=None, taps=1, stride=1, up=0, asym
         a.splits = plan[2]                  # pinned: the row-block size of the statistics depends on it (32 behind split-K)
         rows = lib.lr_gemm_gn_rows(a)
         hw = gn_hw or H * W
-        if hw % rows == 0:                  # row blocks never straddle two samples
+        # (phase form, statistics from the epilogue: the row blocks hold source pixels of one phase -- they must divide a sample's Hs * Ws)
+        if (Hs * Ws if up == 3 and a.splits == 1 else hw) % rows == 0:                  # row blocks never straddle two samples
             chunks = lib.lr_gemm_gn_group_chunks(a) if GN_GROUPS else 0
             gp = torch.empty(M // hw, chunks, 32, 2, device=x1.device, dtype=torch.float32) if chunks > 0 else None
             gstats = (torch.empty((M + rows - 1) // rows, n_out, 2, device=x1.device, dtype=torch.float32), rows, gp, chunks)

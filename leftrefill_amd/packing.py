@@ -20,6 +20,32 @@ def pack_conv(w, cin_pad=None, cout_pad=None, dtype=torch.float16):
     return out.reshape(cout_pad, kh * kw * cin_pad).contiguous()
 
 
+def up_phase_taps(w):
+    """Exact phase weights of `conv3x3(nearest_2x(x))`: w [Cout, Cin, 3, 3] -> [2, 2, Cout, Cin, 2, 2] in w's dtype, no rounding beyond its
+    additions.  Output pixel (2i + a, 2j + b) reads source rows i - 1 (ky = 0) and i (ky = 1, 2) when a = 0, rows i (ky = 0, 1) and i + 1
+    (ky = 2) when a = 1 -- columns alike with b -- so it is a 2x2 conv over source pixels (i + a - 1 + dy, j + b - 1 + dx) whose tap
+    (dy, dx) is the sum of the 3x3 taps that land on that pixel."""
+    def merge(t, dim, a):
+        t0, t1, t2 = t.select(dim, 0), t.select(dim, 1), t.select(dim, 2)
+        return torch.stack([t0, t1 + t2] if a == 0 else [t0 + t1, t2], dim)
+    return torch.stack([torch.stack([merge(merge(w, 2, a), 3, b) for b in (0, 1)]) for a in (0, 1)])
+
+
+def pack_conv_up_phase(w, cin_pad=None, cout_pad=None, dtype=torch.float16):
+    """3x3 weights of an Upsample conv -> [4, Cout_pad, 4 * Cin_pad] for lr_gemm_conv_f16's phase form (up = LR_UP_PHASE): slice 2a + b holds
+    the 2x2 kernel of output phase (a, b), K index = (2 dy + dx) * Cin_pad + c.  The taps that merge are the `dtype`-rounded taps of the 9-tap
+    pack, summed exactly (fp32 holds the sum of four 16-bit values) and rounded to `dtype` once: every packed weight is the nearest
+    `dtype` value to the sum the up = 1 form multiplies by."""
+    cout, cin, kh, kw = w.shape
+    assert kh == 3 and kw == 3
+    cin_pad = cin_pad or pad_to(cin, 64)
+    cout_pad = cout_pad or pad_to(cout, 64)
+    wp = up_phase_taps(w.to(dtype).float()).to(dtype)                     # [2, 2, Cout, Cin, 2, 2]
+    out = torch.zeros(4, cout_pad, 4, cin_pad, dtype=dtype, device=w.device)
+    out[:, :cout, :, :cin] = wp.permute(0, 1, 2, 4, 5, 3).reshape(4, cout, 4, cin)
+    return out.reshape(4, cout_pad, 4 * cin_pad).contiguous()
+
+
 def pack_bias(b, n_pad=None):
     n_pad = n_pad or pad_to(b.numel(), 64)
     out = torch.zeros(n_pad, dtype=torch.float32, device=b.device)
