@@ -208,16 +208,19 @@ typedef struct lr_gemm_args {
    * deterministic, no second launch.  Plans that do not qualify fall back to mode 0 silently. */
   int32_t splitk_mode;
 } lr_gemm_args;
-/* row tiles per sample of gn_group_out for this call, 0 if the plan cannot produce per-group sums */
+/* The five queries below and lr_gemm_conv_f16 share ONE resolution of args (resolve_plan in csrc/gemm_conv.hip: tile, pipe, split-K
+ * factor and kernel instance), so a buffer sized from a query is the size the launch writes.  They read only the integer fields and
+ * whether p2 / skip1 / skip2 are null; the launch alone may still drop an automatic split for want of a workspace. */
+/* row tiles per sample of gn_group_out in the resolved plan, 0 if it cannot produce per-group sums */
 int lr_gemm_gn_group_chunks(const lr_gemm_args* args);
-/* rows per block of gn_stats_out (a function of the tile that will be used) */
+/* rows per block of gn_stats_out: the resolved instance's wave-tile rows, 32 behind split-K */
 int lr_gemm_gn_rows(const lr_gemm_args* args);
-/* plan[0..3] = (tile_m, tile_n, splits, pipe) the call would use: explicit requests as given, zeros resolved by the static
+/* plan[0..3] = (tile_m, tile_n, splits, pipe) of the resolved plan: explicit requests as given, zeros resolved by the static
  * heuristics (a pure function of the shape -- never of timing; the Python front end ships its tuned choices as a table). */
 int lr_gemm_plan(const lr_gemm_args* args, int32_t* plan);
-/* number of per-row partials this call writes to stats_out (a function of N and the tile that will be used) */
+/* number of per-row partials this call writes to stats_out: column tiles of the resolved plan x its instance's waves along N */
 int lr_gemm_stats_parts(const lr_gemm_args* args);
-/* bytes of workspace lr_gemm_conv_f16 would like for this problem (0 if it will not split) */
+/* bytes of workspace lr_gemm_conv_f16 would like for the resolved plan (0 if it will not split) */
 int64_t lr_gemm_workspace_bytes(const lr_gemm_args* args);
 int lr_gemm_conv_f16(const lr_gemm_args* args, lr_stream_t s);
 /* number of bounded-spin timeouts of the in-launch split-K reduce since the library was loaded (0 in a healthy run; synchronises

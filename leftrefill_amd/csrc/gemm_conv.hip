@@ -824,13 +824,13 @@ static int launch_pipe(const GemmParams& P, hipStream_t st) {
   if constexpr (MODE != 2) { if (P.bf16) return launch_pipe_t<BM2, NW, BN, WMW, NSTAGE, MODE, bf16, PH>(P, st); }
   return launch_pipe_t<BM2, NW, BN, WMW, NSTAGE, MODE, f16, PH>(P, st);
 }
-template <int BN, int WMW, int NSTAGE, int MODE>
-static int launch_gemm256(const GemmParams& P, hipStream_t st) { return launch_pipe<256, 8, BN, WMW, NSTAGE, MODE>(P, st); }
 template <int BN, int MODE>
 static int launch_gemm(const GemmParams& P, hipStream_t st) {
   if constexpr (MODE != 2) { if (P.bf16) return launch_gemm_t<BN, MODE, bf16>(P, st); }
   return launch_gemm_t<BN, MODE, f16>(P, st);
 }
+template <int BN>
+static int launch_halo(const GemmParams& P, hipStream_t st) { return lr_launch_conv_halo(P, BN, st); }      // conv_halo.hip
 
 static int launch_reduce(const GemmParams& P, hipStream_t st) {
   const dim3 grid((P.N + 8 * RED_GROUPS - 1) / (8 * RED_GROUPS), (P.M + RED_ROWS - 1) / RED_ROWS);
@@ -843,7 +843,7 @@ static int launch_reduce(const GemmParams& P, hipStream_t st) {
 // split-K heuristic: only when the tile grid cannot fill the chip (256 CUs x 2 resident blocks) and K is long.
 // geglu: the GEGLU / erf-GELU epilogue modes, which are not instantiated for the 160-column tiles
 // phase: the phase form of the upsample conv (lr_gemm_args.up == LR_UP_PHASE) -- only the pipelined instances gather it: 256-row tiles where
-// they fill the chip, else the 8-wave 128-row ones (plan_pipe)
+// they fill the chip, else the 8-wave 128-row ones (resolve_plan: pipe)
 static void choose_tile(int M, int N, int geglu, int* tm, int* tn, bool phase = false) {
   // explicit requests win; otherwise: the 256-row 8-wave kernel for large M when BN divides N, else the 128-row one
   if (phase) {
@@ -869,6 +869,7 @@ static int choose_splits(int M, int N, int K, int tm, int tn, int geglu, int sta
   if (geglu) return 1;
   const int tiles = ((M + tm - 1) / tm) * ((N + tn - 1) / tn);
   const int nk = K / BK;
+  if (tiles < 1) return 1;                                    // (an empty problem: the launch refuses it, the queries must not divide by it)
   if (stages == LR_PIPE_HALO) {                               // the halo-tile conv splits by whole 64-channel chunks (9 K-steps each)
     const int t_ = ((M + 255) / 256) * ((N + tn - 1) / tn), chunks = K / 576;
     if (t_ * 10 > 256 * 6 || chunks < 8) return 1;
@@ -885,70 +886,112 @@ static int choose_splits(int M, int N, int K, int tm, int tn, int geglu, int sta
   return s < 1 ? 1 : s;
 }
 
-// pipeline variant (lr_gemm_args.pipe) of the instance that serves tile (tm, tn): for 128-row tiles 2 = the 4-wave 2-stage
-// kernel (several blocks per CU cover each other's waits) and, for tn = 128 | 160, LR_PIPE_W8_DEEP (4: 8 waves, 4-stage ring,
-// one block per CU, loads three K-steps ahead); for 256-row tiles the ring depth of the only instance.
-// (An 8-wave 2-stage variant with two blocks per CU was measured too: 2-3 us faster on the short-K linears in isolation,
-// no difference in the step -- not kept.)
-static int choose_stages(int tm, int tn, int stages) {
-  if (stages == LR_PIPE_HALO && tm == 256 && (tn == 160 || tn == 320)) return LR_PIPE_HALO;
-  if (tm == 128) return (stages == 4 && (tn == 128 || tn == 160)) ? 4 : 2;
-  return (tn == 128 || tn == 160) ? 3 : 2;
+// THE INSTANCE TABLE: one row per kernel instance that exists; what the plan queries report about a tile and what the launch runs for it
+// are both read from its row.  Key: (tile, form, epilogue mode 0 plain | 1 GEGLU | 2 erf-GELU, phase gather).  form (from lr_gemm_args.pipe):
+// 0 = the tile's standard instance -- 128 rows: the 4-wave 2-stage kernel (several blocks per CU cover each other's waits), 256 rows: the
+// only one; LR_PIPE_W8_DEEP (4) = 128 x (128 | 160) with 8 waves and a 4-stage ring, one block per CU, loads three K-steps ahead;
+// LR_PIPE_HALO (8) = the halo-tile conv.  (An 8-wave 2-stage variant with two blocks per CU was measured too: 2-3 us faster on the short-K
+// linears in isolation, no difference in the step -- not kept.)
+struct Instance {
+  int tm, tn, form, mode, phase;
+  int wnw;         // waves along N: each writes one (sum, sumsq) partial per row (stats_out)
+  int wave_rows;   // rows per wave tile: the row-block size of gn_stats_out
+  int stages;      // ring depth, reported as plan[3] and accepted as lr_gemm_args.pipe
+  int (*launch)(const GemmParams&, hipStream_t);      // picks fp16 | bf16 inside; null: no such instance
+};
+static const Instance INSTANCES[] = {
+    // tm, tn, form, mode, phase, wnw, wave_rows, stages, launch
+    // the pipelined instances with the phase gather (gemm_conv_pipe_kernel<.., PH = true>)
+    {128, 128, LR_PIPE_W8_DEEP, 0, 1, 2, 32, 4, launch_pipe<128, 8, 128, 4, 4, 0, true>},
+    {128, 160, LR_PIPE_W8_DEEP, 0, 1, 2, 32, 4, launch_pipe<128, 8, 160, 4, 4, 0, true>},
+    {256, 128, 0, 0, 1, 2, 64, 3, launch_pipe<256, 8, 128, 4, 3, 0, true>},
+    {256, 160, 0, 0, 1, 2, 64, 3, launch_pipe<256, 8, 160, 4, 3, 0, true>},
+    {256, 320, 0, 0, 1, 4, 128, 2, launch_pipe<256, 8, 320, 2, 2, 0, true>},
+    // plain epilogue
+    {128, 128, LR_PIPE_W8_DEEP, 0, 0, 2, 32, 4, launch_pipe<128, 8, 128, 4, 4, 0>},      // 8 waves, 4 x 2: wave tile 32 x BN/2
+    {128, 160, LR_PIPE_W8_DEEP, 0, 0, 2, 32, 4, launch_pipe<128, 8, 160, 4, 4, 0>},
+    {128, 128, 0, 0, 0, 2, 64, 2, launch_gemm<128, 0>},                                  // 4 waves, 2 x 2
+    {128, 64, 0, 0, 0, 2, 64, 2, launch_gemm<64, 0>},
+    {128, 160, 0, 0, 0, 2, 64, 2, launch_gemm<160, 0>},
+    {256, 128, 0, 0, 0, 2, 64, 3, launch_pipe<256, 8, 128, 4, 3, 0>},                    // 8 waves, 4 x 2
+    {256, 160, 0, 0, 0, 2, 64, 3, launch_pipe<256, 8, 160, 4, 3, 0>},
+    {256, 256, 0, 0, 0, 4, 128, 2, launch_pipe<256, 8, 256, 2, 2, 0>},                   // 2 x 4: wave tile 128 x 64
+    {256, 320, 0, 0, 0, 4, 128, 2, launch_pipe<256, 8, 320, 2, 2, 0>},                   // wave tile 128 x 80
+    // GEGLU (not instantiated for the 160-column tiles)
+    {128, 128, LR_PIPE_W8_DEEP, 1, 0, 2, 32, 4, launch_pipe<128, 8, 128, 4, 4, 1>},
+    {128, 128, 0, 1, 0, 2, 64, 2, launch_gemm<128, 1>},
+    {128, 64, 0, 1, 0, 2, 64, 2, launch_gemm<64, 1>},
+    {256, 128, 0, 1, 0, 2, 64, 3, launch_pipe<256, 8, 128, 4, 3, 1>},
+    {256, 256, 0, 1, 0, 4, 128, 2, launch_pipe<256, 8, 256, 2, 2, 1>},
+    {256, 320, 0, 1, 0, 2, 64, 2, launch_pipe<256, 8, 320, 4, 2, 1>},                    // 4 x 2, wave tile 64 x 160: even TN
+    // erf-GELU (text tower MLP): the small-tile instances only, fp16 only
+    {128, 128, 0, 2, 0, 2, 64, 2, launch_gemm<128, 2>},
+    {128, 64, 0, 2, 0, 2, 64, 2, launch_gemm<64, 2>},
+    {256, 128, 0, 2, 0, 2, 64, 3, launch_pipe<256, 8, 128, 4, 3, 2>},
+    // the halo-tile 3x3 conv (conv_halo.hip: input patch resident in LDS), plain epilogue only
+    {256, 160, LR_PIPE_HALO, 0, 0, 2, 64, LR_PIPE_HALO, launch_halo<160>},
+    {256, 320, LR_PIPE_HALO, 0, 0, 4, 128, LR_PIPE_HALO, launch_halo<320>},
+};
+
+// The row of a (tile, lr_gemm_args.pipe as planned, mode, phase).  A tile can be requested that no instance serves (256 x 64, 128 x 160 with
+// GEGLU, pipe 4 on a 256-row tile ...): the launch refuses it (launch == null); the queries answer for it as for the wave grid such a tile
+// would have -- 128 rows: 2 x 2 waves (4 x 2 on the 4-stage ring for 128 | 160 columns), else 4 x 2 (3 stages for 128 | 160 columns, else 2),
+// 2 x 4 for 256 and non-GEGLU 320 columns.
+static Instance find_instance(int tm, int tn, int pipe, int mode, int phase) {
+  const int form = (pipe == LR_PIPE_W8_DEEP || pipe == LR_PIPE_HALO) ? pipe : 0;
+  for (const Instance& r : INSTANCES)
+    if (r.tm == tm && r.tn == tn && r.form == form && r.mode == mode && r.phase == phase) return r;
+  const bool mid = tn == 128 || tn == 160, wide = tm != 128 && (tn == 256 || (tn == 320 && mode != 1));
+  const int stages = tm == 128 ? (pipe == 4 && mid ? 4 : 2) : (pipe == LR_PIPE_HALO && tm == 256 && (tn == 160 || tn == 320)) ? LR_PIPE_HALO : mid ? 3 : 2;
+  return {tm, tn, form, mode, phase, wide ? 4 : 2, wide ? 128 : (tm == 128 && stages == 4) ? 32 : 64, stages, nullptr};
 }
 
 static bool is_phase(const lr_gemm_args* a) { return a->up == LR_UP_PHASE; }
-// lr_gemm_args.pipe as planned: the 128-row tiles of the phase form always run on the 8-wave 4-stage instance
-static int plan_pipe(const lr_gemm_args* a, int tm) { return (is_phase(a) && tm == 128 && a->pipe == 0) ? 4 : a->pipe; }
+// the 16-channel 3x3 source: K = 144 zero-padded to three K-steps (wt is [N][192], k = tap * 16 + c, taps 9..11 zero)
+static bool is_c16(const lr_gemm_args* a) { return a->C1 == 16 && !(a->p2 && a->C2) && a->taps == 9 && a->stride == 1 && a->up == 0 && !a->asym; }
 
-// waves along N of the instance that serves tile (tm, tn): each writes one (sum, sumsq) partial per row
-static int tile_wnw(int tm, int tn, int geglu) {
-  if (tm == 128) return 2;
-  if (tn == 256) return 4;
-  if (tn == 320) return geglu ? 2 : 4;
-  return 2;   // 256 x {128, 160}: 4 x 2 waves
+// THE RESOLVED PLAN of a call: what the five queries below report and what the launch runs, derived from lr_gemm_args in one place.
+struct Plan {
+  int M, K;        // rows; reduction length (the 16-channel source: 192)
+  int tm, tn;
+  int pipe;        // lr_gemm_args.pipe as planned: the 128-row tiles of the phase form always run on the 8-wave 4-stage instance
+  int splits;      // as requested, else the heuristic's (the launch alone may still fall back to 1 for want of a workspace)
+  Instance inst;   // inst.stages: the reported ring depth
+};
+static Plan resolve_plan(const lr_gemm_args* a) {
+  Plan p;
+  p.M = a->B * a->H * a->W;
+  p.K = is_c16(a) ? 192 : a->taps * (a->C1 + (a->p2 ? a->C2 : 0)) + (a->skip1 ? a->Cs1 + (a->skip2 ? a->Cs2 : 0) : 0);
+  p.tm = a->tile_m; p.tn = a->tile_n;
+  choose_tile(p.M, a->N, a->geglu != 0, &p.tm, &p.tn, is_phase(a));
+  p.pipe = (is_phase(a) && p.tm == 128 && a->pipe == 0) ? 4 : a->pipe;
+  p.splits = a->splits ? a->splits : choose_splits(p.M, a->N, p.K, p.tm, p.tn, a->geglu == 1, p.pipe);
+  p.inst = find_instance(p.tm, p.tn, p.pipe, a->geglu == 1 ? 1 : a->geglu == 2 ? 2 : 0, is_phase(a));
+  return p;
 }
 
 extern "C" int lr_gemm_plan(const lr_gemm_args* a, int32_t* plan) {
   if (!a || !plan) return LR_E_ARG;
-  const int M = a->B * a->H * a->W;
-  const int K = a->taps * (a->C1 + (a->p2 ? a->C2 : 0)) + (a->skip1 ? a->Cs1 + (a->skip2 ? a->Cs2 : 0) : 0);
-  int tn = a->tile_n, tm = a->tile_m;
-  choose_tile(M, a->N, a->geglu != 0, &tm, &tn, is_phase(a));
-  plan[0] = tm; plan[1] = tn;
-  plan[2] = a->splits ? a->splits : choose_splits(M, a->N, K, tm, tn, a->geglu == 1, plan_pipe(a, tm));
-  plan[3] = choose_stages(tm, tn, plan_pipe(a, tm));
+  const Plan p = resolve_plan(a);
+  plan[0] = p.tm; plan[1] = p.tn; plan[2] = p.splits; plan[3] = p.inst.stages;
   return 0;
-}
-
-// rows per wave tile of the instance that serves tile (tm, tn): the row-block size of gn_stats_out
-static int tile_wave_rows(int tm, int tn, int geglu, int stages = 0) {
-  if (tm == 128) return choose_stages(tm, tn, stages) == 4 ? 32 : 64;     // 8-wave instance: 4 x 2 waves, wave tile 32 x BN/2
-  if (tn == 256) return 128;
-  if (tn == 320) return geglu ? 64 : 128;
-  return 64;   // 256 x {128, 160}: 4 x 2 waves
 }
 
 extern "C" int lr_gemm_gn_rows(const lr_gemm_args* a) {
   if (!a) return 0;
-  int tn = a->tile_n, tm = a->tile_m;
-  const int M = a->B * a->H * a->W;
-  choose_tile(M, a->N, a->geglu != 0, &tm, &tn, is_phase(a));
-  const int K = a->taps * (a->C1 + (a->p2 ? a->C2 : 0)) + (a->skip1 ? a->Cs1 + (a->skip2 ? a->Cs2 : 0) : 0);
-  const int splits = a->splits ? a->splits : choose_splits(M, a->N, K, tm, tn, a->geglu == 1, plan_pipe(a, tm));
-  if (splits > 1) return RED_ROWS;     // the statistics come out of the split-K reduce kernel
-  return tile_wave_rows(tm, tn, a->geglu == 1, plan_pipe(a, tm));
+  const Plan p = resolve_plan(a);
+  return p.splits > 1 ? RED_ROWS : p.inst.wave_rows;     // behind split-K the statistics come out of the reduce kernel
 }
 
 // chunks per sample of gn_group_out for this call (0: the plan cannot produce per-group sums -- tile width not a whole number
 // of groups, tiles straddling samples, GEGLU): rows per chunk = the tile's rows (32 behind a split-K reduce)
-static int gn_group_chunks(const lr_gemm_args* a, int tm, int tn, int splits) {
+static int gn_group_chunks(const lr_gemm_args* a, const Plan& p, int splits) {
   if (a->geglu || a->N % 32) return 0;
   const int cg = a->N / 32;
   const int hw = a->gn_hw > 0 ? a->gn_hw : a->H * a->W;
-  const int M = a->B * a->H * a->W;
-  if (hw <= 0 || M % hw) return 0;
-  const int rows = splits > 1 ? RED_ROWS : tm;
-  const int width = splits > 1 ? 8 * RED_GROUPS : tn;
+  if (hw <= 0 || p.M % hw) return 0;
+  const int rows = splits > 1 ? RED_ROWS : p.tm;
+  const int width = splits > 1 ? 8 * RED_GROUPS : p.tn;
   if (width % cg || hw % rows) return 0;
   // phase form: a row tile holds source pixels of ONE phase; it must also lie inside one sample (the chunks of a sample: 4 phases x Hs Ws / rows)
   if (is_phase(a) && (hw != a->H * a->W || (splits == 1 && (a->Hs * a->Ws) % rows))) return 0;
@@ -957,29 +1000,25 @@ static int gn_group_chunks(const lr_gemm_args* a, int tm, int tn, int splits) {
 
 extern "C" int lr_gemm_gn_group_chunks(const lr_gemm_args* a) {
   if (!a) return 0;
-  int tn = a->tile_n, tm = a->tile_m;
-  const int M = a->B * a->H * a->W;
-  choose_tile(M, a->N, a->geglu != 0, &tm, &tn, is_phase(a));
-  const int K = a->taps * (a->C1 + (a->p2 ? a->C2 : 0)) + (a->skip1 ? a->Cs1 + (a->skip2 ? a->Cs2 : 0) : 0);
-  const int splits = a->splits ? a->splits : choose_splits(M, a->N, K, tm, tn, a->geglu == 1, plan_pipe(a, tm));
-  return gn_group_chunks(a, tm, tn, splits);
+  const Plan p = resolve_plan(a);
+  return gn_group_chunks(a, p, p.splits);
 }
+
+// (sum, sumsq) partials per row of stats_out: one per wave along N of every column tile
+static int stats_parts(const lr_gemm_args* a, const Plan& p) { return ((a->N + p.tn - 1) / p.tn) * p.inst.wnw; }
 
 extern "C" int lr_gemm_stats_parts(const lr_gemm_args* a) {
   if (!a) return 0;
-  int tn = a->tile_n, tm = a->tile_m;
-  choose_tile(a->B * a->H * a->W, a->N, a->geglu != 0, &tm, &tn, is_phase(a));
-  return ((a->N + tn - 1) / tn) * tile_wnw(tm, tn, a->geglu == 1);
+  return stats_parts(a, resolve_plan(a));
 }
+
+// fp32 partials of `splits` K-slices
+static int64_t workspace_bytes(const lr_gemm_args* a, const Plan& p, int splits) { return splits > 1 ? (int64_t)splits * p.M * a->N * (int64_t)sizeof(float) : 0; }
 
 extern "C" int64_t lr_gemm_workspace_bytes(const lr_gemm_args* a) {
   if (!a) return 0;
-  const int M = a->B * a->H * a->W;
-  const int K = a->taps * (a->C1 + (a->p2 ? a->C2 : 0)) + (a->skip1 ? a->Cs1 + (a->skip2 ? a->Cs2 : 0) : 0);
-  int tn = a->tile_n, tm = a->tile_m;
-  choose_tile(M, a->N, a->geglu != 0, &tm, &tn, is_phase(a));
-  int splits = a->splits ? a->splits : choose_splits(M, a->N, K, tm, tn, a->geglu == 1, plan_pipe(a, tm));
-  return splits > 1 ? (int64_t)splits * M * a->N * (int64_t)sizeof(float) : 0;
+  const Plan p = resolve_plan(a);
+  return workspace_bytes(a, p, p.splits);
 }
 
 // Arrival counters of the in-launch split-K reduce: 16 slots x 2048 tiles, zero at module load and left zero by every launch
@@ -1012,7 +1051,7 @@ extern "C" int lr_gemm_conv_f16(const lr_gemm_args* a, lr_stream_t s) {
   GemmParams P;
   P.p1 = (const f16*)a->p1; P.C1 = a->C1;
   P.p2 = (const f16*)a->p2; P.C2 = a->p2 ? a->C2 : 0;
-  P.c16 = (P.C1 == 16 && P.C2 == 0 && a->taps == 9 && a->stride == 1 && a->up == 0 && !a->asym) ? 1 : 0;
+  P.c16 = is_c16(a) ? 1 : 0;
   if (P.C1 <= 0 || (!P.c16 && P.C1 % 64) || P.C2 % 64) return LR_E_ALIGN;
   const bool phase = is_phase(a);
   if (a->taps != 1 && a->taps != 9 && !(phase && a->taps == 4)) return LR_E_UNSUPPORTED;
@@ -1024,6 +1063,9 @@ extern "C" int lr_gemm_conv_f16(const lr_gemm_args* a, lr_stream_t s) {
                 (a->gn_hw > 0 && a->gn_hw != a->H * a->W)))
     return LR_E_UNSUPPORTED;
   if (a->B <= 0 || a->H <= 0 || a->W <= 0 || a->Hs <= 0 || a->Ws <= 0 || a->N <= 0) return LR_E_ARG;
+  const Plan plan = resolve_plan(a);      // (pure: the checks below refuse in the order they always did)
+  const Instance& inst = plan.inst;
+  const int tm = plan.tm, tn = plan.tn;
   P.H = a->H; P.W = a->W; P.Hs = a->Hs; P.Ws = a->Ws;
   P.taps = a->taps; P.stride = a->stride; P.up = phase ? 0 : a->up;
   P.phase = phase ? 1 : 0; P.ph_rows = a->B * a->Hs * a->Ws; P.ph_tiles = 0; P.ph_stride = 0;      // (tiles / stride: set by the launcher)
@@ -1033,7 +1075,7 @@ extern "C" int lr_gemm_conv_f16(const lr_gemm_args* a, lr_stream_t s) {
   if (P.zins) P.up = 1;
   P.pad = a->asym ? 0 : 1;   // asym: F.pad(x, (0,1,0,1)) + conv padding 0 (VAE Downsample)
   P.wt = (const f16*)a->wt; P.N = a->N; P.bias = a->bias;
-  P.M = a->B * a->H * a->W;
+  P.M = plan.M;
   P.p3 = (const f16*)a->skip1; P.C3 = a->skip1 ? a->Cs1 : 0;
   P.p4 = a->skip1 ? (const f16*)a->skip2 : nullptr; P.C4 = P.p4 ? a->Cs2 : 0;
   if (P.p3) {      // pointwise K extension (the ResBlock's skip_connection inside its last conv): see GemmParams.p3
@@ -1042,7 +1084,7 @@ extern "C" int lr_gemm_conv_f16(const lr_gemm_args* a, lr_stream_t s) {
       return LR_E_UNSUPPORTED;
     if (P.C3 <= 0 || P.C3 % 64 || P.C4 % 64 || (((uintptr_t)P.p3 | (uintptr_t)P.p4) & 15)) return LR_E_ALIGN;
   }
-  P.K = P.c16 ? 192 : a->taps * (P.C1 + P.C2) + P.C3 + P.C4;      // c16: wt is [N][192] (k = tap * 16 + c, taps 9..11 zero)
+  P.K = plan.K;
   // 32-bit byte offsets in the gather (bit 31 marks out-of-range): every operand must stay below 2 GiB
   const int64_t lim = (int64_t)1 << 31;
   const int64_t src_rows = (int64_t)a->B * a->Hs * a->Ws;
@@ -1070,19 +1112,12 @@ extern "C" int lr_gemm_conv_f16(const lr_gemm_args* a, lr_stream_t s) {
   if (((uintptr_t)P.p1 | (uintptr_t)P.p2 | (uintptr_t)P.wt | (uintptr_t)P.out | (uintptr_t)P.resid |
        (uintptr_t)P.rowvec | (uintptr_t)P.bias) & 15)
     return LR_E_ALIGN;
-  int tn = a->tile_n, tm = a->tile_m;
-  choose_tile(P.M, P.N, P.geglu || P.gelu, &tm, &tn, phase);
-  const int pipe = plan_pipe(a, tm);
-  int splits = a->splits;
-  if (P.c16) {      // only the pipelined 256-row instances gather 16-channel taps; three K-steps: never split
-    if (tm != 256 || (a->splits > 1) || P.geglu || P.gelu || a->wt_bstride) return LR_E_UNSUPPORTED;
-    splits = 1;
-  }
-  if (splits == 0) splits = choose_splits(P.M, P.N, P.K, tm, tn, P.geglu, pipe);
+  int splits = plan.splits;
+  // 16-channel source: only the pipelined 256-row instances gather it; three K-steps, never split (the heuristic does not split them either)
+  if (P.c16 && (tm != 256 || splits > 1 || P.geglu || P.gelu || a->wt_bstride)) return LR_E_UNSUPPORTED;
   if (splits > 1 && P.geglu) return LR_E_UNSUPPORTED;
   if (splits > 1) {
-    const int64_t need = (int64_t)splits * P.M * P.N * (int64_t)sizeof(float);
-    if (!a->workspace || a->workspace_bytes < need) {
+    if (!a->workspace || a->workspace_bytes < workspace_bytes(a, plan, splits)) {
       if (a->splits > 1) return LR_E_ARG;   // explicitly requested but no room
       splits = 1;
     }
@@ -1114,10 +1149,10 @@ extern "C" int lr_gemm_conv_f16(const lr_gemm_args* a, lr_stream_t s) {
   if (P.gs_out && (P.geglu || ((uintptr_t)P.gs_out & 15))) return LR_E_ARG;
   P.gs_store = P.gs_out != nullptr;
   // phase form, statistics from the epilogue: a wave's row block must lie inside one sample of one phase
-  if (phase && P.gs_out && splits == 1 && (a->Hs * a->Ws) % tile_wave_rows(tm, tn, 0, pipe)) return LR_E_ARG;
+  if (phase && P.gs_out && splits == 1 && (a->Hs * a->Ws) % inst.wave_rows) return LR_E_ARG;
   P.gp_out = a->gn_group_out; P.gp_cg = 1; P.gp_chunks = 0; P.gp_hw = 1;
   if (P.gp_out) {
-    P.gp_chunks = gn_group_chunks(a, tm, tn, splits);
+    P.gp_chunks = gn_group_chunks(a, plan, splits);
     if (P.gp_chunks <= 0 || ((uintptr_t)P.gp_out & 7) || a->stats_out) return LR_E_ARG;
     P.gp_cg = P.N / 32;
     P.gp_hw = a->gn_hw > 0 ? a->gn_hw : a->H * a->W;
@@ -1131,62 +1166,20 @@ extern "C" int lr_gemm_conv_f16(const lr_gemm_args* a, lr_stream_t s) {
     if ((int64_t)a->B * P.wt_bstride * 2 >= lim) return LR_E_UNSUPPORTED;
   }
   P.st_out = a->stats_out;
-  P.st_parts = ((P.N + tn - 1) / tn) * tile_wnw(tm, tn, P.geglu);
+  P.st_parts = stats_parts(a, plan);
   if (P.st_out && (splits > 1 || ((uintptr_t)P.st_out & 7))) return LR_E_ARG;
   hipStream_t st = (hipStream_t)s;
-  int rc;
-  const int mode = P.geglu ? 1 : P.gelu ? 2 : 0;
-  if (pipe != 0 && pipe != choose_stages(tm, tn, pipe)) return LR_E_UNSUPPORTED;
-  const bool deep = tm == 128 && choose_stages(tm, tn, pipe) == 4;
+  // no instance for this tile / mode, or a requested ring depth that is not the instance's
+  if (!inst.launch || (plan.pipe != 0 && plan.pipe != inst.stages)) return LR_E_UNSUPPORTED;
 #ifdef LR_DEV_VARIANTS
   // in-launch split-K reduce: the 8-wave instances with 160- / 320-column tiles, the whole grid resident at once (one block per CU)
-  if (P.splits > 1 && a->splitk_mode == 1 && mode != 1 && (tn == 160 || tn == 320) && (tm == 256 || deep || a->pipe == LR_PIPE_HALO)) {
+  if (P.splits > 1 && a->splitk_mode == 1 && inst.mode != 1 && (tn == 160 || tn == 320) && (tm == 256 || inst.form == LR_PIPE_W8_DEEP)) {
     const int64_t tiles = (int64_t)((P.M + tm - 1) / tm) * ((P.N + tn - 1) / tn);
     if (tiles * P.splits <= 256 && tiles <= 2048 && (int64_t)P.splits * P.M * P.N * 4 < lim && P.N % 8 == 0)
       P.sk_cnt = sk_counter_slot();
   }
 #endif
-  if (a->pipe == LR_PIPE_HALO) {      // 3x3 stride-1 conv with the input patch resident in LDS (conv_halo.hip)
-    if (mode != 0 || a->asym) return LR_E_UNSUPPORTED;
-    rc = lr_launch_conv_halo(P, tn, st);
-    if (rc || P.splits == 1 || P.sk_cnt) return rc;
-    return launch_reduce(P, st);
-  }
-  if (phase) {      // the pipelined instances with the phase gather (gemm_conv_pipe_kernel<.., PH = true>)
-    if (deep && tn == 128) rc = launch_pipe<128, 8, 128, 4, 4, 0, true>(P, st);
-    else if (deep && tn == 160) rc = launch_pipe<128, 8, 160, 4, 4, 0, true>(P, st);
-    else if (tm == 256 && tn == 128) rc = launch_pipe<256, 8, 128, 4, 3, 0, true>(P, st);
-    else if (tm == 256 && tn == 160) rc = launch_pipe<256, 8, 160, 4, 3, 0, true>(P, st);
-    else if (tm == 256 && tn == 320) rc = launch_pipe<256, 8, 320, 2, 2, 0, true>(P, st);
-    else return LR_E_UNSUPPORTED;
-  } else if (mode == 0) {
-    if (deep && tn == 128) rc = launch_pipe<128, 8, 128, 4, 4, 0>(P, st);
-    else if (deep && tn == 160) rc = launch_pipe<128, 8, 160, 4, 4, 0>(P, st);
-
-    else if (tm == 128 && tn == 128) rc = launch_gemm<128, 0>(P, st);
-    else if (tm == 128 && tn == 64) rc = launch_gemm<64, 0>(P, st);
-    else if (tm == 128 && tn == 160) rc = launch_gemm<160, 0>(P, st);
-    else if (tm == 256 && tn == 128) rc = launch_gemm256<128, 4, 3, 0>(P, st);
-    else if (tm == 256 && tn == 160) rc = launch_gemm256<160, 4, 3, 0>(P, st);
-    else if (tm == 256 && tn == 256) rc = launch_gemm256<256, 2, 2, 0>(P, st);                 // wave tile 128 x 64
-    else if (tm == 256 && tn == 320) rc = launch_gemm256<320, 2, 2, 0>(P, st);                 // wave tile 128 x 80
-    else return LR_E_UNSUPPORTED;
-  } else if (mode == 1) {
-    if (deep && tn == 128) rc = launch_pipe<128, 8, 128, 4, 4, 1>(P, st);
-    else if (deep) return LR_E_UNSUPPORTED;
-    else if (tm == 128 && tn == 128) rc = launch_gemm<128, 1>(P, st);
-    else if (tm == 128 && tn == 64) rc = launch_gemm<64, 1>(P, st);
-    else if (tm == 256 && tn == 128) rc = launch_gemm256<128, 4, 3, 1>(P, st);
-    else if (tm == 256 && tn == 256) rc = launch_gemm256<256, 2, 2, 1>(P, st);
-    else if (tm == 256 && tn == 320) rc = launch_gemm256<320, 4, 2, 1>(P, st);                 // wave tile 64 x 160: even TN
-    else return LR_E_UNSUPPORTED;
-  } else {   // erf-GELU epilogue (text tower MLP): the small-tile instances only
-    if (deep) return LR_E_UNSUPPORTED;
-    if (tm == 128 && tn == 128) rc = launch_gemm<128, 2>(P, st);
-    else if (tm == 128 && tn == 64) rc = launch_gemm<64, 2>(P, st);
-    else if (tm == 256 && tn == 128) rc = launch_gemm256<128, 4, 3, 2>(P, st);
-    else return LR_E_UNSUPPORTED;
-  }
+  const int rc = inst.launch(P, st);      // (the halo-tile launcher refuses what it cannot gather -- asym, strides -- itself)
   if (rc || P.splits == 1 || P.sk_cnt) return rc;
   return launch_reduce(P, st);
 }

@@ -352,34 +352,9 @@ def gemm_conv(x1, wt, *, B, H, W, Hs=None, Ws=None, taps=1, stride=1, up=0, asym
         scale = _PLAN_BATCH_SCALE[0]
         # (a conv with the pointwise extension is planned like the plain conv: the table knows that shape)
         key = tile_key(M * scale, Nw, Kw - Cs1 - Cs2, taps, stride, up, geglu, C2 > 0, asym, gelu, ln is not None, want_stats)
-        best = tile_cache().get(key)
-        (TABLE_HITS if best is not None else TABLE_MISSES).add(key)
-        if best is None and PLAN_LOG and key not in _untabulated:      # developer aid: which shapes fall back to the static heuristic
-            _untabulated.add(key)
-            import sys
-            print(f"[leftrefill] untabulated GEMM shape {key} (taps {taps}, H {H}, W {W}, skip {skip is not None})", file=sys.stderr, flush=True)
-        if best is None and (scale != 1 or (HEURISTIC_REFINE and not AUTOTUNE and skip is None and not per_sample and not c16)):
-            # not in the table: the library's static heuristic for the (scaled) batch, refined by what the in-step tuning of round 6 found on
-            # every small-M shape (_refine_plan); a caller of the C ABI without this front end gets the unrefined heuristic
-            a.B = B * scale
-            if ln is not None or want_stats:
-                a.splits = 1                 # row statistics / the LayerNorm fold never split K -- like the unscaled plan below
-            best = _refine_plan(lib, a, geglu or gelu) if HEURISTIC_REFINE and skip is None and not per_sample and not c16 else _lib_plan(lib, a)
-            a.B, a.splits, a.tile_m, a.tile_n, a.pipe = B, 0, 0, 0, 0
-        if best is None and AUTOTUNE and not torch.cuda.is_current_stream_capturing():
-            best = _tune_tiles(lib, a, x1.device, geglu, ln is not None or want_stats, want_stats)
-            tile_cache()[key] = best
-        if best is not None and PLAN_TRIAL is not None and PLAN_TRIAL.get(key) is not None:
-            best = PLAN_TRIAL[key]
-        if best is not None:
-            a.tile_m, a.tile_n, a.splits = best[:3]
-            a.pipe = best[3] if len(best) > 3 else 0
-            if a.pipe == 8 and (W % 16 or (H % 16 and not (H == 8 and M % 256 == 0 and (M * scale) % 256 == 0))):      # the table is keyed by M: the halo-tile instance needs 16 x 16 pixel tiles (or pairs of 8-line images; decided for the planned batch AND this call),
-                a.pipe = 0                              # any other latent of the same size takes the tile's gather instance
-        if skip is not None and best is None:      # static heuristic: ask the library, then make sure the tile is a pipelined one
-            plan = (ctypes.c_int32 * 4)()
-            lib.lr_gemm_plan(a, plan)
-            a.tile_m, a.tile_n, a.splits, a.pipe = plan[0], plan[1], plan[2], plan[3]
+        plan = _choose_plan(lib, a, key, scale, x1.device, refine=skip is None and not per_sample and not c16, want_stats=want_stats)
+        if plan is not None:
+            a.tile_m, a.tile_n, a.splits, a.pipe = plan
     stats = None
     if want_stats:
         if a.splits == 0:
@@ -391,9 +366,7 @@ def gemm_conv(x1, wt, *, B, H, W, Hs=None, Ws=None, taps=1, stride=1, up=0, asym
         a.splits = 1
     gstats = None
     if want_gn_stats:
-        plan = (ctypes.c_int32 * 4)()
-        lib.lr_gemm_plan(a, plan)
-        a.splits = plan[2]                  # pinned: the row-block size of the statistics depends on it (32 behind split-K)
+        a.splits = _lib_plan(lib, a)[2]     # pinned: the row-block size of the statistics depends on it (32 behind split-K)
         rows = lib.lr_gemm_gn_rows(a)
         hw = gn_hw or H * W
         # (phase form, statistics from the epilogue: the row blocks hold source pixels of one phase -- they must divide a sample's Hs * Ws)
@@ -405,9 +378,7 @@ def gemm_conv(x1, wt, *, B, H, W, Hs=None, Ws=None, taps=1, stride=1, up=0, asym
             a.gn_group_out = _p(gp)
     ws = _workspace(lib, a, x1.device)
     if LAUNCH_HOOK is not None and tile_m == 0 and tile_n == 0 and splits == 0:
-        plan = (ctypes.c_int32 * 4)()
-        lib.lr_gemm_plan(a, plan)
-        LAUNCH_HOOK(key, 0, tuple(plan))
+        LAUNCH_HOOK(key, 0, _lib_plan(lib, a))
         rc = lib.lr_gemm_conv_f16(a, st)
         LAUNCH_HOOK(key, 1, rc)
         if rc != 0 and PLAN_TRIAL is not None and PLAN_TRIAL.get(key) is not None:      # the trial plan is not one this call can take
@@ -464,19 +435,54 @@ def _refine_plan(lib, a, act_epilogue):
     return (128, tn, plan[2], 4)
 
 
+def _static_plan(lib, a, tabulated, *, scale=1, act, refine=True, no_split=False, always=True):
+    """The plan that is a pure function of the shape: the in-tree table's entry, else the library's static heuristic for the (scaled) batch,
+    refined by what the in-step tuning of round 6 found on every small-M shape (_refine_plan); a caller of the C ABI without this front end
+    gets the unrefined heuristic.  `a` has tile_m = tile_n = splits = 0 and comes back as it was.  always = False: None where the
+    heuristic is the launch's business (an unscaled batch that is not refined, or one that the autotuner will time)."""
+    refine = refine and HEURISTIC_REFINE
+    if tabulated is not None or not (always or scale != 1 or (refine and not AUTOTUNE)):
+        return tabulated
+    a.B, a.splits = a.B * scale, int(no_split)      # (row statistics / the LayerNorm fold never split K)
+    best = _refine_plan(lib, a, act) if refine else _lib_plan(lib, a)
+    a.B, a.splits = a.B // scale, 0
+    return best
+
+
+def _choose_plan(lib, a, key, scale, device, *, refine, want_stats):
+    """(tile_m, tile_n, splits, pipe) of a gemm_conv call that requests none, or None (the launch plans for itself).  In order: the table,
+    the batch-scaled / refined heuristic, the autotuner, a trial plan, the halo guard, the skip fallback."""
+    geglu, no_split = a.geglu == 1, bool(a.ln_stats) or want_stats
+    hit = tile_cache().get(key)
+    (TABLE_HITS if hit is not None else TABLE_MISSES).add(key)
+    best = hit if hit is not None else _static_plan(lib, a, None, scale=scale, act=a.geglu != 0, refine=refine, no_split=no_split, always=False)
+    if PLAN_LOG and hit is None and key not in _untabulated:      # developer aid: which shapes fall back to the static heuristic
+        _untabulated.add(key)
+        import sys
+        print(f"[leftrefill] untabulated GEMM shape {key} (taps {a.taps}, H {a.H}, W {a.W}, skip {bool(a.skip1)})", file=sys.stderr, flush=True)
+    if best is None and AUTOTUNE and not torch.cuda.is_current_stream_capturing():
+        best = _tune_tiles(lib, a, device, geglu, no_split, want_stats)
+        tile_cache()[key] = best
+    if best is not None and PLAN_TRIAL is not None and PLAN_TRIAL.get(key) is not None:
+        best = PLAN_TRIAL[key]
+    if best is not None:
+        M, pipe = a.B * a.H * a.W, best[3] if len(best) > 3 else 0
+        # the table is keyed by M: the halo-tile instance needs 16 x 16 pixel tiles (or pairs of 8-line images; decided for the planned batch
+        # AND this call, ADVICE r5), any other latent of the same size takes the tile's gather instance
+        if pipe == 8 and (a.W % 16 or (a.H % 16 and not (a.H == 8 and M % 256 == 0 and (M * scale) % 256 == 0))):
+            pipe = 0
+        return best[0], best[1], best[2], pipe
+    return _lib_plan(lib, a) if a.skip1 else None      # skip: ask the library, so that the tile is a pipelined one
+
+
 def gemm_plan(M, N, K, **kw):
     """(tile_m, tile_n, splits, pipe) lr_gemm_conv_f16 uses for a shape: the in-tree table, else the static heuristic."""
-    best = tile_cache().get(tile_key(M, N, K, **kw))
-    if best is not None:
-        return tuple(best) if len(best) > 3 else tuple(best) + (0,)
-    lib = _lib.load()
     a = GemmArgs()
     a.B, a.H, a.W, a.N, a.taps, a.C1 = 1, 1, M, N, kw.get("taps", 1), K // kw.get("taps", 1)
     a.geglu = int(kw.get("geglu", False))
-    if kw.get("ln") or kw.get("stats"):
-        a.splits = 1
-    plan = _refine_plan(lib, a, bool(kw.get("geglu") or kw.get("gelu"))) if HEURISTIC_REFINE else _lib_plan(lib, a)
-    return tuple(plan)[:3] + (plan[3] if plan[3] in (4, 8) else 0,)
+    best = _static_plan(_lib.load(), a, tile_cache().get(tile_key(M, N, K, **kw)), act=bool(kw.get("geglu") or kw.get("gelu")),
+                        no_split=bool(kw.get("ln") or kw.get("stats")))
+    return tuple(best[:3]) + (best[3] if len(best) > 3 and best[3] in (4, 8) else 0,)
 
 
 def _workspace(lib, a, device):
@@ -507,13 +513,11 @@ def _tune_tiles(lib, a, device, geglu, no_split, want_stats, reps=4, rounds=2):
     """Developer mode: time every (tile, split-K) configuration and return the fastest (tile_m, tile_n, splits)."""
     st = _stream()
     best, best_t = None, float("inf")
-    plan = (ctypes.c_int32 * 4)()
     for tm, tn, stg in TILE_CANDIDATES:
         if geglu and tn == 160:
             continue
         a.tile_m, a.tile_n, a.splits, a.pipe = tm, tn, 0, stg
-        lib.lr_gemm_plan(a, plan)
-        cands = {1} if no_split else {1, int(plan[2])}
+        cands = {1} if no_split else {1, _lib_plan(lib, a)[2]}
         for sp in sorted(cands):
             a.splits = sp
             stats = None

@@ -1256,6 +1256,66 @@ def test_gemm_conv_randomised_shapes():
     assert n_checked >= 50
 
 
+# which entries of ops.TILE_CANDIDATES lr_gemm_conv_f16 has an instance for, per epilogue mode (fp16 and bf16 alike, except that the erf-GELU
+# epilogue is fp16 only) and for the phase form of the upsample conv; every other request is refused as `unsupported`
+GEMM_INSTANCES = {
+    "plain": {(128, 64, 0), (128, 128, 0), (128, 160, 0), (128, 128, 4), (128, 160, 4), (256, 128, 0), (256, 160, 0), (256, 256, 0),
+              (256, 320, 0), (256, 160, 8), (256, 320, 8)},
+    "geglu": {(128, 64, 0), (128, 128, 0), (128, 128, 4), (256, 128, 0), (256, 256, 0), (256, 320, 0)},
+    "gelu": {(128, 64, 0), (128, 128, 0), (256, 128, 0)},
+    # (pipe 0 on a 128-row tile is planned as the 4-stage ring: the only 128-row instances with the phase gather)
+    "phase": {(128, 128, 0), (128, 160, 0), (128, 128, 4), (128, 160, 4), (256, 128, 0), (256, 160, 0), (256, 320, 0)},
+}
+
+
+def test_gemm_every_instance_is_reached_and_only_those():
+    """Every ops.TILE_CANDIDATES entry under plain / GEGLU / erf-GELU in fp16 and bf16, and as the phase form, splits = 1, on a 3x3 conv of
+    2 x 16 x 32 pixels, 320 -> 640 channels (four 256-row tiles; 640 = a multiple of 64, 128, 160, 320 with a column tail at 256): the
+    combinations of GEMM_INSTANCES launch, the others raise `unsupported`, and what launches equals the 128 x 64 instance of its mode and
+    dtype bit for bit (phase form: the 128 x 128 instance, there is no 128 x 64 one).
+    Not bit-equal: the halo-tile instances (256, 160, 8) and (256, 320, 8), which accumulate chunk-major -- they are held to the bound of
+    test_gemm_conv_randomised_shapes against F.conv2d instead."""
+    from leftrefill_amd import ops, packing
+    d = dev()
+    B, H, W, C, N = 2, 16, 32, 320, 640
+    w = torch.from_numpy(weights.fill_like("inst.w", (N, C, 3, 3)))
+    launched = {}
+    for dtype in (torch.float16, torch.bfloat16):
+        tok = lambda t: t.permute(0, 2, 3, 1).reshape(-1, C).to(dtype).contiguous().to(d)
+        x, xs = G.T("inst.x", (B, C, H, W)).to(dtype).float(), G.T("inst.xs", (B, C, H // 2, W // 2)).to(dtype).float()
+        wr = w.to(dtype).float()
+        w9, wp = packing.pack_conv(wr, cin_pad=C, dtype=dtype).to(d), packing.pack_conv_up_phase(wr, cin_pad=C, dtype=dtype).to(d)
+        refs = {"plain": F.conv2d(x, wr, padding=1), "phase": F.conv2d(F.interpolate(xs, scale_factor=2, mode="nearest"), wr, padding=1)}
+
+        def close(y, ref):
+            err = (from_tok(y, B, H, W) - ref).abs()
+            return bool((err <= 2e-3 * ref.abs() + 2e-3 * max(1.0, ref.abs().max().item())).all())
+
+        for mode in ("plain", "geglu", "gelu", "phase"):
+            base = {}
+            for tm, tn, pipe in sorted(ops.TILE_CANDIDATES, key=lambda c: c != ((128, 128, 0) if mode == "phase" else (128, 64, 0))):
+                kw = dict(B=B, H=H, W=W, tile_m=tm, tile_n=tn, pipe=pipe, splits=1)
+                try:
+                    if mode == "phase":
+                        y = ops.gemm_conv(tok(xs), wp, Hs=H // 2, Ws=W // 2, taps=4, up=3, **kw)
+                    else:
+                        y = ops.gemm_conv(tok(x), w9, taps=9, geglu=mode == "geglu", gelu=mode == "gelu", **kw)
+                except RuntimeError as e:
+                    assert "unsupported" in str(e), (mode, dtype, tm, tn, pipe, str(e))
+                    continue
+                launched.setdefault((mode, dtype), set()).add((tm, tn, pipe))
+                if not base:
+                    base["y"] = y
+                    assert mode not in refs or close(y, refs[mode]), (mode, dtype, tm, tn, pipe)
+                elif pipe == 8:
+                    assert close(y, refs[mode]), (mode, dtype, tm, tn, pipe)
+                else:
+                    assert torch.equal(y, base["y"]), (mode, dtype, tm, tn, pipe)
+    want = {(mode, dtype): inst for mode, inst in GEMM_INSTANCES.items() for dtype in (torch.float16, torch.bfloat16)
+            if (mode, dtype) != ("gelu", torch.bfloat16)}
+    assert launched == want
+
+
 def test_attention_randomised_shapes():
     """30 random (B, heads, Nq, Nkv) problems, ragged in both dimensions, on all three V paths (transpose read, pre-transposed,
     register-transposed), against the oracle's attention."""
