@@ -746,6 +746,56 @@ typedef struct lr_nvs_job {
 int lr_nvs_prep(const uint8_t* arena, int64_t arena_bytes, const lr_nvs_job* jobs, const lr_nvs_job* jobs_host, int B, int S,
                 float* image, float* masked_image, float* mask, lr_stream_t s);
 
+/* ---- Pillow's 8-bit resampler and the inpainting canvas of the one-call route (leftrefill_amd/refill.py) on the device (added under
+ *      ABI 30 like lr_batch_prep: two new symbols, nothing renumbered or re-typed; a library without them fails to bind) ----------------
+ * replaces: the host image work of the reference's interactive entry point --
+ *             `Image.resize((512, 512), BICUBIC)` of source and reference, `BILINEAR` of the mask         ref_inpainting_gradio.py:168-170
+ *             `r.resize((int(512 / ratio), 512), BICUBIC)` of every result                                                            :207
+ *             `init_mask[init_mask > 0] = 255`, `pad_image` (np.pad mode='edge'), the [reference | source] stitch        :142-145, 171-188
+ *             `convert("L") / 255.0`, `< 0.5 -> 0, >= 0.5 -> 1`, `/ 127.5 - 1.0`, `image * (mask < 0.5)`, the n copies             :54-79
+ *           in this tree leftrefill_amd/refill.py (pil_coeffs, resize_u8, prepare_numpy), whose numpy statement is pinned against Pillow
+ *           itself and is the yardstick.  The tail (composite, crop, 8-bit) is lr_eval_metrics with x0 = Wc = W, r = 1.
+ * lr_pil_resize: n_jobs (1 .. 65535) independent `Image.resize` jobs in at most two launches.
+ *   src: a byte arena on the device, 16-byte aligned (LR_E_ALIGN); a job's source is uint8 [hs][ws][c], c in {1, 3}, packed at ANY byte
+ *   offset src_off.  tables: an int32 arena on the device and the same words in host memory (tables_host).  A pass along an axis of
+ *   n_in cells to n_out cells has at word offset h_off / v_off: lo[n_out], cnt[n_out], kk[n_out][ksize], computed on the host in double
+ *   arithmetic (Pillow's precompute_coeffs + normalize_coeffs_8bpc): scale = n_in / n_out, fs = max(scale, 1), support = S_f fs (S_f = 2
+ *   bicubic, 1 bilinear), ksize = (int)ceil(support) * 2 + 1; per output index i: center = (i + 0.5) scale,
+ *   lo = max((int)(center - support + 0.5), 0), cnt = min((int)(center + support + 0.5), n_in) - lo,
+ *   w[x] = f((x + lo - center + 0.5) * (1 / fs)), summed in index order and divided by a non-zero sum,
+ *   kk = (int)(w < 0 ? -0.5 + w 2^22 : 0.5 + w 2^22); bicubic f(|x|), a = -0.5: ((a + 2) x - (a + 3)) x x + 1 below 1,
+ *   (((x - 5) x + 8) x - 4) a below 2, else 0; bilinear: 1 - x below 1, else 0.
+ *   One pass: out[i] = clamp((2^21 + sum_{j < cnt[i]} kk[i][j] in[lo[i] + j]) >> 22, 0, 255) per channel, arithmetic shift, 32-bit
+ *   accumulation (sum |kk| < 1.4 * 2^22 for both filters, times 255 stays below 2^31).
+ *   Launch 1: the horizontal pass of every job that has one (h_ksize > 0; wd == ws otherwise), into the workspace at tmp_off when a
+ *   vertical pass follows, else straight to dst.  Launch 2: the vertical pass (v_ksize > 0; hd == hs otherwise) from the workspace or
+ *   the source, or -- neither pass -- the copy.  Jobs of different sizes share a launch; a launch no job needs is not made.
+ *   jobs on the device, jobs_host the same table in host memory: every offset, size, window, ksize and lo + cnt <= n_in is checked
+ *   there before any launch.  LR_E_ARG: a null pointer, n_jobs out of range, c not 1 or 3, a side outside 1 .. 2^20, a window outside its
+ *   buffer, a skipped pass whose sizes differ, a table row outside the axis.  LR_E_UNSUPPORTED: ksize > LR_PIL_MAX_KSIZE = 1025, which admits shrinking by
+ *   up to 256 x under bicubic and 512 x under bilinear (16384 -> 64 bicubic is ksize 1025: served).
+ * lr_refill_canvas: ref, src, mask uint8 [P][Sh][Sw][3] (resize destinations of P pairs) -> the batch of P n canvases H x 2W
+ *   [reference | source], each pair's n copies adjacent: edge pad v(y, x) = in[min(y, Sh - 1)][min(x, Sw - 1)] (Sh <= H, Sw <= W);
+ *   image = (float)v / 127.5f - 1 [P n][3][H][2W]; mask [P n][1][H][2W]: 0 on the left half, on the right every channel of the mask
+ *   pixel first becomes (> 0 ? 255 : 0), then L = (19595 R + 38470 G + 7471 B + 32768) >> 16, 1 where L >= 128;
+ *   masked_image = image * (mask < 0.5 ? 1.f : 0.f).  One launch; 1 <= P, H <= 65535, n >= 1 (LR_E_ARG).
+ * Plain integer code with plain vector stores, no atomics, nothing read back: capturable, bitwise reproducible. */
+#define LR_PIL_MAX_KSIZE 1025
+typedef struct lr_pil_job {
+  int64_t src_off;       /* byte offset of the source in the src arena */
+  int64_t tmp_off;       /* byte offset of the [hs][wd][c] intermediate in the workspace (both passes run) */
+  int64_t dst_off;       /* byte offset of the [hd][wd][c] result in dst */
+  int64_t h_off, v_off;  /* word offsets of the passes' lo / cnt / kk in the table arena */
+  int32_t hs, ws, hd, wd, c;
+  int32_t h_ksize, v_ksize; /* 0: the pass is skipped */
+  int32_t reserved;
+} lr_pil_job;
+int lr_pil_resize(const uint8_t* src, int64_t src_bytes, const int32_t* tables, const int32_t* tables_host, int64_t table_words,
+                  uint8_t* work, int64_t work_bytes, uint8_t* dst, int64_t dst_bytes, const lr_pil_job* jobs,
+                  const lr_pil_job* jobs_host, int n_jobs, lr_stream_t s);
+int lr_refill_canvas(const uint8_t* ref, const uint8_t* src, const uint8_t* mask, int P, int Sh, int Sw, int H, int W, int n,
+                     float* image, float* masked_image, float* mask_out, lr_stream_t s);
+
 /* ---- bfloat16 twins: same signatures and semantics as the fp16 entry points above, every lr_half is bfloat16 bits -------- */
 int lr_groupnorm_stats_bf16(const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, float* partials,
     lr_stream_t s);

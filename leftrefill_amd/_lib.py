@@ -117,6 +117,12 @@ class NvsJob(ctypes.Structure):
                [("lo", ctypes.c_uint8 * 32), ("hi", ctypes.c_uint8 * 32)]
 
 
+class PilJob(ctypes.Structure):
+    """struct lr_pil_job (include/leftrefill_hip.h); leftrefill_amd.refill.JOB_DTYPE is its numpy image."""
+    _fields_ = [(n, c_int64) for n in ("src_off", "tmp_off", "dst_off", "h_off", "v_off")] + \
+               [(n, ctypes.c_int32) for n in ("hs", "ws", "hd", "wd", "c", "h_ksize", "v_ksize", "reserved")]
+
+
 class OptimTensor(ctypes.Structure):
     """struct lr_optim_tensor (include/leftrefill_hip.h)."""
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("numel", ctypes.c_int64),
@@ -214,6 +220,10 @@ SIGNATURES = {
     "lr_batch_prep": [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     # added under ABI 30 as well: NVS batch assembly from raw RGBA renders (csrc/nvs_prep.hip)
     "lr_nvs_prep": [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    # added under ABI 30 as well: Pillow's resampler and the one-call inpainting canvas (csrc/pil_resample.hip)
+    "lr_pil_resize": [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int,
+                      c_void_p],
+    "lr_refill_canvas": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
 }
 INT64_RETURNS = ("lr_gemm_workspace_bytes", "lr_lpips_workspace_bytes")
 

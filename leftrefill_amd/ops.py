@@ -1095,3 +1095,38 @@ def lpips_alex(pred, origin, mask, x0, Wc, r, packed, out=None):
     a.workspace, a.workspace_bytes, a.out = _p(workspace), need, _p(out)
     _lib.check(lib.lr_lpips_alex(ctypes.byref(a), _stream()), "lpips_alex")
     return out
+
+
+PIL_MAX_KSIZE = 1025      # LR_PIL_MAX_KSIZE
+
+
+def pil_resize(src, tables, tables_host, jobs, jobs_host, n_jobs, work, dst):
+    """lr_pil_resize: `n_jobs` independent `PIL.Image.resize` jobs (bicubic / bilinear, 8-bit, 1 or 3 channels) in at most two launches.
+    src: the uint8 source arena on the device; tables / tables_host: the int32 coefficient arena on the device and in host memory;
+    jobs / jobs_host: the uint8 image of the lr_pil_job table on the device and in host memory (leftrefill_amd.refill.ResizeTable
+    builds both); work: the uint8 workspace of the intermediates; dst: the uint8 destination, which is returned.  Nothing is read back."""
+    lib = _lib.load()
+    for t, name in ((src, "src"), (work, "work"), (dst, "dst"), (jobs, "jobs")):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous(), f"{name}: contiguous cuda uint8"
+    assert tables.is_cuda and tables.dtype == torch.int32 and tables.is_contiguous(), "tables: contiguous cuda int32"
+    assert not tables_host.is_cuda and tables_host.dtype == torch.int32 and tables_host.numel() == tables.numel(), "tables_host: tables in host memory"
+    assert not jobs_host.is_cuda and jobs_host.dtype == torch.uint8 and jobs_host.numel() == jobs.numel(), "jobs_host: jobs in host memory"
+    assert jobs.numel() >= n_jobs * ctypes.sizeof(_lib.PilJob), "jobs: n_jobs lr_pil_job"
+    _lib.check(lib.lr_pil_resize(_p(src), src.numel(), _p(tables), _p(tables_host), tables.numel(), _p(work), work.numel(), _p(dst),
+                                 dst.numel(), _p(jobs), _p(jobs_host), int(n_jobs), _stream()), "pil_resize")
+    return dst
+
+
+def refill_canvas(ref, src, mask, H, W, n):
+    """lr_refill_canvas: uint8 [P,Sh,Sw,3] reference, source and mask (resize destinations) -> the one-call route's batch of P * n
+    canvases [reference | source], edge-padded to H x 2W: (image, masked_image [P n,3,H,2W], mask [P n,1,H,2W]) fp32, NCHW."""
+    lib = _lib.load()
+    P, Sh, Sw, _ = ref.shape
+    for t, name in ((ref, "ref"), (src, "src"), (mask, "mask")):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and tuple(t.shape) == (P, Sh, Sw, 3), f"{name}: contiguous cuda uint8 [P,Sh,Sw,3]"
+    image = torch.empty(P * n, 3, H, 2 * W, device=ref.device, dtype=torch.float32)
+    masked_image = torch.empty_like(image)
+    mask_out = torch.empty(P * n, 1, H, 2 * W, device=ref.device, dtype=torch.float32)
+    _lib.check(lib.lr_refill_canvas(_p(ref), _p(src), _p(mask), P, Sh, Sw, int(H), int(W), int(n), _p(image), _p(masked_image), _p(mask_out),
+                                    _stream()), "refill_canvas")
+    return image, masked_image, mask_out
