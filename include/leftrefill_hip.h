@@ -796,6 +796,44 @@ int lr_pil_resize(const uint8_t* src, int64_t src_bytes, const int32_t* tables, 
 int lr_refill_canvas(const uint8_t* ref, const uint8_t* src, const uint8_t* mask, int P, int Sh, int Sw, int H, int W, int n,
                      float* image, float* masked_image, float* mask_out, lr_stream_t s);
 
+/* ---- the training logger's image grid and token drift (leftrefill_amd/imagelog.py, dropin inpainting_ldm/logger.py) on the device (added
+ *      under ABI 30 like lr_batch_prep: two new symbols, nothing renumbered or re-typed; a library without them fails to bind) -------------
+ * replaces: the host work of the reference's image logger --
+ *             `.detach().cpu()`, `torch.clamp(-1, 1)` of every logged batch                               inpainting_ldm/logger.py:93-98
+ *             `torchvision.utils.make_grid(images[k], nrow=1)`, `(grid + 1.0) / 2.0`, the transposes,
+ *             `(grid * 255).astype(np.uint8)`, `np.concatenate(grids, axis=1)`                                                  :60-67
+ *             `sqrt(sum((old[j] - weight[j])**2)).item()` per token and the re-clone of the snapshot                         :118-123
+ *           in this tree leftrefill_amd/imagelog.py (grid_numpy, token_drift_numpy) states the arithmetic and is the yardstick.
+ * lr_image_grid: n_sources (1 .. LR_GRID_MAX_SOURCES) batches of N images, H rows each -> ONE uint8 canvas out [Hc][Wc][3] in one launch.
+ *   N == 1: Hc = H and a source of width W owns the canvas columns col .. col + W - 1 (make_grid returns a single image unpadded).
+ *   N > 1:  Hc = N (H + 2) + 2 and a source owns col .. col + W + 3: image k at canvas rows k (H + 2) + 2 .., columns col + 2 ..;
+ *           every other pixel of the canvas, the columns no source owns included, is padding (value 0).
+ *   A source is read in place through its ELEMENT strides: value(k, c, y, x) = ptr[k stride_n + c stride_c + y stride_h + x stride_w] of
+ *   kind LR_EVAL_PRED_F32 / _F16 / _BF16 (16-bit values are widened to fp32 first); C == 1 is repeated to three channels.  An NHWC view
+ *   (stride_c = 1, stride_w = 3) and an NCHW tensor share a launch; the caller vouches that N, C, H, W and the strides stay inside the
+ *   source's buffer.
+ *   Per byte, fp32, in this order and never contracted: v = clamp ? min(max(v, -1), 1) : v;  v = rescale ? (v + 1) / 2 : v;  v = v * 255;
+ *   truncation towards zero (padding: grey 127 with rescale, 0 without).  Without clamp, what falls outside 0 .. 255 saturates and a
+ *   NaN's byte is unspecified (the numpy statement refuses both); with clamp a NaN becomes 0.
+ *   out needs no alignment: bytes in front of the first and behind the last 4-byte-aligned address are byte stores, the rest dword stores.
+ *   LR_E_ARG, before any launch: a null pointer, n_sources outside 1 .. LR_GRID_MAX_SOURCES, N < 1, H < 1, Wc < 1, a kind outside the
+ *   three, C outside {1, 3}, W < 1, a column range that leaves 0 .. Wc - 1 or overlaps another source's, a canvas of 2^31 bytes or more.
+ * lr_token_drift: old_, new_ fp32 [T][D], contiguous and distinct -> out[t] = sqrt(sum_d (old_[t][d] - new_[t][d])^2), fp32, summed in a
+ *   fixed order (lane l of one wave adds elements l, l + 64, ... -- groups of four when D % 4 == 0 and both pointers are 16-byte aligned --
+ *   then a butterfly over the lanes), and new_ copied into old_ in the same pass.  LR_E_ARG: a null pointer, T < 1, D < 1, old_ == new_.
+ * Plain vector and byte stores from C++, no atomics, no allocation, nothing read back: capturable, bitwise reproducible. */
+#define LR_GRID_MAX_SOURCES 8
+typedef struct lr_grid_source {
+  const void* ptr;       /* element (0, 0, 0, 0) of the batch */
+  int32_t kind;          /* LR_EVAL_PRED_F32 | _F16 | _BF16 */
+  int32_t C;             /* 1 | 3 */
+  int32_t W;             /* image width */
+  int32_t col;           /* first canvas column of this source's grid (its padding included) */
+  int64_t stride_n, stride_c, stride_h, stride_w;   /* in elements */
+} lr_grid_source;
+int lr_image_grid(const lr_grid_source* sources, int n_sources, int N, int H, int clamp, int rescale, uint8_t* out, int Wc, lr_stream_t s);
+int lr_token_drift(float* old_, const float* new_, int T, int D, float* out, lr_stream_t s);
+
 /* ---- bfloat16 twins: same signatures and semantics as the fp16 entry points above, every lr_half is bfloat16 bits -------- */
 int lr_groupnorm_stats_bf16(const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, float* partials,
     lr_stream_t s);

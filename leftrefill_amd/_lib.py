@@ -123,6 +123,12 @@ class PilJob(ctypes.Structure):
                [(n, ctypes.c_int32) for n in ("hs", "ws", "hd", "wd", "c", "h_ksize", "v_ksize", "reserved")]
 
 
+class GridSource(ctypes.Structure):
+    """struct lr_grid_source (include/leftrefill_hip.h)."""
+    _fields_ = [("ptr", c_void_p)] + [(n, ctypes.c_int32) for n in ("kind", "C", "W", "col")] + \
+               [(n, c_int64) for n in ("stride_n", "stride_c", "stride_h", "stride_w")]
+
+
 class OptimTensor(ctypes.Structure):
     """struct lr_optim_tensor (include/leftrefill_hip.h)."""
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("numel", ctypes.c_int64),
@@ -224,6 +230,9 @@ SIGNATURES = {
     "lr_pil_resize": [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int,
                       c_void_p],
     "lr_refill_canvas": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    # added under ABI 30 as well: the training logger's image grid and token drift (csrc/image_grid.hip)
+    "lr_image_grid": [ctypes.POINTER(GridSource), c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p],
+    "lr_token_drift": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
 }
 INT64_RETURNS = ("lr_gemm_workspace_bytes", "lr_lpips_workspace_bytes")
 

@@ -1130,3 +1130,45 @@ def refill_canvas(ref, src, mask, H, W, n):
     _lib.check(lib.lr_refill_canvas(_p(ref), _p(src), _p(mask), P, Sh, Sw, int(H), int(W), int(n), _p(image), _p(masked_image), _p(mask_out),
                                     _stream()), "refill_canvas")
     return image, masked_image, mask_out
+
+
+GRID_MAX_SOURCES = 8      # LR_GRID_MAX_SOURCES
+
+
+def image_grid(sources, N, H, clamp=True, rescale=True, out=None):
+    """lr_image_grid: the logger's uint8 canvas [Hc, Wc, 3] of up to GRID_MAX_SOURCES image batches in one launch (per source
+    `make_grid(nrow=1, padding=2)`, clamp, (x + 1) / 2, * 255, truncation; leftrefill_amd.imagelog.grid_numpy states it).  sources: cuda
+    tensors [B >= N, C, H, W], C in {1, 3}, fp32 | fp16 | bf16, of ANY strides (an NHWC view, a sliced batch: read in place, never copied),
+    laid left to right; the first N images of each are used.  `out` (cuda uint8 [Hc, Wc, 3], contiguous) is filled when given.  Nothing
+    is read back."""
+    from .imagelog import canvas_layout
+    lib = _lib.load()
+    N, H = int(N), int(H)
+    for t in sources:
+        assert t.is_cuda and t.dim() == 4 and t.dtype in EVAL_PRED_KIND and t.shape[0] >= N and t.shape[2] == H, \
+            "sources: cuda [B >= N, C, H, W] fp32 / fp16 / bf16"
+    Hc, Wc, cols = canvas_layout([t.shape[3] for t in sources], N, H)
+    arr = (_lib.GridSource * max(1, len(sources)))()
+    for a, t, col in zip(arr, sources, cols):
+        a.ptr, a.kind, a.C, a.W, a.col = t.data_ptr(), EVAL_PRED_KIND[t.dtype], t.shape[1], t.shape[3], col
+        a.stride_n, a.stride_c, a.stride_h, a.stride_w = t.stride()
+    if out is None:
+        out = torch.empty(Hc, Wc, 3, device=sources[0].device, dtype=torch.uint8)
+    assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (Hc, Wc, 3) and out.is_contiguous(), f"out: cuda uint8 [{Hc}, {Wc}, 3]"
+    _lib.check(lib.lr_image_grid(arr, len(sources), N, H, int(bool(clamp)), int(bool(rescale)), _p(out), Wc, _stream()), "image_grid")
+    return out
+
+
+def token_drift(old, new, out=None):
+    """lr_token_drift: out[t] = sqrt(sum_d (old[t, d] - new[t, d])^2) and old <- new in the same launch (the logger's "log the distance,
+    then re-clone").  old, new: distinct contiguous cuda fp32 [T, D]; returns out fp32 [T] (a device tensor; `out` is filled when given)."""
+    lib = _lib.load()
+    for t, name in ((old, "old"), (new, "new")):
+        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous(), f"{name}: contiguous cuda fp32 [T, D]"
+    assert old.shape == new.shape and old.device == new.device, "old: like new"
+    T, D = new.shape
+    if out is None:
+        out = torch.empty(T, device=new.device, dtype=torch.float32)
+    assert out.is_cuda and out.dtype == torch.float32 and out.numel() == T and out.is_contiguous(), "out: fp32 [T]"
+    _lib.check(lib.lr_token_drift(_p(old), _p(new), T, D, _p(out), _stream()), "token_drift")
+    return out

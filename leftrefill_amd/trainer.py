@@ -13,11 +13,19 @@ ranks with dist.allreduce_mean_grads before the step, so every rank takes the sa
 `lr_schedulers`, `global_step`, `epoch`, `native_amp_scaling_state`), so inpainting_ldm.model.load_state_dict and
 tools/run_inpainting.py read it; `resume_from_checkpoint` continues from one.
 
+`callbacks`: objects with Lightning's hooks.  After EVERY micro-batch (accumulate_grad_batches does not thin it; on a batch that ends an
+optimizer step, after the step) each one's `on_train_batch_end(trainer, model, loss, batch, idx, 0)` is called with the in-epoch index --
+under hip_graph with the static batch -- and after each validation its `on_validation_end(trainer, model)`; a callback has either hook
+or both.  The trainer serves them `global_step`, `current_epoch`, `local_rank`, `log_every_n_steps`, `log`, `logged` (validation adds
+the means of `validation_epoch_end` as `val/<key>`) and `logger.save_dir` (= default_root_dir; the module gets the same `logger`).
+`inpainting_ldm.logger.InpaintingLogger`, `ModelCheckpoint` and `LearningRateMonitor` below are such callbacks.
+
 hip_graph=True captures training_step + backward + optimizer step of one micro-batch as one hipGraph (fixed shapes; batches must be
 dicts of tensors, which are copied into static device buffers before every replay).  It needs accumulate_grad_batches == 1 and a
 single rank.
 """
 import os
+from types import SimpleNamespace
 
 import torch
 
@@ -26,13 +34,16 @@ from . import dist as lrd
 
 class Trainer:
     def __init__(self, max_steps, accumulate_grad_batches=1, val_check_interval=None, precision=16, default_root_dir=None,
-                 resume_from_checkpoint=None, hip_graph=False, growth_interval=2000, local_rank=0, log_every_n_steps=50, verbose=True):
+                 resume_from_checkpoint=None, hip_graph=False, growth_interval=2000, local_rank=0, log_every_n_steps=50, verbose=True,
+                 callbacks=None):
         assert str(precision) in ("16", "bf16", "32"), "precision: 16 | 'bf16' | 32"
         self.max_steps, self.accumulate_grad_batches = int(max_steps), int(accumulate_grad_batches)
         self.val_check_interval, self.precision = val_check_interval, precision
         self.default_root_dir, self.resume_from_checkpoint = default_root_dir, resume_from_checkpoint
         self.hip_graph, self.growth_interval, self.local_rank = bool(hip_graph), int(growth_interval), int(local_rank)
         self.log_every_n_steps, self.verbose = log_every_n_steps, verbose
+        self.callbacks = list(callbacks or [])
+        self.logger = SimpleNamespace(save_dir=default_root_dir)      # what Lightning's `trainer.logger` / `module.logger` give a callback
         self.global_step = self.current_epoch = 0
         self.optimizer = self.lr_schedulers = None
         self.logged = {}            # last value of every logged name (device tensors stay on the device until someone reads them)
@@ -91,6 +102,9 @@ class Trainer:
     def _setup(self, model):
         model.trainer = self
         model.log, model.log_dict = self.log, self.log_dict      # Lightning's logging calls of the module's hooks
+        model.logger = self.logger
+        if not hasattr(model, "current_epoch"):      # the task models have it (ddpm.py); a bare module gets Lightning's live view
+            type(model).current_epoch = property(lambda m: getattr(m.trainer, "current_epoch", 0))
         model.train()
         conf = model.configure_optimizers()
         if isinstance(conf, tuple):
@@ -173,15 +187,20 @@ class Trainer:
                 else:
                     loss = self._micro_step(model, batch, idx)
                 micro += 1
-                if micro % self.accumulate_grad_batches:
+                stepped = micro % self.accumulate_grad_batches == 0
+                if stepped:
+                    if not self.hip_graph:
+                        self._optimizer_step()
+                    self.global_step += 1
+                    self.found_inf_history.append(self.optimizer.found_inf_tensor().clone())
+                    self.logged["loss"] = loss.detach()
+                    self.loss_history.append(loss.detach().float().clone())
+                    model.on_train_batch_end()
+                for cb in self.callbacks:
+                    if hasattr(cb, "on_train_batch_end"):
+                        cb.on_train_batch_end(self, model, loss, static if self.hip_graph else batch, idx, 0)
+                if not stepped:
                     continue
-                if not self.hip_graph:
-                    self._optimizer_step()
-                self.global_step += 1
-                self.found_inf_history.append(self.optimizer.found_inf_tensor().clone())
-                self.logged["loss"] = loss.detach()
-                self.loss_history.append(loss.detach().float().clone())
-                model.on_train_batch_end()
                 if self.verbose and self.local_rank == 0 and self.global_step % self.log_every_n_steps == 0:
                     print(f"step {self.global_step}: loss {float(loss):.5f} lr {self.optimizer.param_groups[0]['lr']:.3e} "
                           f"scale {self.optimizer.amp_state()['scale']:g}", flush=True)
@@ -203,7 +222,72 @@ class Trainer:
         with torch.no_grad():
             outs = [model.validation_step({k: (v.to(device) if torch.is_tensor(v) else v) for k, v in b.items()} if isinstance(b, dict) else b, i)
                     for i, b in enumerate(val_batches)]
-        model.validation_epoch_end(outs)
+        means = model.validation_epoch_end(outs)
+        for k, v in (means or {}).items():
+            self.logged[f"val/{k}"] = v
         self.val_results.append(outs)
         model.train(was_training)
+        for cb in self.callbacks:
+            if hasattr(cb, "on_validation_end"):
+                cb.on_validation_end(self, model)
         return outs
+
+
+class ModelCheckpoint:
+    """Keeps the best `save_top_k` checkpoints by `trainer.logged[monitor]` (what Lightning's ModelCheckpoint does for the reference's
+    train_inpainting.py:104-111): after every validation, `<dirpath>/epoch={e}-step={s}.ckpt` with the payload of `Trainer.checkpoint`
+    when the score is among the best so far, and the worst kept file deleted when a better one arrives.  save_top_k = 0 keeps none, -1
+    all.  mode: 'min' | 'max'.  Rank 0 writes and deletes.  save_last: `<dirpath>/last.ckpt` after every validation as well (the trainer's
+    own `<default_root_dir>/ckpts/last.ckpt` is written by the trainer as before, and not twice when it is the same file)."""
+
+    def __init__(self, dirpath, save_top_k, monitor, mode="min", save_last=True):
+        if mode not in ("min", "max"):
+            raise ValueError(f"ModelCheckpoint: mode {mode!r} is neither 'min' nor 'max'")
+        self.dirpath, self.save_top_k, self.monitor, self.mode, self.save_last = dirpath, int(save_top_k), monitor, mode, save_last
+        self.best_k = {}      # path -> score of the kept checkpoints
+
+    def _worse(self, a, b):
+        return a > b if self.mode == "min" else a < b
+
+    def on_validation_end(self, trainer, model):
+        if self.save_last:
+            last = os.path.join(self.dirpath, "last.ckpt")
+            own = trainer.default_root_dir and os.path.join(trainer.default_root_dir, "ckpts", "last.ckpt")
+            if not own or os.path.abspath(own) != os.path.abspath(last):
+                trainer.save_checkpoint(model, last)
+        if self.save_top_k == 0:
+            return
+        if self.monitor not in trainer.logged:
+            raise KeyError(f"ModelCheckpoint: {self.monitor!r} was not logged by the validation (logged: {sorted(trainer.logged)})")
+        score = float(trainer.logged[self.monitor])
+        path = os.path.join(self.dirpath, f"epoch={trainer.current_epoch}-step={trainer.global_step}.ckpt")
+        full = self.save_top_k > 0 and len(self.best_k) >= self.save_top_k and path not in self.best_k
+        worst = None
+        if full:
+            worst = (max if self.mode == "min" else min)(self.best_k, key=self.best_k.get)
+            if not self._worse(self.best_k[worst], score):
+                return
+        trainer.save_checkpoint(model, path)
+        self.best_k[path] = score
+        if full:
+            del self.best_k[worst]
+            if trainer.local_rank == 0 and os.path.exists(worst):
+                os.remove(worst)
+
+    @property
+    def best_model_path(self):
+        if not self.best_k:
+            return ""
+        return (min if self.mode == "min" else max)(self.best_k, key=self.best_k.get)
+
+
+class LearningRateMonitor:
+    """One `trainer.log('lr-AdamW', lr)` per optimizer step (Lightning's LearningRateMonitor names a single AdamW that way)."""
+
+    def __init__(self):
+        self._step = None
+
+    def on_train_batch_end(self, trainer, model, outputs, batch, batch_idx, dataloader_idx):
+        if trainer.global_step != self._step:      # micro-batches inside an accumulation window take no optimizer step
+            self._step = trainer.global_step
+            trainer.log("lr-AdamW", trainer.optimizer.param_groups[0]["lr"])

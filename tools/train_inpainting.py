@@ -24,7 +24,13 @@ the model's own `train_dataloader` / `val_dataloader`; with --device_prep a batc
 [-1, 1] mapping of a whole batch are one HIP kernel launch (leftrefill_amd/dataprep.py, csrc/batch_prep.hip).
 --val (with --dataset inpainting | crossview | objaverse): the `val`-mode dataset over `val_image_path` / `val_mask_path` (objaverse: `val_list`;`test_limit` images,
 batches of `val_batch_size`, default 4; `test_limit` from the model's data section, else the training config) is validated every
-`val_check_interval` steps (a fraction: of an epoch) and its metrics printed.
+`val_check_interval` steps (a fraction: of an epoch) and its metrics printed.  With --synthetic N, --val scores the first generated batch.
+The reference's callbacks (train_inpainting.py:93-138) come from the training config: `logger_freq` adds the image logger
+(`inpainting_ldm.logger.InpaintingLogger`: a JPEG grid masked_image | origin_image | pred of the current batch every `logger_freq`
+batches under <save_path>/<exp_name>/samples/train/, sampled at the model's `cfg`, and the drift of every learned token; --no_image_log
+leaves it out), `save_top_k` adds `leftrefill_amd.trainer.ModelCheckpoint` on `val/<monitor>` (`monitor`, default lpips; `monitor_mode`,
+default min) writing ckpts/epoch={e}-step={s}.ckpt next to last.ckpt; either adds the learning-rate monitor.  Without these keys nothing
+changes.
 """
 import argparse
 import importlib
@@ -102,8 +108,9 @@ def main():
     ap.add_argument("--loss_file", type=str, default=None, help="write every step's loss as a JSON list when the run ends")
     ap.add_argument("--index_file", type=str, default=None, help="write the sampler's indices, one list per epoch, as JSON when the run ends (--dataset crossview)")
     ap.add_argument("--hip_graph", action="store_true", help="replay the whole step as one hipGraph (fixed shapes)")
+    ap.add_argument("--no_image_log", action="store_true", help="no sample grids even when the config has logger_freq")
     a = ap.parse_args()
-    if (a.device_prep or a.val) and a.dataset not in ("inpainting", "crossview", "objaverse"):
+    if (a.device_prep or (a.val and not a.synthetic)) and a.dataset not in ("inpainting", "crossview", "objaverse"):
         raise SystemExit("--device_prep and --val need --dataset inpainting, --dataset crossview or --dataset objaverse")
     if a.seed is not None:
         import random
@@ -115,7 +122,7 @@ def main():
     import leftrefill_amd.dropin as dropin
     dropin.install()
     from inpainting_ldm.model import create_model, load_config, load_state_dict
-    from leftrefill_amd.trainer import Trainer
+    from leftrefill_amd.trainer import LearningRateMonitor, ModelCheckpoint, Trainer
     from tools.run_inpainting import synthetic_batches
 
     rank = int(os.environ.get("LOCAL_RANK", 0))
@@ -135,9 +142,21 @@ def main():
     if a.restore and resume is None:
         raise FileNotFoundError(last)
     bs = int(config.get("batch_size", 1))
+    # the reference's callbacks (train_inpainting.py:93-138), each behind its own config key: a config without them runs as before
+    callbacks = []
+    if "logger_freq" in config and not a.no_image_log:
+        from inpainting_ldm.logger import InpaintingLogger
+        callbacks.append(InpaintingLogger(batch_frequency=config["logger_freq"], save_dir=f"{a.exp_name}/samples",
+                                          log_images_kwargs={"unconditional_guidance_scale": model.data_cfg["cfg"]}))
+    if "save_top_k" in config:
+        callbacks.append(ModelCheckpoint(f"{a.save_path}/{a.exp_name}/ckpts", config["save_top_k"], f"val/{config.get('monitor', 'lpips')}",
+                                         config.get("monitor_mode", "min")))
+    if callbacks:
+        callbacks.append(LearningRateMonitor())
     trainer = Trainer(max_steps=int(config["max_steps"]), accumulate_grad_batches=int(config.get("accumulate_grad_batches") or 1),
                       log_every_n_steps=a.log_every_n_steps, precision=16 if a.fp16 else ("bf16" if a.bf16 else 32), default_root_dir=root,
-                      resume_from_checkpoint=resume, hip_graph=a.hip_graph, local_rank=rank)
+                      resume_from_checkpoint=resume, hip_graph=a.hip_graph, local_rank=rank, callbacks=callbacks)
+    trainer.logger.save_dir = a.save_path      # the reference's logger directory: samples land in <save_path>/<exp_name>/samples/<split>
     model.trainer = trainer      # the model's loaders read their rank here
     val_data = None
     workers = min(8, max(0, a.num_workers))
@@ -156,6 +175,8 @@ def main():
                                            num_workers=8, drop_last=True)
     elif a.synthetic:
         data = list(synthetic_batches(a.synthetic, bs, int(model.img_size), seed=rank))
+        if a.val:      # no held-out set to generate: the first generated batch is scored
+            val_data = data[:1]
     else:
         raise SystemExit("give --synthetic N, --dataset crossview, --dataset inpainting, --dataset objaverse or --dataset module:Class")
     drawn = record_draws(data.sampler) if a.index_file and a.dataset == "crossview" else None
