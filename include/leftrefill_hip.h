@@ -834,6 +834,27 @@ typedef struct lr_grid_source {
 int lr_image_grid(const lr_grid_source* sources, int n_sources, int N, int H, int clamp, int rescale, uint8_t* out, int Wc, lr_stream_t s);
 int lr_token_drift(float* old_, const float* new_, int T, int D, float* out, lr_stream_t s);
 
+/* ---- attention-map probe (leftrefill_amd/attnprobe.py, the `return_attn` surface of the drop-in; csrc/attention_probe.hip) (added
+ *      under ABI 30 like lr_image_grid: two new symbols, nothing renumbered or re-typed; a library without them fails to bind) ------------
+ * replaces: the commented-out `q @ k^T` score computation of the reference's attention modules       multiview_attention.py:333-343, 357-358
+ *
+ *   out[b, i, c] = beta * out[b, i, c]
+ *                + alpha * (1/heads) * sum_h  sum_j softmax_j(scale * q_h[b,i,:] . k_h[b,j,:]) * cols[j, c]
+ *
+ * i.e. attention with a tiny V that all samples and heads share, head-averaged; the L x L matrix is never materialised.
+ *   q, k: 16-bit, [B*Nq, >= heads*64] / [B*Nkv, >= heads*64] with row strides ldq / ldk (multiples of 8, 16-byte aligned pointers:
+ *         LR_E_ALIGN) and unit column stride -- column slices of a fused projection as lr_attention_f16 takes them; d_head = 64.
+ *   cols: the probe columns, 16-bit in the compute type, [Nkv][ldc] with 1 <= ncols <= 8 and ldc >= ncols (LR_E_ARG), 2-byte aligned.
+ *   out:  fp32 [B][Nq][ncols], contiguous, 4-byte aligned.  beta == 0: out is not read (it may hold NaNs).
+ *   Any Nq >= 1, Nkv >= 1 (LR_E_ARG otherwise, as for a null pointer); key and query tails are masked as in lr_attention_f16.
+ * QK^T and the online softmax are those of lr_attention_f16 (scale folded into Q); a block keeps its 128 queries for all heads,
+ * normalises each head by its own row sum and adds the head terms in head order in fp32: no atomics, no workspace, bit-identical
+ * from run to run, capturable. */
+int lr_attention_probe_f16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* cols, int ldc, int ncols, float* out,
+                           int B, int heads, int Nq, int Nkv, float scale, float alpha, float beta, lr_stream_t s);
+int lr_attention_probe_bf16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* cols, int ldc, int ncols, float* out,
+                            int B, int heads, int Nq, int Nkv, float scale, float alpha, float beta, lr_stream_t s);
+
 /* ---- bfloat16 twins: same signatures and semantics as the fp16 entry points above, every lr_half is bfloat16 bits -------- */
 int lr_groupnorm_stats_bf16(const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, float* partials,
     lr_stream_t s);

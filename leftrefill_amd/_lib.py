@@ -233,6 +233,9 @@ SIGNATURES = {
     # added under ABI 30 as well: the training logger's image grid and token drift (csrc/image_grid.hip)
     "lr_image_grid": [ctypes.POINTER(GridSource), c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p],
     "lr_token_drift": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
+    # added under ABI 30 as well: the attention-map probe behind return_attn (csrc/attention_probe.hip)
+    "lr_attention_probe_f16": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float,
+                               c_float, c_float, c_void_p],
 }
 INT64_RETURNS = ("lr_gemm_workspace_bytes", "lr_lpips_workspace_bytes")
 
@@ -244,7 +247,8 @@ BF16_TWINS = ["lr_groupnorm_stats", "lr_groupnorm_apply", "lr_groupnorm_apply_n"
               "lr_mv_gather_bwd", "lr_mv_scatter_bwd", "lr_attention_f16", "lr_attention_causal_f16", "lr_attention_lse_f16",
               "lr_attention_vt_f16", "lr_transpose_v_f16", "lr_attention_bwd_f16", "lr_xattn_block_f16",
               "lr_xattn_pack_vt_f16", "lr_ffn_block_f16", "lr_stin_block_f16", "lr_rowlin_f16", "lr_gn_conv_out_f16",
-              "lr_attention_causal_lse_f16", "lr_attention_causal_bwd_f16", "lr_gelu_fwd_f16", "lr_gelu_bwd_f16"]
+              "lr_attention_causal_lse_f16", "lr_attention_causal_bwd_f16", "lr_gelu_fwd_f16", "lr_gelu_bwd_f16",
+              "lr_attention_probe_f16"]
 
 
 def twin(name):

@@ -14,14 +14,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libleftrefill_hip.so")
-SOURCES = ["norm.hip", "elementwise.hip", "gemm_conv.hip", "conv_halo.hip", "attention.hip", "attention_bwd.hip", "xattn_block.hip", "xattn_block640.hip", "stin_block.hip", "rowlin.hip", "ffn_block.hip", "conv_out.hip", "eval_metrics.hip", "optim.hip", "lpips.hip", "batch_prep.hip", "nvs_prep.hip", "pil_resample.hip", "image_grid.hip"]
+SOURCES = ["norm.hip", "elementwise.hip", "gemm_conv.hip", "conv_halo.hip", "attention.hip", "attention_probe.hip", "attention_bwd.hip", "xattn_block.hip", "xattn_block640.hip", "stin_block.hip", "rowlin.hip", "ffn_block.hip", "conv_out.hip", "eval_metrics.hip", "optim.hip", "lpips.hip", "batch_prep.hip", "nvs_prep.hip", "pil_resample.hip", "image_grid.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 # attention: keep MFMA accumulators in VGPRs -- the softmax VALU stream reads every S^T value and rescales O, and
 # AGPR accumulators cost ~150 v_accvgpr_read/write per 64-key tile.
 # xattn_block640.hip is deliberately NOT listed: its kernels need up to 512 registers per lane and keep about half of them as AGPRs
 # (PRE: 256 VGPRs + 256 AGPRs); the VGPR form would confine the MFMA operands to the 256 VGPRs.  That is also why it stays a
 # translation unit of its own next to xattn_block.hip (shared code: csrc/chain_common.h).
-EXTRA = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "xattn_block.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "ffn_block.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "stin_block.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "rowlin.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "attention_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+EXTRA = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "attention_probe.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "xattn_block.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "ffn_block.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "stin_block.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "rowlin.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "attention_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
 def hipcc():
@@ -43,7 +43,7 @@ def build(force=False, verbose=True):
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     cc = hipcc()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "chain_common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(HERE, "..", "include", "leftrefill_hip.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "chain_common.h"), os.path.join(CSRC, "attention_common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(HERE, "..", "include", "leftrefill_hip.h")]
     jobs = []
     for s in SOURCES:
         src = os.path.join(CSRC, s)

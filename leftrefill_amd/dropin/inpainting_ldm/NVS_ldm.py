@@ -138,16 +138,21 @@ class NVSLDM(LatentInpaintDiffusion):
         return n, c_full, uc_full
 
     @torch.no_grad()
-    def log_images(self, batch, N=4, ddim_steps=50, ddim_eta=0.0, unconditional_guidance_scale=9.0, **kwargs):
+    def log_images(self, batch, N=4, ddim_steps=50, ddim_eta=0.0, unconditional_guidance_scale=9.0, return_attn=False, **kwargs):
+        """return_attn: adds log["att_scores"] (DDIMSampler.ddim_sampling); the separator-token UNet itself is refused by the
+        attention probe, so this serves NVS models on the plain single-view UNet."""
         log = {"masked_image": batch["masked_image"].permute(0, 3, 1, 2), "origin_image": batch["image"].permute(0, 3, 1, 2)}
         n, c_full, uc_full = self._cond_pair(batch, N)
+        attn = {"return_attn": True} if return_attn else {}
         if unconditional_guidance_scale > 1.0:
-            samples, _ = self.sample_log(cond=c_full, batch_size=n, ddim=ddim_steps is not None, ddim_steps=ddim_steps, eta=ddim_eta,
-                                         unconditional_guidance_scale=unconditional_guidance_scale, unconditional_conditioning=uc_full)
+            out = self.sample_log(cond=c_full, batch_size=n, ddim=ddim_steps is not None, ddim_steps=ddim_steps, eta=ddim_eta,
+                                  unconditional_guidance_scale=unconditional_guidance_scale, unconditional_conditioning=uc_full, **attn)
         else:      # (the reference drops c_input on this branch, 274-276)
-            samples, _ = self.sample_log(cond={k: c_full[k] for k in ("c_concat", "c_crossattn")}, batch_size=n,
-                                         ddim=ddim_steps is not None, ddim_steps=ddim_steps, eta=ddim_eta)
-        log["pred"] = self.decode_first_stage(samples)
+            out = self.sample_log(cond={k: c_full[k] for k in ("c_concat", "c_crossattn")}, batch_size=n,
+                                  ddim=ddim_steps is not None, ddim_steps=ddim_steps, eta=ddim_eta, **attn)
+        log["pred"] = self.decode_first_stage(out[0])
+        if return_attn:
+            log["att_scores"] = out[2]
         return log
 
     @torch.no_grad()

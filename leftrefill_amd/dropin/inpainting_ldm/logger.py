@@ -16,8 +16,11 @@ Same constructor arguments, defaults, methods and file names as the reference.  
 Both routes produce the same array and therefore the same file.
 
 Stated deviations: a 5-D entry [B, V, C, H, W] (the multi-view model's `reference`) is laid out as V columns where the reference's
-make_grid raises; `att_scores` are not drawn (the samplers refuse `return_attn`, so no model hands them out); `mapping_color` keeps its
-signature and imports matplotlib only when called.
+make_grid raises; `mapping_color` keeps its signature and imports matplotlib only when called; an `att_scores` entry (a list with one
+[N, h, w] map in [0, 1] per attention layer, what `log_images(return_attn=True)` hands out) is drawn as the reference draws it
+(logger.py:47-58: nearest resize, `make_grid(nrow=1, padding=2)`, viridis over [0, 1], appended to the right of the canvas) except
+that the maps are resized to the logged images' [H, W] -- the reference resizes to a fixed 512 x 512, which only concatenates with
+the other grids when H = 512.  The image keys keep their route; the attention panels are host work (matplotlib's colour map).
 """
 import os
 
@@ -29,7 +32,7 @@ from leftrefill_amd import imagelog
 
 
 def mapping_color(img, vmin, vmax, cmap="rainbow"):
-    import matplotlib.pyplot as plt      # only the att_scores branch of the reference calls this, and nothing here reaches it
+    import matplotlib.pyplot as plt      # only the att_scores panels call this
     from matplotlib import cm
     np_img = img
     if vmin is not None and vmax is not None:
@@ -71,7 +74,25 @@ class InpaintingLogger:
     # ---- the canvas ----------------------------------------------------------------------------------------------------------------------
     def canvas(self, images):
         """uint8 [Hc, Wc, 3] numpy canvas of the logged images, by the device route when every entry is a CUDA tensor and `device`."""
+        att = images.get('att_scores')
         images = {k: v for k, v in images.items() if k in imagelog.KEYS and torch.is_tensor(v)}
+        if att:
+            first = next(images[k] for k in imagelog.KEYS if k in images)
+            return np.concatenate([self._image_canvas(images), self.attention_panels(att, first.shape[-2], first.shape[-1])], axis=1)
+        return self._image_canvas(images)
+
+    def attention_panels(self, att_scores, H, W):
+        """uint8 [Hc, n (W + 2 pad), 3]: one viridis panel per attention map [N, h, w] (values in [0, 1]; the first max_images are drawn),
+        nearest-resized to [H, W] and laid out like an image key (reference logger.py:51-58)."""
+        panels = []
+        for a in att_scores:
+            a = a[:min(a.shape[0], self.max_images)].detach().float().cpu()
+            a = torch.nn.functional.interpolate(a.unsqueeze(1), size=[H, W], mode='nearest').numpy()
+            grid = imagelog.make_grid_numpy(a)[0]
+            panels.append((mapping_color(grid, 0, 1, cmap="viridis") * 255).astype(np.uint8))
+        return np.concatenate(panels, axis=1)
+
+    def _image_canvas(self, images):
         if self.device and images and all(v.is_cuda for v in images.values()):
             from leftrefill_amd import ops
             sources = [s.detach() for s in imagelog.sources_of(images, max_images=self.max_images)]
@@ -106,10 +127,10 @@ class InpaintingLogger:
             with torch.no_grad():
                 images = pl_module.log_images(batch, split=split, **self.log_images_kwargs)
 
-            if 'att_scores' in images:
-                raise NotImplementedError("InpaintingLogger: att_scores are not drawn by this build (the samplers refuse return_attn)")
             for k in images:      # views; clamp, cut to max_images and the move to the host happen where the canvas is made
-                if torch.is_tensor(images[k]):
+                if k == 'att_scores':
+                    images[k] = [a[:min(a.shape[0], self.max_images)].detach() for a in images[k]]
+                elif torch.is_tensor(images[k]):
                     images[k] = images[k][:min(images[k].shape[0], self.max_images)].detach()
 
             if pl_module.local_rank == 0:

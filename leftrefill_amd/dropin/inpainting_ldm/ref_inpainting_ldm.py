@@ -63,10 +63,16 @@ class RefInpaintLDM(LatentInpaintDiffusion):
         return self.get_learned_conditioning([""] * N)
 
     @torch.no_grad()
-    def log_images(self, batch, N=4, ddim_steps=50, ddim_eta=0.0, unconditional_guidance_scale=9.0, sampler="ddim", **kwargs):
+    def log_images(self, batch, N=4, ddim_steps=50, ddim_eta=0.0, unconditional_guidance_scale=9.0, sampler="ddim", return_attn=False,
+                   **kwargs):
         """sampler: "ddim" (the reference's), "plms" or "dpm_solver"; ddim_steps is the step count of any of them.  "ddpm": the
         ancestral sampler over the full schedule (ddim_steps is ignored), which has no guidance -- unconditional_guidance_scale must
-        be 1 (or 0: the empty-prompt condition)."""
+        be 1 (or 0: the empty-prompt condition).  return_attn (the reference's keyword, passed from the config's `return_attn`; DDIM
+        only): adds log["att_scores"], the sampler's per-layer reference-attention maps (DDIMSampler.ddim_sampling)."""
+        if return_attn and sampler != "ddim":
+            raise NotImplementedError(f"log_images: return_attn is served by the DDIM sampler, not {sampler!r} (wrap the call in a "
+                                      "leftrefill_amd.attnprobe.AttentionProbe instead)")
+        attn = {"return_attn": True} if return_attn else {}
         if sampler == "ddpm" and unconditional_guidance_scale not in (0.0, 1.0):
             _ddpm_has_no_guidance(unconditional_guidance_scale)
         use_ddim = ddim_steps is not None
@@ -78,18 +84,20 @@ class RefInpaintLDM(LatentInpaintDiffusion):
         log["origin_image"] = batch['image'].permute(0, 3, 1, 2)
         if unconditional_guidance_scale > 1.0:
             uc_full = {"c_concat": [c_concat], "c_crossattn": [self.get_unconditional_conditioning(N)]}
-            samples, _ = self.sample_log(cond={"c_concat": [c_concat], "c_crossattn": [c_crossattn]}, batch_size=N,
-                                         ddim=use_ddim, ddim_steps=ddim_steps, eta=ddim_eta,
-                                         unconditional_guidance_scale=unconditional_guidance_scale,
-                                         unconditional_conditioning=uc_full, sampler=sampler)
+            out = self.sample_log(cond={"c_concat": [c_concat], "c_crossattn": [c_crossattn]}, batch_size=N,
+                                  ddim=use_ddim, ddim_steps=ddim_steps, eta=ddim_eta,
+                                  unconditional_guidance_scale=unconditional_guidance_scale,
+                                  unconditional_conditioning=uc_full, sampler=sampler, **attn)
         elif unconditional_guidance_scale == 0.0:
             uc_cross = self.get_unconditional_conditioning(N)
-            samples, _ = self.sample_log(cond={"c_concat": [c_concat], "c_crossattn": [uc_cross]}, batch_size=N,
-                                         ddim=use_ddim, ddim_steps=ddim_steps, eta=ddim_eta, sampler=sampler)
+            out = self.sample_log(cond={"c_concat": [c_concat], "c_crossattn": [uc_cross]}, batch_size=N,
+                                  ddim=use_ddim, ddim_steps=ddim_steps, eta=ddim_eta, sampler=sampler, **attn)
         else:
-            samples, _ = self.sample_log(cond={"c_concat": [c_concat], "c_crossattn": [c_crossattn]}, batch_size=N,
-                                         ddim=use_ddim, ddim_steps=ddim_steps, eta=ddim_eta, sampler=sampler)
-        log["pred"] = self.decode_first_stage(samples)
+            out = self.sample_log(cond={"c_concat": [c_concat], "c_crossattn": [c_crossattn]}, batch_size=N,
+                                  ddim=use_ddim, ddim_steps=ddim_steps, eta=ddim_eta, sampler=sampler, **attn)
+        log["pred"] = self.decode_first_stage(out[0])
+        if return_attn:
+            log["att_scores"] = out[2]
         return log
 
     @torch.no_grad()

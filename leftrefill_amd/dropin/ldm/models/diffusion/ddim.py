@@ -180,12 +180,15 @@ class DDIMSampler(CFGModelEval):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
-               unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None, **kwargs):
+               unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None, return_attn=False, **kwargs):
+        """return_attn: also return `att_scores` (reference ddim.py:139-141), see `ddim_sampling`."""
         self._warn_conditioning_count(conditioning, batch_size, dict_only=True)
         if quantize_x0 or score_corrector is not None or dynamic_threshold is not None or noise_dropout > 0.:
             raise NotImplementedError("quantize_x0 / score_corrector / dynamic_threshold / noise_dropout are unused")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
+        if isinstance(conditioning, list) and return_attn:
+            _unsupported("DDIMSampler", "return_attn with list conditioning (ddim_multi_sampling)")
         if isinstance(conditioning, list):       # NVS consistency sampler (ddim.py:103-120)
             return self.ddim_multi_sampling(conditioning, (batch_size, C, H, W), callback=callback, temperature=temperature,
                                             x_T=x_T, unconditional_guidance_scale=unconditional_guidance_scale,
@@ -194,12 +197,47 @@ class DDIMSampler(CFGModelEval):
         return self.ddim_sampling(conditioning, (batch_size, C, H, W), callback=callback, img_callback=img_callback,
                                   mask=mask, x0=x0, temperature=temperature, x_T=x_T, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning, ucg_schedule=ucg_schedule)
+                                  unconditional_conditioning=unconditional_conditioning, ucg_schedule=ucg_schedule,
+                                  return_attn=return_attn)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, callback=None, timesteps=None, mask=None, x0=None,
                       img_callback=None, log_every_t=100, temperature=1., unconditional_guidance_scale=1.,
-                      unconditional_conditioning=None, ucg_schedule=None, **kwargs):
+                      unconditional_conditioning=None, ucg_schedule=None, return_attn=False, **kwargs):
+        """return_attn: returns (samples, intermediates, att_scores) as the reference does (ddim.py:298-300).  att_scores: a list over
+        the UNet's self-attention layers (execution order) of fp32 [b, h_l, w_l] device tensors -- the step mean of the head-averaged
+        attention mass every query puts on the reference (left) half of the canvas, recorded by a leftrefill_amd.attnprobe.AttentionProbe
+        around the loop (the UNet then runs its eager route) and, under guidance, folded like the reference's scores:
+        a_uncond + scale (a_cond - a_uncond) (ddim.py:338-340; once after the step mean, which equals the per-step fold at a constant
+        scale -- hence no ucg_schedule)."""
+        probe = contextlib.nullcontext()
+        if return_attn:
+            if ucg_schedule is not None:
+                _unsupported("DDIMSampler", "return_attn together with ucg_schedule (the maps are folded once, at one guidance scale)")
+            from leftrefill_amd.attnprobe import AttentionProbe
+            probe = AttentionProbe(self._unet())
+        with probe:
+            img, intermediates = self._ddim_loop(cond, shape, x_T, callback, timesteps, mask, x0, img_callback, log_every_t, temperature,
+                                                 unconditional_guidance_scale, unconditional_conditioning, ucg_schedule)
+        if return_attn:
+            return img, intermediates, self._att_scores(probe, shape[0], unconditional_guidance_scale, unconditional_conditioning)
+        return img, intermediates
+
+    @staticmethod
+    def _att_scores(probe, b, scale, unconditional_conditioning):
+        """The probe's per-layer reference-mass maps as the reference's `att_scores`; the [uncond; cond] halves of a guided batch
+        (uncond first, `_prepare_cfg_inputs`) are folded with fold_cfg."""
+        from leftrefill_amd.attnprobe import fold_cfg
+        guided = unconditional_conditioning is not None and float(scale) != 1.
+        maps = []
+        for l in probe.recorded:
+            m = probe.mass(l)
+            assert m.shape[0] == (2 * b if guided else b), f"layer {l}: {m.shape[0]} maps for batch {b}"
+            maps.append(fold_cfg(m[:b], m[b:], float(scale)) if guided else m)
+        return maps
+
+    def _ddim_loop(self, cond, shape, x_T, callback, timesteps, mask, x0, img_callback, log_every_t, temperature,
+                   unconditional_guidance_scale, unconditional_conditioning, ucg_schedule):
         device = self.model.betas.device
         b = shape[0]
         img = torch.randn(shape, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)

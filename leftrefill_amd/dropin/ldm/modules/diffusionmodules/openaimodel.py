@@ -577,6 +577,19 @@ class UNetModel(nn.Module):
             raise NotImplementedError("gradient w.r.t. the noisy latent is not produced (p_losses feeds x_noisy without grad)")
         context = context.to(self.compute_dtype).contiguous()
         c_input = kwargs.get("c_input")
+        probe = engine.PROBE
+        if probe is not None and probe.begin_step(self):
+            # an active leftrefill_amd.attnprobe.AttentionProbe on this UNet: the eager route below (never the captured graph), each
+            # selected self-attention followed by its probe launch
+            ok = False
+            try:
+                with torch.no_grad():
+                    out = self._run_plan(x, timesteps, context, self._context_kv(context), c_input=c_input,
+                                         emb_all=self._emb_rows(timesteps, x.shape[0]))
+                ok = True
+            finally:
+                probe.end_step(ok)
+            return out
         if self._needs_autograd(context, c_input):
             # training (frozen weights, gradient flows to `context` and / or to the refinement branch behind `c_input`,
             # NVS_ldm.py:64-68): eager launches through leftrefill_amd.train_ops, torch.autograd records the HIP backward

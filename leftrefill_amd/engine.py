@@ -412,6 +412,12 @@ def resblock(act: Act, pr: PackedRes, emb_out):
     return conv(h, pr.c2, resid=resid, gn_stats=True)
 
 
+# The active leftrefill_amd.attnprobe.AttentionProbe, or None (the default: every launch is the usual one).  While it is set, the
+# self-attentions of a single-view block also launch ops.attention_probe on their q|k|v projection, and UNetModel.forward runs eager
+# (no captured graph, no CFG shared prefix: a probed self-attention always sees the full batch).
+PROBE = None
+
+
 def attention_plain(x, ctx, pa: PackedAttn, B, L, Lc=None):
     """CrossAttention.forward on its own (attention.py:165-196): to_out(attention(x Wq, c Wk, c Wv)), c = x when self."""
     if pa.is_self:
@@ -429,6 +435,8 @@ def self_attention(x, st, pn, pa: PackedAttn, B, L, want_stats=False, qkv=None, 
         n, x = ops.layer_norm_fork(x, pn.g, pn.b, pn.eps)      # the residual's gradient joins inside the LayerNorm backward kernel
         qkv = linear(n, pa.qkv)
     qkv = ln_linear(x, st, pn, pa.qkv, wide=wide) if qkv is None else qkv
+    if PROBE is not None:
+        PROBE.record(qkv, B, pa.heads, L, pa.dim_head ** -0.5)
     a = ops.attention_qkv(qkv, B, pa.heads, L, pa.dim_head ** -0.5)
     return linear(a, pa.out, resid=x, want_stats=want_stats)
 
@@ -470,6 +478,8 @@ def self_then_cross_attention(x, st, pt, N, L, Lc, kv, want_stats, dup=False, qk
         x = dup2(x)
     else:
         qkv = ln_linear(x, st, pt.n1, pa1.qkv, wide="qkv") if qkv0 is None else qkv0
+        if PROBE is not None:
+            PROBE.record(qkv, N, pa1.heads, L, pa1.dim_head ** -0.5)
         a = ops.attention_qkv(qkv, N, pa1.heads, L, pa1.dim_head ** -0.5)
     return ops.xattn_block(x, pa2.xq_pi, pa2.q.bf, kv[2], kv[3], pa2.xwo, pa2.out.b, HW=L, heads=pa2.heads, Lc=Lc, eps=pa2.q.eps,
                            scale=pa2.dim_head ** -0.5, want_stats=want_stats, pre=(a, pa1.out.w, pa1.out.b))
@@ -786,6 +796,8 @@ def spatial_transformer(act: Act, ctx, Lc, ps: PackedST, kv_cache=None, dup=Fals
         assert st_dup_ok(ps)
         x_in = dup2(x_in)
         act = Act(x_in, 2 * act.N, act.H, act.W)
+    if PROBE is not None:
+        PROBE.canvas = (act.H, act.W)      # the canvas the tokens of this SpatialTransformer's self-attentions lie on
     want = gn_fuse_ok(h)      # inference: proj_out rides behind the last feed-forward (fused block / composed GEMM) with GroupNorm sums
     for i, pt in enumerate(ps.blocks):
         kv = kv_cache[pt.kv_slot] if kv_cache is not None else None

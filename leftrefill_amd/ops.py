@@ -595,6 +595,28 @@ def attention_qkv(qkv, B, heads, L, scale):
     return attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, heads, L, L, scale)
 
 
+def attention_probe(q, k, cols, B, heads, Nq, Nkv, scale, out=None, alpha=1.0, beta=0.0):
+    """lr_attention_probe_f16: out[b, i, c] = beta out[b, i, c] + alpha mean_h sum_j softmax_j(scale q_h[b,i] . k_h[b,j]) cols[j, c].
+
+    q [B*Nq, >= heads*64], k [B*Nkv, >= heads*64]: 16-bit, strided rows, unit column stride (column slices of a fused projection, as
+    `attention` takes them).  cols [Nkv, ncols <= 8] in q's dtype (any row stride), shared by samples and heads.  out: contiguous fp32
+    [B, Nq, ncols], made here when None (then beta must be 0); with beta == 0 it is not read.  leftrefill_amd.attnprobe.probe_reference
+    states the arithmetic."""
+    lib = _lib.load()
+    for t_ in (q, k, cols):
+        assert t_.is_cuda and t_.dtype == q.dtype and q.dtype in HALF_TYPES and t_.dim() == 2 and t_.stride(1) == 1
+    assert cols.shape[0] == Nkv, "cols: [Nkv, ncols]"
+    ncols = cols.shape[1]
+    if out is None:
+        assert beta == 0.0, "beta != 0 needs the tensor to accumulate into"
+        out = torch.empty(B, Nq, ncols, device=q.device, dtype=torch.float32)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * Nq * ncols, "out: fp32 [B, Nq, ncols]"
+    _lib.check(_fn(lib, "lr_attention_probe_f16", q.dtype)(_p(q), q.stride(0), _p(k), k.stride(0), _p(cols), cols.stride(0), ncols, _p(out),
+                                                          B, heads, Nq, Nkv, float(scale), float(alpha), float(beta), _stream()),
+               "attention_probe")
+    return out
+
+
 def attention_q_kv(q, kv, B, heads, Nq, Nkv, scale, vt=None):
     """Cross-attention: q [B*Nq, C], fused context projection kv [B*Nkv, 2C] (k | v column blocks); vt: optional cached
     transpose_v of the v block (the context is constant over the DDIM steps)."""

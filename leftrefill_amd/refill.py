@@ -298,9 +298,10 @@ def _rgb(img):
     return np.asarray(img.convert("RGB"))
 
 
-def sample_latents(model, image, masked_image, mask, txt, steps, scale, seeds, num_samples, sampler=None):
+def sample_latents(model, image, masked_image, mask, txt, steps, scale, seeds, num_samples, sampler=None, attn=None):
     """The reference's `inpaint` 88-130 on a prepared batch (NCHW fp32 device tensors of P * num_samples canvases): conditioning, the
-    seeded start code, DDIM at eta 1 with classifier-free guidance, the VAE decode.  -> the decoded prediction [N,3,H,2W]."""
+    seeded start code, DDIM at eta 1 with classifier-free guidance, the VAE decode.  -> the decoded prediction [N,3,H,2W].
+    attn: a dict to fill with the reference-attention maps of the sampling (`refill(return_attn=True)`), or None."""
     import torch
     import torch.nn.functional as F
     from ldm.models.diffusion.ddim import DDIMSampler
@@ -322,12 +323,24 @@ def sample_latents(model, image, masked_image, mask, txt, steps, scale, seeds, n
     start = np.concatenate([np.random.RandomState(s).randn(num_samples, 4, h, w) for s in seeds], axis=0)
     start = torch.from_numpy(start).to(device=image.device, dtype=torch.float32)
     sampler = DDIMSampler(model) if sampler is None else sampler
-    samples, _ = sampler.sample(steps, N, [model.channels, h, w], cond, verbose=False, eta=1.0, unconditional_guidance_scale=scale,
-                                unconditional_conditioning=uc_full, x_T=start)
+    import contextlib
+    probe = contextlib.nullcontext()
+    if attn is not None:
+        from .attnprobe import AttentionProbe
+        probe = AttentionProbe(model.model.diffusion_model)
+    with probe:
+        samples, _ = sampler.sample(steps, N, [model.channels, h, w], cond, verbose=False, eta=1.0, unconditional_guidance_scale=scale,
+                                    unconditional_conditioning=uc_full, x_T=start)
+    if attn is not None:
+        # the conditional half of the guided [uncond; cond] batch (all of it at scale 1): the maps of the pass that saw the prompt
+        rows = slice(N, 2 * N) if float(scale) != 1. else slice(0, N)
+        attn["mass"] = [probe.mass(l)[rows][:, :, probe.raw(l).shape[2] // 2:2 * (probe.raw(l).shape[2] // 2)] for l in probe.recorded]
+        attn["correspondence"] = [probe.correspondence(l)[rows] for l in probe.recorded]
     return model.decode_first_stage(samples)
 
 
-def refill(model, source, mask, reference, steps=50, scale=2.5, seed=0, num_samples=1, size=512, device_prep=True, sampler=None):
+def refill(model, source, mask, reference, steps=50, scale=2.5, seed=0, num_samples=1, size=512, device_prep=True, sampler=None,
+           return_attn=False):
     """Fill the masked part of `source` guided by `reference`: `predict` of the reference's ref_inpainting_gradio.py.
 
     source, mask, reference: PIL images or uint8 arrays (`.convert("RGB")` is host work on both routes), or lists of equal length: a
@@ -342,7 +355,13 @@ def refill(model, source, mask, reference, steps=50, scale=2.5, seed=0, num_samp
     an image whose resize the library refuses is resized on the host and uploaded.  device_prep=False: `prepare_numpy` / `finish_numpy`
     with Pillow doing the resizes; the stages between are the same code, and the two routes return the same bytes.
     `steps` goes to DDIM's uniform schedule as it is: the stride `1000 // steps` must keep the last timestep inside the table (50, 20,
-    4 do; 3 does not, here as in the reference).  `sampler` is reserved: a ready `DDIMSampler(model)` to reuse, nothing else."""
+    4 do; 3 does not, here as in the reference).  `sampler` is reserved: a ready `DDIMSampler(model)` to reuse, nothing else.
+
+    return_attn=True: returns `(images, attn)`; the sampling runs under a leftrefill_amd.attnprobe.AttentionProbe (the UNet's eager
+    route: same launches, same images).  attn = {"mass": [...], "correspondence": [...]}: per self-attention layer of the UNet (execution
+    order) a CUDA tensor [N, h, w // 2] over the (padded, `plan`) target half of the latent canvas -- how much of its attention each
+    target token puts on the reference half, head and step mean of the prompted pass -- and [N, h, w // 2, 2], the (x, y) inside the reference half it looks at (token units, nan where
+    the mass is 0); N = all samples of all pairs, in the order of the returned images.  Nothing is read back."""
     import torch
     from PIL import Image
 
@@ -367,7 +386,8 @@ def refill(model, source, mask, reference, steps=50, scale=2.5, seed=0, num_samp
         else:
             parts = [prepare_numpy(s, m, r, size, n, resize=resize_pil) for s, m, r in zip(sources, masks, references)]
             image, masked_image, mask_t = (torch.from_numpy(np.concatenate([p[k] for p in parts], axis=0)).to(device) for k in range(3))
-        pred = sample_latents(model, image, masked_image, mask_t, txt, steps, scale, seeds, n, sampler)
+        attn = {} if return_attn else None
+        pred = sample_latents(model, image, masked_image, mask_t, txt, steps, scale, seeds, n, sampler, attn=attn)
         if device_prep:
             arrays = finish_device(pred, image, mask_t, out_whs)
         else:
@@ -377,4 +397,5 @@ def refill(model, source, mask, reference, steps=50, scale=2.5, seed=0, num_samp
                                        resize=resize_pil)
     images = [Image.fromarray(a) for a in arrays]
     groups = [images[i * n:(i + 1) * n] for i in range(P)]
-    return groups[0] if single else groups
+    out = groups[0] if single else groups
+    return (out, attn) if return_attn else out

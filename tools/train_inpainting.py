@@ -147,7 +147,8 @@ def main():
     if "logger_freq" in config and not a.no_image_log:
         from inpainting_ldm.logger import InpaintingLogger
         callbacks.append(InpaintingLogger(batch_frequency=config["logger_freq"], save_dir=f"{a.exp_name}/samples",
-                                          log_images_kwargs={"unconditional_guidance_scale": model.data_cfg["cfg"]}))
+                                          log_images_kwargs={"return_attn": config.get("return_attn", False),
+                                                             "unconditional_guidance_scale": model.data_cfg["cfg"]}))
     if "save_top_k" in config:
         callbacks.append(ModelCheckpoint(f"{a.save_path}/{a.exp_name}/ckpts", config["save_top_k"], f"val/{config.get('monitor', 'lpips')}",
                                          config.get("monitor_mode", "min")))
