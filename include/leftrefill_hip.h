@@ -855,6 +855,33 @@ int lr_attention_probe_f16(const lr_half* q, int ldq, const lr_half* k, int ldk,
 int lr_attention_probe_bf16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* cols, int ldc, int ncols, float* out,
                             int B, int heads, int Nq, int Nkv, float scale, float alpha, float beta, lr_stream_t s);
 
+/* ---- LoRA on the attention / GEGLU Linears (added under ABI 30; csrc/lora.hip) ---------------------------------------------------------
+ * replaces: LoraInjectedLinear.forward (inpainting_ldm/lora.py:28-33) `linear(x) + lora_up(lora_down(x)) * scale` and its autograd
+ *           backward for the factors, and, for sampling, the fold W + scale * up . down into the weight the packers read.
+ * R is the PADDED rank of the 16-bit kernels: 32 or 64 (LR_E_UNSUPPORTED otherwise); the caller pads the factors with zero rows / columns.
+ * 16-bit operands: unit column stride, row strides multiples of 8, 16-byte aligned pointers (LR_E_ALIGN); K, N, C multiples of 8; any M >= 1.
+ *
+ *   lr_lora_down   t[M][R] = 16-bit(alpha * x[M][K] . a[R][K]^T)            fp32 accumulation on the matrix cores, one rounding
+ *   lr_lora_up     y[M][N] = 16-bit((accumulate ? y : 0) + t[M][R] . u[N][R]^T)   fp32 add to the stored y, one rounding; ldy >= N lets a
+ *                            call land in a column range of a wider buffer
+ *   lr_lora_wgrad  d[R][C] = alpha * p[M][R]^T . q[M][C]  (fp32, row stride ldd % 4 == 0)   the sum over the M rows is split over
+ *                            workgroups into fp32 partials in `workspace` (>= lr_lora_wgrad_workspace_bytes(M, R, C) bytes, 16-byte
+ *                            aligned; LR_E_ARG when smaller) and added in split order by a second launch: no atomics, bit-identical from
+ *                            run to run; the split is a function of (M, C) alone
+ *   lr_lora_merge_f32  w_eff[N][K] = w[N][K] + alpha * b[N][R] . a[R][K]   all fp32, contiguous, 1 <= R <= 64 (the TRUE rank, no padding),
+ *                            K % 4 == 0; terms added in r order by fmaf; an element whose low-rank sum is zero (up == 0)
+ *                            keeps the bits of w; w_eff may be w. */
+int lr_lora_down_f16(const lr_half* x, int ldx, const lr_half* a, int lda, lr_half* t, int ldt, int M, int K, int R, float alpha, lr_stream_t s);
+int lr_lora_up_f16(const lr_half* t, int ldt, const lr_half* u, int ldu, lr_half* y, int ldy, int M, int N, int R, int accumulate, lr_stream_t s);
+int64_t lr_lora_wgrad_workspace_bytes(int M, int R, int C);
+int lr_lora_wgrad_f16(const lr_half* p, int ldp, const lr_half* q, int ldq, float* d, int ldd, int M, int R, int C, float alpha,
+                      void* workspace, int64_t workspace_bytes, lr_stream_t s);
+int lr_lora_merge_f32(const float* w, const float* b, const float* a, float* w_eff, int N, int K, int R, float alpha, lr_stream_t s);
+int lr_lora_down_bf16(const lr_half* x, int ldx, const lr_half* a, int lda, lr_half* t, int ldt, int M, int K, int R, float alpha, lr_stream_t s);
+int lr_lora_up_bf16(const lr_half* t, int ldt, const lr_half* u, int ldu, lr_half* y, int ldy, int M, int N, int R, int accumulate, lr_stream_t s);
+int lr_lora_wgrad_bf16(const lr_half* p, int ldp, const lr_half* q, int ldq, float* d, int ldd, int M, int R, int C, float alpha,
+                       void* workspace, int64_t workspace_bytes, lr_stream_t s);
+
 /* ---- bfloat16 twins: same signatures and semantics as the fp16 entry points above, every lr_half is bfloat16 bits -------- */
 int lr_groupnorm_stats_bf16(const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, float* partials,
     lr_stream_t s);

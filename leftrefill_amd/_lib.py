@@ -236,8 +236,14 @@ SIGNATURES = {
     # added under ABI 30 as well: the attention-map probe behind return_attn (csrc/attention_probe.hip)
     "lr_attention_probe_f16": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float,
                                c_float, c_float, c_void_p],
+    # added under ABI 30 as well: LoRA factor products, factor gradients and the fp32 merge (csrc/lora.hip)
+    "lr_lora_down_f16": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p],
+    "lr_lora_up_f16": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "lr_lora_wgrad_workspace_bytes": [c_int, c_int, c_int],
+    "lr_lora_wgrad_f16": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p],
+    "lr_lora_merge_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p],
 }
-INT64_RETURNS = ("lr_gemm_workspace_bytes", "lr_lpips_workspace_bytes")
+INT64_RETURNS = ("lr_gemm_workspace_bytes", "lr_lpips_workspace_bytes", "lr_lora_wgrad_workspace_bytes")
 
 # bfloat16 twins (include/leftrefill_hip.h, last section): same argument lists as the fp16 entry points
 BF16_TWINS = ["lr_groupnorm_stats", "lr_groupnorm_apply", "lr_groupnorm_apply_n", "lr_layernorm", "lr_layernorm_bwd",
@@ -248,7 +254,7 @@ BF16_TWINS = ["lr_groupnorm_stats", "lr_groupnorm_apply", "lr_groupnorm_apply_n"
               "lr_attention_vt_f16", "lr_transpose_v_f16", "lr_attention_bwd_f16", "lr_xattn_block_f16",
               "lr_xattn_pack_vt_f16", "lr_ffn_block_f16", "lr_stin_block_f16", "lr_rowlin_f16", "lr_gn_conv_out_f16",
               "lr_attention_causal_lse_f16", "lr_attention_causal_bwd_f16", "lr_gelu_fwd_f16", "lr_gelu_bwd_f16",
-              "lr_attention_probe_f16"]
+              "lr_attention_probe_f16", "lr_lora_down_f16", "lr_lora_up_f16", "lr_lora_wgrad_f16"]
 
 
 def twin(name):

@@ -11,8 +11,9 @@ configs/nvs_training_config.yaml) on the MI355X build.
 optimizer owns (`trainable_parameters`, reference 314-337); `validation_step` / `validation_epoch_end` (374-412): the right half of
 the RAW prediction (no paste: "whole image test", 380-381) scored by the HIP metrics kernel (evalglue.device_metrics).  
 `train_dataloader` / `val_dataloader` (348-372) build the Objaverse dataset (dropin dataloaders/obj_nvs_dataset.py; the DTU branches
-raise: the reference tree ships no such modules) and `on_train_batch_end` (299-306) is the mask warm-up.  The progress-bar hook and
-LoRA injection (308-312, 414-435) stay out of scope.  The shipped configs use the plain UNetModel with `use_sep: False` and no refinement; the
+raise: the reference tree ships no such modules) and `on_train_batch_end` (299-306) is the mask warm-up.  `set_lora` (154-168) injects LoRA
+layers into the UNet's attention / GEGLU Linears (inpainting_ldm/lora.py, `lora_type: 'default'`) and `configure_optimizers` gives the factors
+a parameter group of their own (`lr_lora`, `wd_lora`).  The progress-bar hook (308-312) stays out of scope.  The shipped configs use the plain UNetModel with `use_sep: False` and no refinement; the
 class is kept a drop-in for checkpoints / configs that turn them on.
 """
 import torch
@@ -85,8 +86,6 @@ class NVSLDM(LatentInpaintDiffusion):
         lora = kwargs.pop("lora", None) or {"do_lora": False}
         cond_cfg = kwargs.get("cond_stage_config")
         super().__init__(*args, **kwargs)
-        if lora.get("do_lora"):
-            raise NotImplementedError("LoRA injection (inpainting_ldm/lora.py) is out of scope of this build")
         self.loss_fn_alex = None
         self.cfg = None
         self.optim_cfg = None
@@ -106,6 +105,22 @@ class NVSLDM(LatentInpaintDiffusion):
         if self.refinement_config.get("use_input_refinement"):
             self.refinement_model = refinement_network(kwargs["unet_config"]["params"]["model_channels"])
             self.refinement_alpha = nn.Parameter(torch.tensor(0, dtype=torch.float32), requires_grad=True)
+
+    def set_lora(self):
+        """reference 154-168: inject the LoRA layers the `lora:` block asks for; called once the base weights are loaded and before the
+        optimizer is built (tools/train_inpainting.py)."""
+        self.unet_lora_params = None
+        if not self.lora_cfg.get("do_lora"):
+            return
+        from .lora import inject_trainable_lora, inject_trainable_lora_extended
+        kind = self.lora_cfg.get("lora_type", "default")
+        kw = dict(r=self.lora_cfg["lora_rank"], scale=self.lora_cfg.get("lora_scale", 1.0))
+        if kind == "default":
+            self.unet_lora_params, _ = inject_trainable_lora(self.model.diffusion_model, verbose=False, **kw)
+        elif kind == "extended":
+            inject_trainable_lora_extended(self.model.diffusion_model, **kw)      # (NotImplementedError naming the reason)
+        else:
+            raise NotImplementedError("Not implemented LoRA")
 
     def get_input(self, batch, k, cond_key=None, bs=None, return_first_stage_outputs=False, force_c_encode=True):
         x, c = super().get_input(batch, k, cond_key, bs, return_first_stage_outputs, force_c_encode)
@@ -244,9 +259,23 @@ class NVSLDM(LatentInpaintDiffusion):
         if self.optim_cfg.get("all_trainable", False):
             raise NotImplementedError("all_trainable: this build computes no weight gradients of the UNet (its backward stops at the "
                                       "activations and the context)")
-        if self.unet_lora_params is not None:
-            raise NotImplementedError("LoRA parameter group: this build computes no weight gradients, LoRA factors included")
-        return configure_prompt_optimizer(self, [{"params": self.trainable_parameters(), "lr": self.optim_cfg["learning_rate"]}])
+        groups = [{"params": self.trainable_parameters(), "lr": self.optim_cfg["learning_rate"]}]
+        if self.unet_lora_params is not None:      # reference 333-335: the factors' own learning rate and weight decay
+            import itertools
+            if getattr(getattr(self, "trainer", None), "hip_graph", False):
+                raise NotImplementedError("Trainer(hip_graph=True) with trainable LoRA factors: the factor-gradient kernels' workspaces "
+                                          "are allocated per call, the captured training step is not validated with them")
+            self.unet_lora_params = [list(g_) for g_ in self.unet_lora_params]      # (the reference's generators: walked once, kept)
+            params = list(itertools.chain(*self.unet_lora_params))
+            # the only weight gradients of this build are those of the factors of LoRA layers injected into THIS model's UNet
+            # (set_lora): any other parameter in the group would sit in the optimizer and never receive a gradient
+            injected = {id(p_) for m_ in self.model.diffusion_model.modules() if hasattr(m_, "lora_down") and hasattr(m_, "lora_up")
+                        for p_ in (m_.lora_up.weight, m_.lora_down.weight)}
+            if not params or any(id(p_) not in injected for p_ in params):
+                raise NotImplementedError("LoRA parameter group: this build computes weight gradients only for the factors of the LoRA "
+                                          "layers that set_lora() injected into this model's UNet; the group holds other parameters")
+            groups.append({"params": params, "lr": self.optim_cfg["lr_lora"], "weight_decay": self.optim_cfg["wd_lora"]})
+        return configure_prompt_optimizer(self, groups)
 
     def on_save_checkpoint(self, checkpoint):
         if self.save_prompt_only:

@@ -52,10 +52,10 @@ class GEGLU(nn.Module):
         self.proj = nn.Linear(dim_in, dim_out * 2)
 
     def forward(self, x):
-        from leftrefill_amd import packing
         tok, B, L = engine.to_tokens(x)
-        w, b = _cached(self, "geglu", lambda: packing.pack_geglu(self.proj.weight.detach(), self.proj.bias.detach()))
-        y = ops.gemm_conv(tok, w, B=1, H=1, W=tok.shape[0], taps=1, bias=b, geglu=True)
+        # (the packing and the launch of the transformer block's own feed-forward: a LoRA-injected projection runs unmerged)
+        w, b, lora = _cached(self, ("geglu", engine.compute_dtype()), lambda: engine.pack_geglu_proj(self.proj))
+        y = engine.geglu_linear(tok, w, b, lora)
         return y.reshape(B, L, -1).to(x.dtype)
 
 

@@ -265,7 +265,83 @@ class UNetModel(nn.Module):
     MAX_GRAPHS = 8        # captured step graphs kept per model (least recently used shape is dropped beyond that)
 
     def _sig(self):
-        return (self.compute_dtype,) + tuple((p.data_ptr(), p._version) for p in self.parameters())
+        if self.__dict__.get("_lora_injected"):
+            # the LoRA factors are no part of the packing's signature: a training step that moves them re-packs nothing (the merged
+            # sampling weights follow them through _select_plan)
+            ps = (p for n, p in self.named_parameters() if ".lora_down." not in n and ".lora_up." not in n)
+        else:
+            ps = self.parameters()
+        return (self.compute_dtype,) + tuple((p.data_ptr(), p._version) for p in ps)
+
+    def _lora_check(self):
+        """Called by inpainting_ldm.lora.inject_trainable_lora before it touches the model."""
+        if self.st_cls is not SpatialTransformer:
+            raise NotImplementedError("LoRA on the multi-view UNet is not implemented: its re-arranged / sharded self-attention has no "
+                                      "low-rank route")
+
+    def _on_lora_injected(self):
+        self._lora_injected = True
+        self._weights_dirty = True          # the Linears were swapped for LoraInjectedLinear modules: re-pack on the next forward
+
+    def _lora_live(self):
+        """Trainable LoRA factors under autograd: the unmerged, differentiable route."""
+        return torch.is_grad_enabled() and any(m.lora_down.weight.requires_grad or m.lora_up.weight.requires_grad
+                                               for m in self._plan["root"]["lora"])
+
+    def _select_plan(self):
+        """With injected LoRA layers the packing exists in two forms that share everything but the SpatialTransformers' records:
+        the unmerged one (`prepare`: base weights + low-rank segments, differentiable w.r.t. the factors) for a grad-enabled forward with
+        trainable factors, and the merged one (W + scale up down folded in fp32, then packed: the launch sequence of the un-injected
+        model, captured graphs included) for everything else.  The merged records are rebuilt when a factor's (data_ptr, _version)
+        changed -- and whenever an unmerged forward has run since, because the optimizer writes the factors through raw pointers."""
+        base = self._plan["root"]
+        if not base["lora"]:
+            return
+        if self._lora_live():
+            self._plan = base
+            base["merged_stale"] = True
+            return
+        lsig = tuple((p.data_ptr(), p._version) for m in base["lora"] for p in (m.lora_down.weight, m.lora_up.weight))
+        mp = base.get("merged")
+        if mp is None or base.get("merged_stale") or mp["lora_sig"] != lsig or mp["dtype"] != self.compute_dtype:
+            repl = {}
+            with engine.compute(self.compute_dtype), engine.lora_merged(), torch.no_grad():
+                for ps, layer in base["st_layers"]:
+                    new = repl[id(ps)] = engine.PackedST(layer)
+                    # proj_out composed with the last feed-forward Linear: neither is an injected layer, so the product formed once on
+                    # the unmerged record (host fp64 matmuls) serves every merge
+                    new._ff_proj = ps._build_ff_proj()
+            mp = self._merged_plan(base, repl)
+            mp["lora_sig"], mp["dtype"] = lsig, self.compute_dtype
+            base["merged"], base["merged_stale"] = mp, False      # (the previous merged records lose their last reference here)
+            self._graphs = {}               # captured steps read the previous merged weights
+        self._plan = mp
+
+    # what a merged plan shares with the unmerged one; everything else -- the previous merged plan under "merged", the training route's
+    # concatenated K/V weight, the staleness flag -- belongs to the unmerged plan alone
+    MERGED_SHARED = ("sig", "root", "lora", "st_layers", "t0", "t2", "cin_pad", "out_norm", "out_conv", "emb_w", "emb_b", "emb_total")
+
+    @classmethod
+    def _merged_plan(cls, base, repl):
+        """The merged twin of the unmerged plan `base`: the records in `repl` ({id(unmerged PackedST): merged PackedST}) in place of the
+        SpatialTransformers', every other record the same object."""
+        mp = {k: base[k] for k in cls.MERGED_SHARED}
+        for k in ("input", "output"):
+            mp[k] = [[(kind, repl.get(id(p_), p_)) for kind, p_ in steps] for steps in base[k]]
+        mp["middle"] = [(kind, repl.get(id(p_), p_)) for kind, p_ in base["middle"]]
+        mp["tblocks"] = cls._number_tblocks(mp)
+        return mp
+
+    @staticmethod
+    def _number_tblocks(plan):
+        tblocks = []
+        for steps in plan["input"] + [plan["middle"]] + plan["output"]:
+            for kind, p_ in steps:
+                if kind == "st":
+                    tblocks.extend(p_.blocks)
+        for i, pt in enumerate(tblocks):
+            pt.kv_slot = i
+        return tblocks
 
     def _load_from_state_dict(self, *args, **kwargs):
         super()._load_from_state_dict(*args, **kwargs)
@@ -296,6 +372,9 @@ class UNetModel(nn.Module):
     def _pack(self, sig):
         E = engine
         plan = {"sig": sig}
+        plan["root"] = plan                 # (a merged LoRA plan is a shallow copy that points back here, see _select_plan)
+        plan["lora"] = [m for m in self.modules() if E.is_lora(m)]
+        st_layers = plan["st_layers"] = []
         plan["t0"] = E.PackedLinear(self.time_embed[0])
         plan["t2"] = E.PackedLinear(self.time_embed[2])
         # the 9 input channels travel as 16 (32 bytes per pixel, lr_gemm_conv_f16's 16-channel gather); wider inputs pad to 64s
@@ -315,6 +394,7 @@ class UNetModel(nn.Module):
                     steps.append(("res", pr))
                 elif isinstance(layer, SpatialTransformer):
                     steps.append(("st", E.PackedST(layer)))
+                    st_layers.append((steps[-1][1], layer))
                 elif isinstance(layer, Downsample):
                     steps.append(("down", E.PackedConv(layer.op)))
                 elif isinstance(layer, Upsample):
@@ -339,14 +419,7 @@ class UNetModel(nn.Module):
             off += pr.cout
         plan["emb_total"] = off
         # cross-attention K/V projections depend only on the context: one cache slot per transformer block
-        tblocks = []
-        for steps in plan["input"] + [plan["middle"]] + plan["output"]:
-            for kind, p_ in steps:
-                if kind == "st":
-                    tblocks.extend(p_.blocks)
-        for i, pt in enumerate(tblocks):
-            pt.kv_slot = i
-        plan["tblocks"] = tblocks
+        plan["tblocks"] = self._number_tblocks(plan)
         self._plan = plan
         self._graphs = {}
         return plan
@@ -355,13 +428,17 @@ class UNetModel(nn.Module):
     def _context_kv(self, context, out=None):
         """[k;v] projections of the context for every cross-attention (attention.py:171-172).  The context is the
         same tensor for all 50 DDIM steps, so the captured step graph reads these from a per-context cache."""
-        P = self._plan
+        P, E = self._plan, engine
         N, L, D = context.shape
         ctx = context.reshape(N * L, D)
         res = []
         for i, pt in enumerate(P["tblocks"]):
             o, ot, xk, xvt = (None,) * 4 if out is None else (tuple(out[i]) + (None, None))[:4]
-            kv = ops.gemm_conv(ctx, pt.attn2.kv.w, B=1, H=1, W=N * L, taps=1, out=o)
+            if pt.attn2.kv.lora:            # unmerged LoRA factors on to_k / to_v (the sampling routes use the merged packing instead)
+                kv = E.linear(ctx, pt.attn2.kv)
+                kv = kv if o is None else o.copy_(kv)
+            else:
+                kv = ops.gemm_conv(ctx, pt.attn2.kv.w, B=1, H=1, W=N * L, taps=1, out=o)
             C = kv.shape[1] // 2
             # V^T copy for lr_attention_vt_f16 (none when the kernel reads V with the LDS transpose read, ops.ATTN_VT = 0)
             ent = (kv, ops.transpose_v(kv[:, C:], N, pt.attn2.heads, L, out=ot) if ops.ATTN_VT else None)
@@ -412,7 +489,7 @@ class UNetModel(nn.Module):
                     for j, s_ in enumerate(chunk):
                         table[s_] = rows[j]
         self._emb_table = table
-        self._emb_table_plan = self._plan      # rows belong to THIS packing: a re-pack (changed weights) drops them (see _emb_rows)
+        self._emb_table_plan = self._plan["root"]      # rows belong to THIS packing: a re-pack (changed weights) drops them (see _emb_rows)
 
     def _emb_rows(self, timesteps, N, out=None):
         """[N, sum Cout] embedding of this call: the precomputed row of the host-named timestep, else computed from `timesteps`."""
@@ -420,7 +497,7 @@ class UNetModel(nn.Module):
         # sampling loop) named; any other caller of the UNet -- a corrector, a second model evaluation, another sampler sharing the
         # model -- runs with no hint and gets the embedding computed from its `timesteps` tensor
         hint = self.__dict__.get("_t_host")
-        if self.__dict__.get("_emb_table_plan") is not self._plan:      # prepare() re-packed since the table was built: stale rows
+        if self.__dict__.get("_emb_table_plan") is not self._plan["root"]:      # prepare() re-packed since the table was built: stale rows
             self._emb_table = {}
         row = self.__dict__.get("_emb_table", {}).get(_t_key(hint)) if hint is not None else None
         if row is not None and row.dtype == self.compute_dtype:
@@ -446,16 +523,25 @@ class UNetModel(nn.Module):
         # recomputes the block in the backward (CheckpointFunction, ldm/modules/diffusionmodules/util.py:102-151) -- a memory
         # optimisation with identical results.  With 288 GB of HBM the activations simply stay resident (batch 16 at 256x512:
         # 9.2 GB peak, 30.2 ms per step); `recompute_in_backward = True` restores the reference's trade (7.6 GB, 39.4 ms).
+        lora_live = bool(P["lora"]) and P is P["root"] and self._lora_live()
+        anchor = next((p_ for m in P["lora"] for p_ in (m.lora_up.weight, m.lora_down.weight) if p_.requires_grad), None) if lora_live else None
         recompute = (self.recompute_in_backward and self.use_checkpoint and torch.is_grad_enabled()
-                     and context.requires_grad)
-        if kv_cache is None and TRAIN_KV_BATCH and torch.is_grad_enabled() and context.requires_grad and P["tblocks"]:
+                     and (context.requires_grad or lora_live))
+        if kv_cache is None and TRAIN_KV_BATCH and torch.is_grad_enabled() and (context.requires_grad or lora_live) and P["tblocks"]:
             # training: the [k;v] projections of the context for EVERY cross-attention as one GEMM (N = sum 2C = 24960 for the SD2 UNet)
             # and, in the backward, one input-gradient GEMM over the concatenated d[k;v] (K = 24960) instead of 16 + 16 launches on
             # 77 x batch rows each (24 us apiece at 16 x 77 rows) and 15 fan-in adds of the context gradient
             w_all = P.get("kv_all_w")
             if w_all is None or w_all.dtype != self.compute_dtype:
                 w_all = P["kv_all_w"] = torch.cat([pt.attn2.kv.w for pt in P["tblocks"]], 0).contiguous()
-            kv_all = ops.gemm_conv(ctx, w_all, B=1, H=1, W=N * L, taps=1)
+            segs, off = [], 0
+            for pt in P["tblocks"]:       # unmerged LoRA factors of every to_k / to_v: applied, and differentiated, in this one node too
+                segs += [(m, off + o_, n_, pm) for m, o_, n_, pm in (pt.attn2.kv.lora or ())]
+                off += pt.attn2.kv.w.shape[0]
+            if segs:
+                kv_all = ops.lora_linear(ctx, w_all, None, segs)
+            else:
+                kv_all = ops.gemm_conv(ctx, w_all, B=1, H=1, W=N * L, taps=1)
             parts = ops.split_cols(kv_all, [pt.attn2.kv.w.shape[0] for pt in P["tblocks"]])
             kv_cache = [(p_, None) for p_ in parts]
 
@@ -493,6 +579,10 @@ class UNetModel(nn.Module):
                     emb_p = emb_all[:act.N, p.emb_off:p.emb_off + p.cout]      # (both halves share the timesteps)
                     act = ckpt(lambda a_, p=p, emb_p=emb_p: E.resblock(a_, p, emb_p), act)
                 elif kind == "st":
+                    if anchor is not None and not act.tok.requires_grad:
+                        # trainable LoRA factors: the first SpatialTransformer's input depends on no trainable tensor, yet its injected
+                        # layers need the differentiable route (train_ops.grad_anchor)
+                        act = E.Act(ops.grad_anchor(act.tok, anchor), act.N, act.H, act.W, tok2=act.tok2, gs=act.gs, gs2=act.gs2)
                     act = ckpt(lambda a_, c_, p=p, d_=half: E.spatial_transformer(a_, c_, L, p, kv_cache, dup=d_), act, ctx)
                     half = False
                 elif kind == "down":
@@ -550,6 +640,8 @@ class UNetModel(nn.Module):
         return ops.nhwc_to_nchw(act.tok, N, act.H, act.W, self.out_channels)
 
     def _needs_autograd(self, context, c_input=None):
+        if self._plan is not None and self._plan["root"]["lora"] and self._lora_live():
+            return True
         return torch.is_grad_enabled() and (context.requires_grad or (c_input is not None and c_input.requires_grad))
 
     def _add_c_input(self, act, c_input):
@@ -569,6 +661,7 @@ class UNetModel(nn.Module):
         """eps = UNet(x, t, context).  Returns fp16 (the reference's output dtype under autocast, appendix B)."""
         assert y is None, "must specify y if and only if the model is class-conditional"
         self.prepare()
+        self._select_plan()
         x = x.float().contiguous()
         # the dtype decides, not the values (no host sync): integer timesteps stay int64, floating ones fp32 (continuous time)
         timesteps = timesteps.to(torch.float32 if timesteps.is_floating_point() else torch.int64).contiguous()

@@ -95,13 +95,68 @@ class PackedConv:
         self.stride = conv.stride[0]
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# LoRA (dropin inpainting_ldm/lora.py): a LoraInjectedLinear is packed in one of two forms
+#   unmerged (default): the base weight, plus `lora` segments on the Packed* record -- (module, first column, columns, row permutation
+#             of the packed weight | None) per injected Linear of a fused projection; `linear` then runs base GEMM + lr_lora_down +
+#             lr_lora_up (train_ops.lora_linear) and reads the fp32 factors at every call.  No LayerNorm-folded / k-slot copies are
+#             packed for such a layer, so every route that would skip the low-rank term is closed.
+#   merged  (inside `with lora_merged():`): W + scale * up . down, formed in fp32 by lr_lora_merge_f32 and then packed like any weight:
+#             every inference route of the un-injected model, no `lora` segments.
+# ---------------------------------------------------------------------------------------------------------------
+_LORA_MERGED = [False]
+
+
+class lora_merged:
+    def __enter__(self):
+        self.prev = _LORA_MERGED[0]
+        _LORA_MERGED[0] = True
+
+    def __exit__(self, *exc):
+        _LORA_MERGED[0] = self.prev
+
+
+def is_lora(mod):
+    return hasattr(mod, "lora_down") and hasattr(mod, "lora_up") and hasattr(mod, "linear")
+
+
+def lin_wb(mod):
+    """(weight, bias) the packers read for an nn.Linear or a LoraInjectedLinear (see above)."""
+    if not is_lora(mod):
+        return mod.weight, mod.bias
+    if not isinstance(mod.selector, torch.nn.Identity):
+        raise NotImplementedError("LoRA selector (set_selector_from_diag) is not implemented by the HIP path")
+    base = mod.linear
+    if not _LORA_MERGED[0]:
+        return base.weight, base.bias
+    return ops.lora_merge(base.weight, mod.lora_up.weight, mod.lora_down.weight, float(mod.scale)), base.bias
+
+
+def lora_segments(mods, perms=None):
+    """`lora` segments of a projection whose packed rows are the concatenated rows of `mods` (None in the merged form / nothing injected)."""
+    if _LORA_MERGED[0]:
+        return None
+    segs, off = [], 0
+    for i, m in enumerate(mods):
+        n = lin_wb(m)[0].shape[0]
+        if is_lora(m):
+            segs.append((m, off, n, None if perms is None else perms[i]))
+        off += n
+    return segs or None
+
+
 class PackedLinear:
     """norm: the nn.LayerNorm that feeds this Linear -- a second, LayerNorm-folded copy of the weights is packed next
-    to the plain one (`wf`, `bf`, `cs`, see packing.fold_layernorm) for the inference path."""
+    to the plain one (`wf`, `bf`, `cs`, see packing.fold_layernorm) for the inference path.
+    lora: segments of unmerged LoRA factors (see above); such a layer packs no folded copy."""
 
-    def __init__(self, lin=None, weight=None, bias=None, norm=None):
+    def __init__(self, lin=None, weight=None, bias=None, norm=None, lora=None):
         if lin is not None:
-            weight, bias = lin.weight, lin.bias
+            weight, bias = lin_wb(lin)
+            lora = lora_segments([lin])
+        self.lora = lora
+        if lora:
+            norm = None
         w = weight.detach()
         if w.dim() == 4:  # 1x1 conv used as a linear (use_linear_in_transformer=False)
             w = w.reshape(w.shape[0], w.shape[1])
@@ -162,20 +217,22 @@ class PackedAttn:
     def __init__(self, attn, is_self, norm=None):
         self.heads = attn.heads
         self.is_self = is_self
+        wq, wk, wv = lin_wb(attn.to_q)[0], lin_wb(attn.to_k)[0], lin_wb(attn.to_v)[0]
         if is_self:
-            self.qkv = PackedLinear(weight=torch.cat([attn.to_q.weight, attn.to_k.weight, attn.to_v.weight], 0), norm=norm)
+            self.qkv = PackedLinear(weight=torch.cat([wq, wk, wv], 0), norm=norm, lora=lora_segments([attn.to_q, attn.to_k, attn.to_v]))
         else:
-            self.q = PackedLinear(weight=attn.to_q.weight, norm=norm)
-            self.kv = PackedLinear(weight=torch.cat([attn.to_k.weight, attn.to_v.weight], 0))
+            self.q = PackedLinear(weight=wq, norm=norm, lora=lora_segments([attn.to_q]))
+            self.kv = PackedLinear(weight=torch.cat([wk, wv], 0), lora=lora_segments([attn.to_k, attn.to_v]))
         self.out = PackedLinear(attn.to_out[0])
         self.xk = None
-        if not is_self and norm is not None and attn.to_q.weight.shape[0] in ops.XATTN_WIDTHS:
+        unmerged = self.out.lora or (not is_self and (self.q.lora or self.kv.lora))      # (the fused block has no low-rank term)
+        if not is_self and norm is not None and wq.shape[0] in ops.XATTN_WIDTHS and not unmerged:
             # operands of the fused cross-attention block (lr_xattn_block_f16): to_k rows / to_out columns in its k-slot order
-            self.xk, self.xwo = packing.pack_xattn(attn.to_k.weight.detach(), attn.to_out[0].weight.detach(), compute_dtype())
+            self.xk, self.xwo = packing.pack_xattn(wk.detach(), lin_wb(attn.to_out[0])[0].detach(), compute_dtype())
             # LayerNorm-folded to_q with its columns in k-slot order: the variant that also runs the self-attention's out-projection
             # hands the normalised rows to the q projection in accumulator order
             self.xq_pi = self.q.wf[:, packing.xattn_perm(self.q.wf.shape[1], self.q.wf.device)].contiguous()
-        self.dim_head = attn.to_q.weight.shape[0] // attn.heads
+        self.dim_head = wq.shape[0] // attn.heads
         if self.dim_head != 64:
             raise RuntimeError(f"attention kernel is specialised for d_head=64 (got {self.dim_head})")
 
@@ -188,15 +245,18 @@ class PackedTBlock:
         self.attn2 = PackedAttn(blk.attn2, False, blk.norm2)
         self.n1, self.n2, self.n3 = PackedNorm(blk.norm1), PackedNorm(blk.norm2), PackedNorm(blk.norm3)
         proj = blk.ff.net[0].proj
-        self.geglu_w, self.geglu_b = packing.pack_geglu(proj.weight.detach(), proj.bias.detach(), compute_dtype())
+        pw, pb = lin_wb(proj)
+        # (unmerged LoRA on the projection: its `up` factor takes the packed (u | g interleaved) row order, `d up` the inverse; the
+        # LayerNorm-folded and fused forms of the feed-forward are closed for such a block, see _ffn)
+        self.geglu_w, self.geglu_b, self.geglu_lora = pack_geglu_proj(proj, (pw, pb))
         # LayerNorm(norm3)-folded copy of the GEGLU projection (rows in the same interleaved order)
-        wf, bf, cs = packing.fold_layernorm(proj.weight.detach(), proj.bias.detach(), blk.norm3.weight.detach(),
+        wf, bf, cs = packing.fold_layernorm(pw.detach(), pb.detach(), blk.norm3.weight.detach(),
                                             blk.norm3.bias.detach(), compute_dtype())
-        perm = packing.geglu_perm(proj.weight.shape[0] // 2, proj.weight.device)
+        perm = packing.geglu_perm(pw.shape[0] // 2, pw.device)
         self.geglu_wf, self.geglu_bf, self.geglu_cs = wf[perm].contiguous(), bf[perm].contiguous(), cs[perm].contiguous()
         self.ff2 = PackedLinear(blk.ff.net[2])
         self.ff2_x = None
-        if self.ff2.w.shape[0] == ops.FFN_C and self.ff2.w.shape[1] % 64 == 0:
+        if self.ff2.w.shape[0] == ops.FFN_C and self.ff2.w.shape[1] % 64 == 0 and not self.geglu_lora:
             # second Linear with its columns in the k-slot order of the fused feed-forward block (lr_ffn_block_f16)
             self.ff2_x = packing.pack_pieces(blk.ff.net[2].weight.detach(), compute_dtype())
         # multi-view attributes (None for the single-view block)
@@ -265,7 +325,28 @@ class PackedST:
 # ---------------------------------------------------------------------------------------------------------------
 def linear(x, pl: PackedLinear, resid=None, M=None, want_stats=False):
     M = x.shape[0] if M is None else M
+    if pl.lora:
+        # unmerged LoRA: base GEMM + low-rank products as one differentiable op (no row statistics: its consumers run their LayerNorm)
+        y = ops.lora_linear(x, pl.w, pl.b, pl.lora, resid=resid)
+        return (y, None) if want_stats else y
     return ops.gemm_conv(x, pl.w, B=1, H=1, W=M, taps=1, bias=pl.b, resid=resid, want_stats=want_stats)
+
+
+def geglu_linear(x, w, b, lora=None):
+    """GEGLU projection + gate on rows that are already normalised: w / b in the packed (u | g interleaved) order, `lora` the
+    projection's unmerged segments (PackedTBlock.geglu_lora) or None.  The one place the un-folded projection is launched from: the
+    transformer block's feed-forward (_ffn) and the stand-alone GEGLU module."""
+    if lora:
+        return ops.lora_linear(x, w, b, lora, geglu=True)
+    return ops.gemm_conv(x, w, B=1, H=1, W=x.shape[0], taps=1, bias=b, geglu=True)
+
+
+def pack_geglu_proj(proj, wb=None):
+    """(packed weight, packed bias, unmerged LoRA segments | None) of a GEGLU's `proj` (an nn.Linear or a LoraInjectedLinear); wb: its
+    `lin_wb` when the caller already has it."""
+    pw, pb = wb or lin_wb(proj)
+    w, b = packing.pack_geglu(pw.detach(), pb.detach(), compute_dtype())
+    return w, b, lora_segments([proj], [packing.geglu_perm(pw.shape[0] // 2, pw.device)])
 
 
 def fold_ok(x):
@@ -588,7 +669,11 @@ def _ffn(x, st, pt: PackedTBlock, want_stats, post=None, fused=None):
         ws = want_stats and fold_ok(x)
         y = ops.ffn_block(x, pt.geglu_wf, pt.geglu_bf, pt.ff2_x, pt.ff2.b, eps=pt.n3.eps, want_stats=ws)
         return y if ws else (y, None)
-    if fold_ok(x) and ops.rowlin_ok(x.shape[0], x.shape[1], pt.geglu_wf.shape[0], "geglu"):
+    if pt.geglu_lora:
+        # unmerged LoRA on the GEGLU projection: LayerNorm kernel, then projection + low-rank term + gate as one differentiable op
+        n3, x = ops.layer_norm_fork(x, pt.n3.g, pt.n3.b, pt.n3.eps)
+        g = geglu_linear(n3, pt.geglu_w, pt.geglu_b, pt.geglu_lora)
+    elif fold_ok(x) and ops.rowlin_ok(x.shape[0], x.shape[1], pt.geglu_wf.shape[0], "geglu"):
         # C = 640: LayerNorm + GEGLU projection + gate with the rows resident in registers (lr_rowlin_f16)
         g = ops.rowlin(x, pt.geglu_wf, pt.geglu_bf, eps=pt.n3.eps, geglu=True)
     elif st is not None:
@@ -596,7 +681,7 @@ def _ffn(x, st, pt: PackedTBlock, want_stats, post=None, fused=None):
                           ln=(st, pt.n3.eps, pt.geglu_cs))
     else:
         n3, x = (ops.layer_norm_fork if TRAIN_FORK else (lambda *a_: (ops.layer_norm(*a_), x)))(x, pt.n3.g, pt.n3.b, pt.n3.eps)      # (training: the residual below takes the fork's x)
-        g = ops.gemm_conv(n3, pt.geglu_w, B=1, H=1, W=n3.shape[0], taps=1, bias=pt.geglu_b, geglu=True)
+        g = geglu_linear(n3, pt.geglu_w, pt.geglu_b)
     if compose:
         # SpatialTransformer.proj_out behind the block: (Wp W2) g + Wp x + b' + x_in in one GEMM over [g | x] (PackedST.ff_proj_w)
         _, wc, bc, x_in, hw = post

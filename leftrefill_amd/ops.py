@@ -1194,3 +1194,96 @@ def token_drift(old, new, out=None):
     assert out.is_cuda and out.dtype == torch.float32 and out.numel() == T and out.is_contiguous(), "out: fp32 [T]"
     _lib.check(lib.lr_token_drift(_p(old), _p(new), T, D, _p(out), _stream()), "token_drift")
     return out
+
+
+# ---- LoRA (csrc/lora.hip) -------------------------------------------------------------------------------------------
+LORA_GRANULE = 32      # rank granule of the 16-bit LoRA kernels: the factors are zero-padded to 32 or 64
+
+
+def lora_pad_rank(r):
+    """Padded rank the 16-bit LoRA kernels run at (32 | 64)."""
+    r = int(r)
+    if not 1 <= r <= 64:
+        raise ValueError(f"LoRA rank {r} is not supported: the HIP LoRA kernels take 1 <= r <= 64 (factors are zero-padded to the rank "
+                         f"granule {LORA_GRANULE}, i.e. to 32 or 64)")
+    return LORA_GRANULE * ((r + LORA_GRANULE - 1) // LORA_GRANULE)
+
+
+def _rows16(t, name):
+    assert (t.is_cuda and t.dtype in HALF_TYPES and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 8 == 0
+            and t.data_ptr() % 16 == 0), f"{name}: cuda fp16 / bf16 [rows, cols], unit column stride, 16-byte aligned rows"
+
+
+def lora_down(x, a, alpha=1.0, out=None):
+    """lr_lora_down: t [M, R] = alpha * x [M, K] . a [R, K]^T (R = padded rank 32 | 64; x may be a column slice of a wider buffer)."""
+    lib = _lib.load()
+    _rows16(x, "x")
+    _rows16(a, "a")
+    M, K = x.shape
+    R = a.shape[0]
+    assert a.shape[1] == K and a.dtype == x.dtype
+    if out is None:
+        out = torch.empty(M, R, device=x.device, dtype=x.dtype)
+    _rows16(out, "out")
+    assert out.shape == (M, R) and out.dtype == x.dtype
+    _lib.check(_fn(lib, "lr_lora_down_f16", x.dtype)(_p(x), x.stride(0), _p(a), a.stride(0), _p(out), out.stride(0), M, K, R, float(alpha),
+                                                    _stream()), "lora_down")
+    return out
+
+
+def lora_up(t, u, out=None, accumulate=False):
+    """lr_lora_up: out [M, N] (+)= t [M, R] . u [N, R]^T; `out` may be a column slice of a wider buffer (accumulate adds to what it holds)."""
+    lib = _lib.load()
+    _rows16(t, "t")
+    _rows16(u, "u")
+    M, R = t.shape
+    N = u.shape[0]
+    assert u.shape[1] == R and u.dtype == t.dtype
+    if out is None:
+        assert not accumulate, "accumulate needs out="
+        out = torch.empty(M, N, device=t.device, dtype=t.dtype)
+    _rows16(out, "out")
+    assert out.shape == (M, N) and out.dtype == t.dtype
+    _lib.check(_fn(lib, "lr_lora_up_f16", t.dtype)(_p(t), t.stride(0), _p(u), u.stride(0), _p(out), out.stride(0), M, N, R,
+                                                  int(bool(accumulate)), _stream()), "lora_up")
+    return out
+
+
+def lora_wgrad_workspace(M, R, C, device):
+    """fp32 workspace of lr_lora_wgrad for the shape (lr_lora_wgrad_workspace_bytes)."""
+    nbytes = _lib.load().lr_lora_wgrad_workspace_bytes(M, R, C)
+    if nbytes < 0:
+        _lib.check(int(nbytes), "lora_wgrad_workspace_bytes")
+    return torch.empty(nbytes // 4, device=device, dtype=torch.float32)
+
+
+def lora_wgrad(p, q, alpha=1.0, out=None, workspace=None):
+    """lr_lora_wgrad: d [R, C] fp32 = alpha * p [M, R]^T . q [M, C] (fixed-order split over M, no atomics).  out / workspace
+    (lora_wgrad_workspace): buffers of a caller that keeps them."""
+    lib = _lib.load()
+    _rows16(p, "p")
+    _rows16(q, "q")
+    M, R = p.shape
+    C = q.shape[1]
+    assert q.shape[0] == M and q.dtype == p.dtype
+    ws = lora_wgrad_workspace(M, R, C, p.device) if workspace is None else workspace
+    d = torch.empty(R, C, device=p.device, dtype=torch.float32) if out is None else out
+    assert ws.is_cuda and ws.dtype == torch.float32 and ws.is_contiguous() and d.is_cuda and d.dtype == torch.float32 and d.shape == (R, C) \
+        and d.is_contiguous()
+    _lib.check(_fn(lib, "lr_lora_wgrad_f16", p.dtype)(_p(p), p.stride(0), _p(q), q.stride(0), _p(d), C, M, R, C, float(alpha), _p(ws),
+                                                     ws.numel() * 4, _stream()), "lora_wgrad")
+    return d
+
+
+def lora_merge(w, up, down, alpha=1.0):
+    """lr_lora_merge_f32: w [N, K] + alpha * up [N, r] . down [r, K], all fp32 (a new tensor)."""
+    lib = _lib.load()
+    w, up, down = (t.detach().float().contiguous() for t in (w, up, down))
+    N, K = w.shape
+    r = up.shape[1]
+    assert w.is_cuda and up.shape == (N, r) and down.shape == (r, K)
+    if not 1 <= r <= 64:
+        lora_pad_rank(r)
+    out = torch.empty_like(w)
+    _lib.check(lib.lr_lora_merge_f32(_p(w), _p(up), _p(down), _p(out), N, K, r, float(alpha), _stream()), "lora_merge")
+    return out

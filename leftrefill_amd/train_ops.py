@@ -12,9 +12,12 @@ and an input requires grad, in which case it runs as a `torch.autograd.Function`
   attention        lr_attention_bwd_f16 (flash-style recomputation from the saved log-sum-exp); causal (text tower):
                    lr_attention_causal_lse_f16 + lr_attention_causal_bwd_f16
 
+  LoRA factors     lr_lora_down / lr_lora_up next to the base GEMM, lr_lora_wgrad for the two fp32 factor gradients (`lora_linear`)
+
 torch.autograd only orchestrates (graph, fan-in sums of residual branches, `torch.utils.checkpoint` recomputation like
-the reference's CheckpointFunction, ldm/modules/diffusionmodules/util.py:102-151); weights never receive gradients --
-the optimizer of the reference owns only the prompt tokens (ref_inpainting_ldm.py:86-87), which sit upstream of `context`.
+the reference's CheckpointFunction, ldm/modules/diffusionmodules/util.py:102-151); the base weights never receive gradients --
+the optimizer of the reference owns only the prompt tokens (ref_inpainting_ldm.py:86-87), which sit upstream of `context`, and,
+with `lora.do_lora`, the LoRA factors of the attention / GEGLU Linears (NVS_ldm.py:333-335).
 """
 import torch
 
@@ -662,3 +665,118 @@ def mv_gather(x, b, v, s):
 
 def mv_scatter(seq, b, v, s):
     return _MvScatter.apply(seq, b, v, s) if _needs_grad(seq) else ops.mv_scatter(seq, b, v, s)
+
+
+# ---- LoRA: the first weight gradients of this package (csrc/lora.hip) ---------------------------------------------------------------
+def _operand16(f, axis, R, dtype):
+    """The fp32 factor (or a view of it: transposed, row-permuted) as a contiguous 16-bit kernel operand, zero-padded along its rank
+    `axis` to R: one fill and one converting copy."""
+    shape = list(f.shape)
+    shape[axis] = R
+    buf = torch.zeros(shape, device=f.device, dtype=dtype)
+    buf.narrow(axis, 0, f.shape[axis]).copy_(f)
+    return buf
+
+
+class _LoraLinear(torch.autograd.Function):
+    """y = x W^T (+ bias) (+ resid) + sum_i  (x down_i^T) (scale_i up_i)^T  added into the column range of segment i; with `geglu` the
+    GEGLU gate follows (W, bias and the `up` rows in the packed u | g order).  One node for a whole fused projection ([q | k | v],
+    [k | v], every cross-attention's [k | v] of TRAIN_KV_BATCH): the fp32 factors are inputs, read (and cast to the 16-bit operands) at
+    every forward -- the optimizer writes them through raw pointers, no `_version` would tell.
+
+    backward: dx = g W (the base input-gradient GEMM) + sum_i dT_i down_i (lr_lora_up, accumulate), dT_i = scale_i g_i up_i (lr_lora_down);
+              d up_i^T = scale_i T_i^T g_i,  d down_i = dT_i^T x  (lr_lora_wgrad: fp32, fixed-order split sums, no atomics).
+    Saved: x and every T_i = x down_i^T (16-bit, [M, padded rank]); the GEGLU form also keeps the projection, as _GemmConv does."""
+
+    @staticmethod
+    def forward(ctx, x, resid, wt, bias, meta, *factors):
+        ctx.set_materialize_grads(False)
+        segs, geglu = meta
+        x = x.contiguous()
+        M = x.shape[0]
+        y = ops.gemm_conv(x, wt, B=1, H=1, W=M, taps=1, bias=bias, resid=resid)
+        ts = []
+        for i, (off, n, scale, perm) in enumerate(segs):
+            down, up = factors[2 * i].detach(), factors[2 * i + 1].detach()
+            R = ops.lora_pad_rank(down.shape[0])
+            u = up * scale if scale != 1.0 else up
+            if perm is not None:
+                u = u[perm]
+            t = ops.lora_down(x, _operand16(down, 0, R, x.dtype))
+            ops.lora_up(t, _operand16(u, 1, R, x.dtype), out=y[:, off:off + n], accumulate=True)
+            ts.append(t)
+        ctx.meta, ctx.wt, ctx.has_resid, ctx.n_seg = meta, wt, resid is not None, len(segs)
+        ctx.save_for_backward(x, *ts, *factors, *((y,) if geglu else ()))
+        return geglu_fwd(y) if geglu else y
+
+    @staticmethod
+    def backward(ctx, dy):
+        segs, geglu = ctx.meta
+        ns = ctx.n_seg
+        if dy is None:
+            return (None,) * (5 + 2 * ns)
+        saved = ctx.saved_tensors
+        x, ts, factors = saved[0], saved[1:1 + ns], saved[1 + ns:1 + 3 * ns]
+        g = dy.contiguous()
+        if geglu:
+            g = geglu_bwd(saved[1 + 3 * ns], g)
+        M, K = x.shape
+        dx = ops.gemm_conv(g, dgrad_weight(ctx.wt, 1, 0, K), B=1, H=1, W=M, taps=1) if ctx.needs_input_grad[0] else None
+        grads = []
+        for i, (off, n, scale, perm) in enumerate(segs):
+            down, up = factors[2 * i].detach(), factors[2 * i + 1].detach()
+            r = down.shape[0]
+            R = ops.lora_pad_rank(r)
+            gi = g[:, off:off + n]
+            upk = up if perm is None else up[perm]
+            dt = ops.lora_down(gi, _operand16(upk.t(), 0, R, x.dtype), alpha=scale)                            # [M, R] = scale g_i up
+            if dx is not None:
+                ops.lora_up(dt, _operand16(down.t(), 1, R, x.dtype), out=dx, accumulate=True)                   # dx += dT down
+            d_down = d_up = None
+            if ctx.needs_input_grad[5 + 2 * i]:
+                d_down = ops.lora_wgrad(dt, x)[:r]                                                             # [r, K] fp32 (the first rows: contiguous)
+            if ctx.needs_input_grad[6 + 2 * i]:
+                d_up = ops.lora_wgrad(ts[i], gi, alpha=scale)[:r].t()                                            # [n, r] fp32 (packed row order)
+                if perm is not None:
+                    unp = torch.empty(n, r, device=d_up.device, dtype=d_up.dtype)
+                    unp[perm] = d_up
+                    d_up = unp
+                d_up = d_up.contiguous()
+            grads += [d_down, d_up]
+        dresid = dy if ctx.has_resid and ctx.needs_input_grad[1] else None
+        return (dx, dresid, None, None, None) + tuple(grads)
+
+
+def lora_linear(x, wt, bias, segs, resid=None, geglu=False):
+    """Linear with unmerged LoRA factors.  segs: (LoraInjectedLinear, first output column, columns, packed-row permutation | None) per
+    injected Linear whose rows lie in `wt` (engine.lora_segments).  Differentiable w.r.t. x, resid and the fp32 factors; under
+    torch.no_grad() it is the same launches without a graph."""
+    meta, factors = [], []
+    for mod, off, n, perm in segs:
+        if mod.training and mod.dropout.p > 0:
+            raise NotImplementedError("LoRA dropout (dropout_p > 0 in training mode) is not implemented by the HIP path")
+        if off % 8 or n % 8:
+            raise ValueError("LoRA segment columns must be multiples of 8")
+        meta.append((off, n, float(mod.scale), perm))
+        factors += [mod.lora_down.weight, mod.lora_up.weight]
+    if resid is not None and geglu:
+        raise ValueError("the GEGLU projection takes no residual")
+    return _LoraLinear.apply(x, resid, wt, bias, (tuple(meta), bool(geglu)), *factors)
+
+
+class _GradAnchor(torch.autograd.Function):
+    """x, unchanged, as a tensor that requires grad (its backward hands nothing on).  With trainable LoRA factors the input of the first
+    SpatialTransformer takes this, so every injected layer -- the first block's self-attention too, whose input depends on no trainable
+    tensor -- runs the differentiable route; the decisions of engine.fold_ok / gn_fuse_ok / forking then hold as they are."""
+
+    @staticmethod
+    def forward(ctx, x, anchor):
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return None, None
+
+
+def grad_anchor(x, anchor):
+    return _GradAnchor.apply(x, anchor) if torch.is_grad_enabled() and not x.requires_grad and anchor.requires_grad else x

@@ -133,6 +133,8 @@ def main():
     model = create_model(config["model_config"])
     if config.get("resume_path"):
         print(model.load_state_dict(load_state_dict(config["resume_path"]), strict=False))
+    if hasattr(model, "lora_cfg"):      # after the base weights, before the optimizer (reference train_inpainting.py:71-72)
+        model.set_lora()
     model.cfg, model.optim_cfg, model.world_size = config, config["optim_cfg"], a.ngpu
     model = model.to(f"cuda:{rank}")
 
