@@ -882,6 +882,44 @@ int lr_lora_up_bf16(const lr_half* t, int ldt, const lr_half* u, int ldu, lr_hal
 int lr_lora_wgrad_bf16(const lr_half* p, int ldp, const lr_half* q, int ldq, float* d, int ldd, int M, int R, int C, float alpha,
                        void* workspace, int64_t workspace_bytes, lr_stream_t s);
 
+/* ---- LoRA dropout: the mask of `dropout(lora_up(lora_down(x)))` regenerated inside the three LoRA kernels (added under ABI 30 like the
+ *      entries above: six new symbols, nothing renumbered or re-typed; a library without them fails to bind; csrc/lora.hip) --------------
+ * replaces: the nn.Dropout of LoraInjectedLinear (inpainting_ldm/lora.py:21, 32) on the [M, N] low-rank branch, forward and backward,
+ *           without a [M, N] temporary or a stored mask.
+ * The mask (leftrefill_amd/lora_dropout.py states it on the host):
+ *   keep(row, col) = philox4x32_10(counter (row, col >> 2, stream, draw), key (seed & 0xffffffff, seed >> 32))[col & 3] >= threshold
+ * row: the row of the masked [M, N] operand; col: the layer's LOGICAL output feature.  The kernels see columns as they lie in memory,
+ * relative to the pointer they are given (a slice of a fused buffer starts at column 0); colgrp, a device table of N / 4 (C / 4, K / 4)
+ * int32 entries, names the logical group of four columns behind each stored group of four (the GEGLU row interleave), NULL = identity.
+ * threshold = min(2^32 - 1, floor(p 2^32)); inv_keep = 1 / (1 - p) as fp32: finite, >= 1 and within 1e-3 (relative) of
+ * 1 / (1 - threshold / 2^32), LR_E_ARG otherwise.  A mask only zeroes a 16-bit value; inv_keep is applied in fp32.
+ * Argument rules otherwise as the unmasked entries; threshold 0 with inv_keep 1 gives their bits.
+ *
+ *   lr_lora_up_drop     y = 16-bit((accumulate ? y : 0) + (keep ? inv_keep * t . u^T : 0)); a dropped element under `accumulate` keeps
+ *                       y's bits.  (row, col) = y's own, col relative to `y`.
+ *   lr_lora_down_drop   t = 16-bit(alpha * (x (.) keep) . a^T): the mask on the wide operand at x's own (row, col) -- the backward's
+ *                       dT = scale inv_keep (g (.) keep) up with alpha = scale * inv_keep.
+ *   lr_lora_wgrad_drop  d = alpha * p^T . (q (.) keep): the mask on q's own (row, col); split plan, workspace and sum order as
+ *                       lr_lora_wgrad (bit-identical from run to run). */
+typedef struct lr_lora_drop {
+  uint64_t seed;
+  uint32_t stream, draw, threshold;
+  float inv_keep;
+  const int32_t* colgrp;
+} lr_lora_drop;
+int lr_lora_down_drop_f16(const lr_half* x, int ldx, const lr_half* a, int lda, lr_half* t, int ldt, int M, int K, int R, float alpha,
+                          const lr_lora_drop* drop, lr_stream_t s);
+int lr_lora_up_drop_f16(const lr_half* t, int ldt, const lr_half* u, int ldu, lr_half* y, int ldy, int M, int N, int R, int accumulate,
+                        const lr_lora_drop* drop, lr_stream_t s);
+int lr_lora_wgrad_drop_f16(const lr_half* p, int ldp, const lr_half* q, int ldq, float* d, int ldd, int M, int R, int C, float alpha,
+                           void* workspace, int64_t workspace_bytes, const lr_lora_drop* drop, lr_stream_t s);
+int lr_lora_down_drop_bf16(const lr_half* x, int ldx, const lr_half* a, int lda, lr_half* t, int ldt, int M, int K, int R, float alpha,
+                           const lr_lora_drop* drop, lr_stream_t s);
+int lr_lora_up_drop_bf16(const lr_half* t, int ldt, const lr_half* u, int ldu, lr_half* y, int ldy, int M, int N, int R, int accumulate,
+                         const lr_lora_drop* drop, lr_stream_t s);
+int lr_lora_wgrad_drop_bf16(const lr_half* p, int ldp, const lr_half* q, int ldq, float* d, int ldd, int M, int R, int C, float alpha,
+                            void* workspace, int64_t workspace_bytes, const lr_lora_drop* drop, lr_stream_t s);
+
 /* ---- bfloat16 twins: same signatures and semantics as the fp16 entry points above, every lr_half is bfloat16 bits -------- */
 int lr_groupnorm_stats_bf16(const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, float* partials,
     lr_stream_t s);

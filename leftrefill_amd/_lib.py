@@ -123,6 +123,12 @@ class PilJob(ctypes.Structure):
                [(n, ctypes.c_int32) for n in ("hs", "ws", "hd", "wd", "c", "h_ksize", "v_ksize", "reserved")]
 
 
+class LoraDrop(ctypes.Structure):
+    """struct lr_lora_drop (include/leftrefill_hip.h)."""
+    _fields_ = [("seed", ctypes.c_uint64), ("stream", ctypes.c_uint32), ("draw", ctypes.c_uint32), ("threshold", ctypes.c_uint32),
+                ("inv_keep", ctypes.c_float), ("colgrp", c_void_p)]
+
+
 class GridSource(ctypes.Structure):
     """struct lr_grid_source (include/leftrefill_hip.h)."""
     _fields_ = [("ptr", c_void_p)] + [(n, ctypes.c_int32) for n in ("kind", "C", "W", "col")] + \
@@ -242,6 +248,13 @@ SIGNATURES = {
     "lr_lora_wgrad_workspace_bytes": [c_int, c_int, c_int],
     "lr_lora_wgrad_f16": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p],
     "lr_lora_merge_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p],
+    # added under ABI 30 as well: the three LoRA products with the dropout mask regenerated in the kernel (csrc/lora.hip)
+    "lr_lora_down_drop_f16": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, ctypes.POINTER(LoraDrop),
+                              c_void_p],
+    "lr_lora_up_drop_f16": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(LoraDrop),
+                            c_void_p],
+    "lr_lora_wgrad_drop_f16": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int64,
+                               ctypes.POINTER(LoraDrop), c_void_p],
 }
 INT64_RETURNS = ("lr_gemm_workspace_bytes", "lr_lpips_workspace_bytes", "lr_lora_wgrad_workspace_bytes")
 
@@ -254,7 +267,8 @@ BF16_TWINS = ["lr_groupnorm_stats", "lr_groupnorm_apply", "lr_groupnorm_apply_n"
               "lr_attention_vt_f16", "lr_transpose_v_f16", "lr_attention_bwd_f16", "lr_xattn_block_f16",
               "lr_xattn_pack_vt_f16", "lr_ffn_block_f16", "lr_stin_block_f16", "lr_rowlin_f16", "lr_gn_conv_out_f16",
               "lr_attention_causal_lse_f16", "lr_attention_causal_bwd_f16", "lr_gelu_fwd_f16", "lr_gelu_bwd_f16",
-              "lr_attention_probe_f16", "lr_lora_down_f16", "lr_lora_up_f16", "lr_lora_wgrad_f16"]
+              "lr_attention_probe_f16", "lr_lora_down_f16", "lr_lora_up_f16", "lr_lora_wgrad_f16",
+              "lr_lora_down_drop_f16", "lr_lora_up_drop_f16", "lr_lora_wgrad_drop_f16"]
 
 
 def twin(name):

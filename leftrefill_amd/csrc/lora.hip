@@ -5,6 +5,10 @@
 //   lr_lora_up     Y[M, N] (+)= T[M, r] . U[N, r]^T             forward y += T (scale up)^T;  backward dx += dT (down^T)^T
 //   lr_lora_wgrad  D[r, C]  = alpha * P[M, r]^T . Q[M, C]       d up^T = scale * T^T dY;  d down = dT^T X     (fp32, split over M)
 //   lr_lora_merge  W_eff    = W + alpha * B[N, R] . A[R, K]     fp32 VALU, any 1 <= R <= 64
+//   lr_lora_*_drop the same three products with the LoRA dropout mask of the [M, N] branch regenerated in the kernel (Philox-4x32-10,
+//                  one call per 4 consecutive logical columns of a row; leftrefill_amd/lora_dropout.py states it): on up's epilogue,
+//                  on down's wide operand as it is loaded, on wgrad's Q chunks before they are staged.  A mask only zeroes; 1 / (1 - p)
+//                  is an fp32 scalar.  Compile-time flag DROP: the unmasked instances carry none of it.
 //
 // down / up are read-bound streams of the wide operand: every MFMA operand (16x16x32, 8 consecutive k per lane) is ONE 16-byte global
 // load of a row of X, T or a factor -- no LDS.  The product is formed transposed (factor rows on the accumulator's row index) so that a
@@ -13,6 +17,7 @@
 // k-major fragments are gathered with ds_read_b64_tr_b16 (as attention_bwd.hip does for Q^T / dO^T): no transposed copies.  M is split
 // over blockIdx.y into fp32 partials, summed in split order by a second launch: no atomics, bit-identical from run to run.
 #include "common.h"
+#include <cmath>
 
 #define LORA_THREADS 256
 
@@ -21,11 +26,53 @@ __device__ __forceinline__ vec8<T> lora_zero8() {
   return __builtin_bit_cast(vec8<T>, make_uint4(0u, 0u, 0u, 0u));
 }
 
+// ---- the dropout mask ---------------------------------------------------------------------------------------------------
+// keep(row, col) = philox4x32_10((row, col >> 2, stream, draw), (seed lo, seed hi))[col & 3] >= thr, col the LOGICAL output feature
+// (colgrp maps a packed group of 4 columns to its logical group; NULL = identity)
+struct lora_mask {
+  uint32_t k0, k1, stream, draw, thr;
+  float inv_keep;
+  const int32_t* colgrp;
+};
+
+// bit i: column 4 grp + i of `row` is kept.  10 rounds of 2 x (v_mul_hi_u32, v_mul_lo_u32); the Weyl key sequence is lane-uniform
+__device__ __forceinline__ uint32_t lora_keep4(const lora_mask& mk, uint32_t row, uint32_t grp) {
+  uint32_t c0 = row, c1 = grp, c2 = mk.stream, c3 = mk.draw, k0 = mk.k0, k1 = mk.k1;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return (uint32_t)(c0 >= mk.thr) | ((uint32_t)(c1 >= mk.thr) << 1) | ((uint32_t)(c2 >= mk.thr) << 2) | ((uint32_t)(c3 >= mk.thr) << 3);
+}
+
+__device__ __forceinline__ uint32_t lora_grp(const lora_mask& mk, uint32_t g) { return mk.colgrp ? (uint32_t)mk.colgrp[g] : g; }
+
+// 2 kept-bits -> the AND mask of the 32-bit word that holds the two 16-bit elements
+__device__ __forceinline__ uint32_t lora_pair(uint32_t b) { return ((b & 1u) ? 0xffffu : 0u) | ((b & 2u) ? 0xffff0000u : 0u); }
+
+// 8 consecutive columns col .. col + 7 (col % 8 == 0) of `row`, masked-out elements set to +0: two Philox calls
+__device__ __forceinline__ uint4 lora_mask8(uint4 v, const lora_mask& mk, uint32_t row, uint32_t col) {
+  const uint32_t b0 = lora_keep4(mk, row, lora_grp(mk, col >> 2)), b1 = lora_keep4(mk, row, lora_grp(mk, (col >> 2) + 1));
+  v.x &= lora_pair(b0);
+  v.y &= lora_pair(b0 >> 2);
+  v.z &= lora_pair(b1);
+  v.w &= lora_pair(b1 >> 2);
+  return v;
+}
+
 // ---- T = alpha X A^T ---------------------------------------------------------------------------------------------------
 // one wave = 16 rows of X against all NR * 16 factor rows; accumulator (reg, lane): T[m0 + (lane & 15)][16 j + 4 (lane >> 4) + reg]
-template <typename T, int NR>
+// DROP: x is masked as it is loaded, at its own (row, column)
+template <typename T, int NR, bool DROP>
 __global__ __launch_bounds__(LORA_THREADS) void lora_down_kernel(const T* __restrict__ x, int ldx, const T* __restrict__ a, int lda,
-                                                                 T* __restrict__ t, int ldt, int M, int K, float alpha) {
+                                                                 T* __restrict__ t, int ldt, int M, int K, float alpha, lora_mask mk) {
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int m0 = (blockIdx.x * 4 + w) * 16;
@@ -38,14 +85,18 @@ __global__ __launch_bounds__(LORA_THREADS) void lora_down_kernel(const T* __rest
   for (int j = 0; j < NR; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const int kfull = K & ~31;
   for (int k0 = 0; k0 < kfull; k0 += 32) {
-    const vec8<T> xf = *reinterpret_cast<const vec8<T>*>(xp + k0);
+    vec8<T> xf = *reinterpret_cast<const vec8<T>*>(xp + k0);
+    if constexpr (DROP) xf = __builtin_bit_cast(vec8<T>, lora_mask8(__builtin_bit_cast(uint4, xf), mk, min(mrow, M - 1), k0 + kq));
 #pragma unroll
     for (int j = 0; j < NR; ++j)
       acc[j] = lr_mfma16(*reinterpret_cast<const vec8<T>*>(ap + (size_t)j * 16 * lda + k0), xf, acc[j]);
   }
   if (kfull < K) {      // K % 8 == 0: a lane's 8 columns are all inside K or all outside
     const bool in = kfull + kq < K;
-    const vec8<T> xf = in ? *reinterpret_cast<const vec8<T>*>(xp + kfull) : lora_zero8<T>();
+    vec8<T> xf = in ? *reinterpret_cast<const vec8<T>*>(xp + kfull) : lora_zero8<T>();
+    if constexpr (DROP) {
+      if (in) xf = __builtin_bit_cast(vec8<T>, lora_mask8(__builtin_bit_cast(uint4, xf), mk, min(mrow, M - 1), kfull + kq));
+    }
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
       const vec8<T> af = in ? *reinterpret_cast<const vec8<T>*>(ap + (size_t)j * 16 * lda + kfull) : lora_zero8<T>();
@@ -68,9 +119,10 @@ __global__ __launch_bounds__(LORA_THREADS) void lora_down_kernel(const T* __rest
 // one wave = 16 rows of T (held in registers) against 256 columns of Y, 16 at a time; accumulator (reg, lane):
 // Y[m0 + (lane & 15)][n0 + 4 (lane >> 4) + reg]
 #define LORA_UP_COLS 256
-template <typename T, int KS>
+// DROP: the mask sits in the epilogue -- a kept element takes inv_keep * acc, a dropped one keeps y's bits (accumulate) or is +0
+template <typename T, int KS, bool DROP>
 __global__ __launch_bounds__(LORA_THREADS) void lora_up_kernel(const T* __restrict__ t, int ldt, const T* __restrict__ u, int ldu,
-                                                               T* __restrict__ y, int ldy, int M, int N, int accumulate) {
+                                                               T* __restrict__ y, int ldy, int M, int N, int accumulate, lora_mask mk) {
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int m0 = (blockIdx.x * 4 + w) * 16;
@@ -88,6 +140,24 @@ __global__ __launch_bounds__(LORA_THREADS) void lora_up_kernel(const T* __restri
     const int nn = n0 + 4 * (lane >> 4);      // N % 8 == 0: the lane's 4 columns are all inside N or all outside
     if (mrow < M && nn < N) {
       T* yp = y + (size_t)mrow * ldy + nn;
+      if constexpr (DROP) {
+        // fp32 product, fp32 sum and the 16-bit rounding stay three roundings, as the unmasked path's add + convert: contracted into one
+        // mixed-precision fma (v_fma_mixlo_f16) the sum would round once, and inv_keep = 1 would not give the unmasked kernel's bits
+#pragma clang fp contract(off)
+        const uint32_t kb = lora_keep4(mk, mrow, lora_grp(mk, nn >> 2));
+        vec4<T> o = __builtin_bit_cast(vec4<T>, make_uint2(0u, 0u));
+        float base[4] = {0.f, 0.f, 0.f, 0.f};
+        if (accumulate) {
+          o = *reinterpret_cast<const vec4<T>*>(yp);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) base[i] = (float)o[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if ((kb >> i) & 1u) o[i] = (T)(acc[i] * mk.inv_keep + base[i]);
+        *reinterpret_cast<vec4<T>*>(yp) = o;
+        continue;
+      }
       if (accumulate) {
         const vec4<T> old = *reinterpret_cast<const vec4<T>*>(yp);
 #pragma unroll
@@ -124,9 +194,10 @@ __device__ __forceinline__ vec8<T> lora_frag_tr(const char* tile, int stride, in
 
 // grid (ceil(C / 128), splits); block (x, y) writes ws[y][NR * 16][C] columns 128 x .. : accumulator (reg, lane) of (i, ct) is
 // r = 16 i + 4 (lane >> 4) + reg, c = c0 + 32 w + 16 ct + (lane & 15)
-template <typename T, int NR>
+// DROP: the chunks of Q are masked before they are staged, at their own (row, column)
+template <typename T, int NR, bool DROP>
 __global__ __launch_bounds__(LORA_THREADS) void lora_wgrad_kernel(const T* __restrict__ p, int ldp, const T* __restrict__ q, int ldq,
-                                                                  float* __restrict__ ws, int M, int C, int rows_per_split) {
+                                                                  float* __restrict__ ws, int M, int C, int rows_per_split, lora_mask mk) {
   constexpr int RP = NR * 16, PS = RP * 2 + 16, PCH = RP / 8;      // PCH: 16-byte chunks of a P row
   __shared__ __attribute__((aligned(16))) char sp[LORA_WG_ROWS * PS];
   __shared__ __attribute__((aligned(16))) char sq[LORA_WG_ROWS * LORA_WG_QS];
@@ -144,6 +215,10 @@ __global__ __launch_bounds__(LORA_THREADS) void lora_wgrad_kernel(const T* __res
     const int r0 = m + qrow, r1 = m + 16 + qrow;
     gq0 = (qcol_in && r0 < mend) ? *reinterpret_cast<const uint4*>(q + (size_t)r0 * ldq + c0 + qch * 8) : z4;
     gq1 = (qcol_in && r1 < mend) ? *reinterpret_cast<const uint4*>(q + (size_t)r1 * ldq + c0 + qch * 8) : z4;
+    if constexpr (DROP) {
+      if (qcol_in && r0 < mend) gq0 = lora_mask8(gq0, mk, r0, c0 + qch * 8);
+      if (qcol_in && r1 < mend) gq1 = lora_mask8(gq1, mk, r1, c0 + qch * 8);
+    }
     gp = (prow < LORA_WG_ROWS && m + prow < mend) ? *reinterpret_cast<const uint4*>(p + (size_t)(m + prow) * ldp + pch * 8) : z4;
   };
   f32x4 acc[NR][2];
@@ -219,29 +294,50 @@ __global__ void lora_merge_kernel(const float* __restrict__ wt, const float* __r
 static inline bool lora_rank_ok(int R) { return R == 32 || R == 64; }
 static inline bool lora_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-template <typename T>
+// the descriptor of a masked launch, checked: 1 / (1 - p) must go with the threshold floor(p 2^32) (LR_E_ARG otherwise)
+static int lora_mask_of(const lr_lora_drop* d, lora_mask* mk) {
+  if (!d) return LR_E_ARG;
+  if (!(d->inv_keep >= 1.f) || !std::isfinite(d->inv_keep)) return LR_E_ARG;
+  const double keep = 1.0 - (double)d->threshold / 4294967296.0;
+  if (std::fabs((double)d->inv_keep * keep - 1.0) > 1e-3) return LR_E_ARG;
+  if ((uintptr_t)d->colgrp & 3) return LR_E_ALIGN;
+  *mk = lora_mask{(uint32_t)(d->seed & 0xffffffffull), (uint32_t)(d->seed >> 32), d->stream, d->draw, d->threshold, d->inv_keep, d->colgrp};
+  return 0;
+}
+
+template <typename T, bool DROP>
 static int lora_down_t(const lr_half* x, int ldx, const lr_half* a, int lda, lr_half* t, int ldt, int M, int K, int R, float alpha,
-                       lr_stream_t s) {
+                       const lr_lora_drop* drop, lr_stream_t s) {
   if (!x || !a || !t || M <= 0 || K <= 0 || ldx < K || lda < K || ldt < R) return LR_E_ARG;
   if (!lora_rank_ok(R)) return LR_E_UNSUPPORTED;
   if (K % 8 || ldx % 8 || lda % 8 || ldt % 8 || !lora_al16(x) || !lora_al16(a) || !lora_al16(t)) return LR_E_ALIGN;
+  lora_mask mk = {};
+  if (DROP) {
+    const int rc = lora_mask_of(drop, &mk);
+    if (rc) return rc;
+  }
   const dim3 grid((M + 63) / 64), block(LORA_THREADS);
   hipStream_t st = (hipStream_t)s;
-  if (R == 32) hipLaunchKernelGGL((lora_down_kernel<T, 2>), grid, block, 0, st, (const T*)x, ldx, (const T*)a, lda, (T*)t, ldt, M, K, alpha);
-  else hipLaunchKernelGGL((lora_down_kernel<T, 4>), grid, block, 0, st, (const T*)x, ldx, (const T*)a, lda, (T*)t, ldt, M, K, alpha);
+  if (R == 32) hipLaunchKernelGGL((lora_down_kernel<T, 2, DROP>), grid, block, 0, st, (const T*)x, ldx, (const T*)a, lda, (T*)t, ldt, M, K, alpha, mk);
+  else hipLaunchKernelGGL((lora_down_kernel<T, 4, DROP>), grid, block, 0, st, (const T*)x, ldx, (const T*)a, lda, (T*)t, ldt, M, K, alpha, mk);
   return lr_launch_status();
 }
 
-template <typename T>
+template <typename T, bool DROP>
 static int lora_up_t(const lr_half* t, int ldt, const lr_half* u, int ldu, lr_half* y, int ldy, int M, int N, int R, int accumulate,
-                     lr_stream_t s) {
+                     const lr_lora_drop* drop, lr_stream_t s) {
   if (!t || !u || !y || M <= 0 || N <= 0 || ldt < R || ldu < R || ldy < N) return LR_E_ARG;
   if (!lora_rank_ok(R)) return LR_E_UNSUPPORTED;
   if (N % 8 || ldt % 8 || ldu % 8 || ldy % 8 || !lora_al16(t) || !lora_al16(u) || !lora_al16(y)) return LR_E_ALIGN;
+  lora_mask mk = {};
+  if (DROP) {
+    const int rc = lora_mask_of(drop, &mk);
+    if (rc) return rc;
+  }
   const dim3 grid((M + 63) / 64, (N + LORA_UP_COLS - 1) / LORA_UP_COLS), block(LORA_THREADS);
   hipStream_t st = (hipStream_t)s;
-  if (R == 32) hipLaunchKernelGGL((lora_up_kernel<T, 1>), grid, block, 0, st, (const T*)t, ldt, (const T*)u, ldu, (T*)y, ldy, M, N, accumulate);
-  else hipLaunchKernelGGL((lora_up_kernel<T, 2>), grid, block, 0, st, (const T*)t, ldt, (const T*)u, ldu, (T*)y, ldy, M, N, accumulate);
+  if (R == 32) hipLaunchKernelGGL((lora_up_kernel<T, 1, DROP>), grid, block, 0, st, (const T*)t, ldt, (const T*)u, ldu, (T*)y, ldy, M, N, accumulate, mk);
+  else hipLaunchKernelGGL((lora_up_kernel<T, 2, DROP>), grid, block, 0, st, (const T*)t, ldt, (const T*)u, ldu, (T*)y, ldy, M, N, accumulate, mk);
   return lr_launch_status();
 }
 
@@ -265,20 +361,25 @@ extern "C" int64_t lr_lora_wgrad_workspace_bytes(int M, int R, int C) {
   return (int64_t)splits * R * C * (int64_t)sizeof(float);
 }
 
-template <typename T>
+template <typename T, bool DROP>
 static int lora_wgrad_t(const lr_half* p, int ldp, const lr_half* q, int ldq, float* d, int ldd, int M, int R, int C, float alpha,
-                        void* workspace, int64_t workspace_bytes, lr_stream_t s) {
+                        void* workspace, int64_t workspace_bytes, const lr_lora_drop* drop, lr_stream_t s) {
   if (!p || !q || !d || !workspace || M <= 0 || C <= 0 || ldp < R || ldq < C || ldd < C) return LR_E_ARG;
   if (!lora_rank_ok(R)) return LR_E_UNSUPPORTED;
   if (C % 8 || ldp % 8 || ldq % 8 || ldd % 4 || !lora_al16(p) || !lora_al16(q) || !lora_al16(d) || !lora_al16(workspace)) return LR_E_ALIGN;
   int splits, rows;
   lora_wgrad_plan(M, C, &splits, &rows);
   if (workspace_bytes < (int64_t)splits * R * C * (int64_t)sizeof(float)) return LR_E_ARG;
+  lora_mask mk = {};
+  if (DROP) {
+    const int rc = lora_mask_of(drop, &mk);
+    if (rc) return rc;
+  }
   const dim3 grid((C + LORA_WG_COLS - 1) / LORA_WG_COLS, splits), block(LORA_THREADS);
   hipStream_t st = (hipStream_t)s;
   float* ws = (float*)workspace;
-  if (R == 32) hipLaunchKernelGGL((lora_wgrad_kernel<T, 2>), grid, block, 0, st, (const T*)p, ldp, (const T*)q, ldq, ws, M, C, rows);
-  else hipLaunchKernelGGL((lora_wgrad_kernel<T, 4>), grid, block, 0, st, (const T*)p, ldp, (const T*)q, ldq, ws, M, C, rows);
+  if (R == 32) hipLaunchKernelGGL((lora_wgrad_kernel<T, 2, DROP>), grid, block, 0, st, (const T*)p, ldp, (const T*)q, ldq, ws, M, C, rows, mk);
+  else hipLaunchKernelGGL((lora_wgrad_kernel<T, 4, DROP>), grid, block, 0, st, (const T*)p, ldp, (const T*)q, ldq, ws, M, C, rows, mk);
   int rc = lr_launch_status();
   if (rc) return rc;
   const long long total = (long long)R * (C / 4);
@@ -296,20 +397,32 @@ extern "C" int lr_lora_merge_f32(const float* w, const float* b, const float* a,
   return lr_launch_status();
 }
 
-// ---- C ABI: fp16 and bf16 forms ------------------------------------------------------------------------------------------
-extern "C" int lr_lora_down_f16(const lr_half* x, int ldx, const lr_half* a, int lda, lr_half* t, int ldt, int M, int K, int R, float alpha,
-                                lr_stream_t s) { return lora_down_t<f16>(x, ldx, a, lda, t, ldt, M, K, R, alpha, s); }
-extern "C" int lr_lora_down_bf16(const lr_half* x, int ldx, const lr_half* a, int lda, lr_half* t, int ldt, int M, int K, int R, float alpha,
-                                 lr_stream_t s) { return lora_down_t<bf16>(x, ldx, a, lda, t, ldt, M, K, R, alpha, s); }
-extern "C" int lr_lora_up_f16(const lr_half* t, int ldt, const lr_half* u, int ldu, lr_half* y, int ldy, int M, int N, int R, int accumulate,
-                              lr_stream_t s) { return lora_up_t<f16>(t, ldt, u, ldu, y, ldy, M, N, R, accumulate, s); }
-extern "C" int lr_lora_up_bf16(const lr_half* t, int ldt, const lr_half* u, int ldu, lr_half* y, int ldy, int M, int N, int R, int accumulate,
-                               lr_stream_t s) { return lora_up_t<bf16>(t, ldt, u, ldu, y, ldy, M, N, R, accumulate, s); }
-extern "C" int lr_lora_wgrad_f16(const lr_half* p, int ldp, const lr_half* q, int ldq, float* d, int ldd, int M, int R, int C, float alpha,
-                                 void* workspace, int64_t workspace_bytes, lr_stream_t s) {
-  return lora_wgrad_t<f16>(p, ldp, q, ldq, d, ldd, M, R, C, alpha, workspace, workspace_bytes, s);
-}
-extern "C" int lr_lora_wgrad_bf16(const lr_half* p, int ldp, const lr_half* q, int ldq, float* d, int ldd, int M, int R, int C, float alpha,
-                                  void* workspace, int64_t workspace_bytes, lr_stream_t s) {
-  return lora_wgrad_t<bf16>(p, ldp, q, ldq, d, ldd, M, R, C, alpha, workspace, workspace_bytes, s);
-}
+// ---- C ABI: fp16 and bf16 forms, unmasked and masked ------------------------------------------------------------------------
+#define LORA_ABI(SUF, TY)                                                                                                                  \
+  extern "C" int lr_lora_down_##SUF(const lr_half* x, int ldx, const lr_half* a, int lda, lr_half* t, int ldt, int M, int K, int R,       \
+                                    float alpha, lr_stream_t s) {                                                                        \
+    return lora_down_t<TY, false>(x, ldx, a, lda, t, ldt, M, K, R, alpha, nullptr, s);                                                    \
+  }                                                                                                                                        \
+  extern "C" int lr_lora_up_##SUF(const lr_half* t, int ldt, const lr_half* u, int ldu, lr_half* y, int ldy, int M, int N, int R,         \
+                                  int accumulate, lr_stream_t s) {                                                                       \
+    return lora_up_t<TY, false>(t, ldt, u, ldu, y, ldy, M, N, R, accumulate, nullptr, s);                                                 \
+  }                                                                                                                                        \
+  extern "C" int lr_lora_wgrad_##SUF(const lr_half* p, int ldp, const lr_half* q, int ldq, float* d, int ldd, int M, int R, int C,        \
+                                     float alpha, void* workspace, int64_t workspace_bytes, lr_stream_t s) {                             \
+    return lora_wgrad_t<TY, false>(p, ldp, q, ldq, d, ldd, M, R, C, alpha, workspace, workspace_bytes, nullptr, s);                       \
+  }                                                                                                                                        \
+  extern "C" int lr_lora_down_drop_##SUF(const lr_half* x, int ldx, const lr_half* a, int lda, lr_half* t, int ldt, int M, int K, int R,  \
+                                         float alpha, const lr_lora_drop* drop, lr_stream_t s) {                                         \
+    return lora_down_t<TY, true>(x, ldx, a, lda, t, ldt, M, K, R, alpha, drop, s);                                                        \
+  }                                                                                                                                        \
+  extern "C" int lr_lora_up_drop_##SUF(const lr_half* t, int ldt, const lr_half* u, int ldu, lr_half* y, int ldy, int M, int N, int R,    \
+                                       int accumulate, const lr_lora_drop* drop, lr_stream_t s) {                                        \
+    return lora_up_t<TY, true>(t, ldt, u, ldu, y, ldy, M, N, R, accumulate, drop, s);                                                     \
+  }                                                                                                                                        \
+  extern "C" int lr_lora_wgrad_drop_##SUF(const lr_half* p, int ldp, const lr_half* q, int ldq, float* d, int ldd, int M, int R, int C,   \
+                                          float alpha, void* workspace, int64_t workspace_bytes, const lr_lora_drop* drop,               \
+                                          lr_stream_t s) {                                                                               \
+    return lora_wgrad_t<TY, true>(p, ldp, q, ldq, d, ldd, M, R, C, alpha, workspace, workspace_bytes, drop, s);                           \
+  }
+LORA_ABI(f16, f16)
+LORA_ABI(bf16, bf16)

@@ -116,7 +116,10 @@ class NVSLDM(LatentInpaintDiffusion):
         kind = self.lora_cfg.get("lora_type", "default")
         kw = dict(r=self.lora_cfg["lora_rank"], scale=self.lora_cfg.get("lora_scale", 1.0))
         if kind == "default":
-            self.unet_lora_params, _ = inject_trainable_lora(self.model.diffusion_model, verbose=False, **kw)
+            # `lora_dropout` (optional, default 0): the reference's inject_trainable_lora(dropout_p=...) -- Philox masks inside the HIP
+            # LoRA kernels, one stream per injected layer (inpainting_ldm/lora.py)
+            self.unet_lora_params, _ = inject_trainable_lora(self.model.diffusion_model, verbose=False,
+                                                             dropout_p=float(self.lora_cfg.get("lora_dropout", 0.0)), **kw)
         elif kind == "extended":
             inject_trainable_lora_extended(self.model.diffusion_model, **kw)      # (NotImplementedError naming the reason)
         else:
@@ -277,7 +280,19 @@ class NVSLDM(LatentInpaintDiffusion):
             groups.append({"params": params, "lr": self.optim_cfg["lr_lora"], "weight_decay": self.optim_cfg["wd_lora"]})
         return configure_prompt_optimizer(self, groups)
 
+    LORA_DROPOUT_KEY = "lora_dropout_state"      # checkpoint key of the UNet's (seed, draw): a resumed run continues the mask sequence
+
+    def on_load_checkpoint(self, checkpoint):
+        from .lora import lora_dropout_state
+        state = lora_dropout_state(self.model.diffusion_model)
+        if state is not None and self.LORA_DROPOUT_KEY in checkpoint:      # (a checkpoint without the key loads as before)
+            state.load_state_dict(checkpoint[self.LORA_DROPOUT_KEY])
+
     def on_save_checkpoint(self, checkpoint):
+        from .lora import lora_dropout_state
+        state = lora_dropout_state(self.model.diffusion_model)
+        if state is not None:
+            checkpoint[self.LORA_DROPOUT_KEY] = state.state_dict()
         if self.save_prompt_only:
             from leftrefill_amd.optim import keep_keys
 

@@ -14,9 +14,16 @@ On the device the injected layers do not run as modules: `UNetModel` packs them 
 lr_lora_down + lr_lora_up with HIP factor gradients for training).  `LoraInjectedLinear.forward` is the plain-torch statement of the layer
 for CPU tensors (what the CPU tests compare against); a device tensor is refused -- this package has no BLAS path.
 
-Out of scope, each a NotImplementedError: `inject_trainable_lora_extended` (it builds its Linears with dropout 0.1 on the [M, N] branch),
-dropout_p > 0 in training mode, `LoraInjectedConv2d`, `set_selector_from_diag`, the multi-view UNet and the text tower.
+LoRA dropout: `inject_trainable_lora(..., dropout_p=p)` gives layer i the stream id `drop_stream = i` (the order of the returned names) and
+the model one `LoraDropoutState` (seed, draw).  The mask is counter-based (leftrefill_amd.lora_dropout: Philox on (row, column group,
+stream, draw)), regenerated inside the HIP kernels and never stored; a layer that has a stream uses the same stated mask in its CPU
+`forward` in place of nn.Dropout.  A layer without a stream (built by hand) keeps nn.Dropout on the CPU and is refused on the device.
+
+Out of scope, each a NotImplementedError: `inject_trainable_lora_extended` (it builds its Linears with dropout 0.1 on the [M, N] branch and
+LoraInjectedConv2d layers), dropout_p > 0 in training mode on a layer that was not injected with a dropout stream, `LoraInjectedConv2d`,
+`set_selector_from_diag`, the multi-view UNet and the text tower.
 """
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -27,6 +34,28 @@ TEXT_ENCODER_EXTENDED_TARGET_REPLACE = {"CLIPAttention"}
 DEFAULT_TARGET_REPLACE = UNET_DEFAULT_TARGET_REPLACE
 EMBED_FLAG = "<embed>"
 MAX_RANK = 64      # the HIP LoRA kernels run at a padded rank of 32 or 64 (leftrefill_amd.ops.lora_pad_rank)
+
+
+class LoraDropoutState:
+    """The dropout state of one injected model: `seed` (64 bits) and `draw`, the 32-bit count of training forwards so far (it wraps).
+    The UNet advances `draw` once per grad-enabled training forward that has a live dropout layer and hands the number it took down to
+    every layer's node; checkpoints carry the pair."""
+
+    def __init__(self, seed=None, draw=0):
+        self.seed = int(torch.initial_seed() if seed is None else seed) & (2 ** 64 - 1)
+        self.draw = int(draw) & 0xFFFFFFFF
+
+    def take(self):
+        """The draw number of this forward; the counter moves on."""
+        d = self.draw
+        self.draw = (d + 1) & 0xFFFFFFFF
+        return d
+
+    def state_dict(self):
+        return {"seed": self.seed, "draw": self.draw}
+
+    def load_state_dict(self, sd):
+        self.seed, self.draw = int(sd["seed"]) & (2 ** 64 - 1), int(sd["draw"]) & 0xFFFFFFFF
 
 
 class LoraInjectedLinear(nn.Module):
@@ -46,6 +75,7 @@ class LoraInjectedLinear(nn.Module):
         self.dropout = nn.Dropout(dropout_p)
         self.lora_up = nn.Linear(r, out_features, bias=False)
         self.selector = nn.Identity()
+        self.drop_stream = self.drop_state = None      # set by inject_trainable_lora: the layer's stream id and the model's LoraDropoutState
         with torch.no_grad():
             self.lora_down.weight.normal_(mean=0.0, std=1.0 / r)
             self.lora_up.weight.zero_()
@@ -54,7 +84,19 @@ class LoraInjectedLinear(nn.Module):
         if input.is_cuda:
             raise RuntimeError("LoraInjectedLinear runs on the device through UNetModel's packed routes only (no BLAS path in this package)")
         low_rank = self.lora_up(self.selector(self.lora_down(input)))
+        if self.dropout_live():
+            # the stated mask at the state's current draw (row = the input's row in [M, K] order), not nn.Dropout's generator
+            from leftrefill_amd import lora_dropout
+            p, n = self.dropout.p, low_rank.shape[-1]
+            keep = lora_dropout.keep_mask(self.drop_state.seed, self.drop_stream, self.drop_state.draw, low_rank.numel() // n, n, p)
+            keep = torch.from_numpy(np.ascontiguousarray(keep)).reshape(low_rank.shape)
+            low_rank = torch.where(keep, low_rank * lora_dropout.inv_keep(p), torch.zeros((), dtype=low_rank.dtype))
+            return self.linear(input) + self.scale * low_rank
         return self.linear(input) + self.scale * self.dropout(low_rank)
+
+    def dropout_live(self):
+        """Training with p > 0 on a layer that inject_trainable_lora gave a dropout stream: the counter-based mask applies."""
+        return self.training and self.dropout.p > 0 and self.drop_stream is not None and self.drop_state is not None
 
     def realize_as_lora(self):
         """(scale * up, down): the two matrices whose product is what the layer adds to its base weight."""
@@ -112,15 +154,21 @@ def _check_target(model, target_replace_module):
 
 def inject_trainable_lora(model, target_replace_module=DEFAULT_TARGET_REPLACE, r=4, loras=None, verbose=False, dropout_p=0.0, scale=1.0):
     """Wrap every nn.Linear below the target classes in a LoraInjectedLinear that keeps it as its `linear` (same Parameters, so a loaded
-    checkpoint stays loaded).  loras: path of a saved [up, down, up, down, ...] list to start from.  Returns ([up.parameters(),
+    checkpoint stays loaded).  loras: path of a saved [up, down, up, down, ...] list to start from.  dropout_p: the rate of the dropout on
+    the low-rank branch; layer i (the order of the returned names) draws its mask from stream i of the model's LoraDropoutState.  Returns ([up.parameters(),
     down.parameters(), ...] layer by layer, [name of each wrapped child in its parent])."""
     _check_target(model, target_replace_module)
     saved = iter(torch.load(loras)) if loras is not None else None
     sites = list(_find_modules(model, target_replace_module, search_class=[nn.Linear]))      # found first, swapped after: the walk sees one tree
     param_iters, names = [], []
-    for owner, leaf, base in sites:
+    state = model.__dict__.get("_lora_dropout")
+    if state is None:
+        state = model.__dict__["_lora_dropout"] = LoraDropoutState()      # (a plain attribute: no module, no buffer, no state_dict key)
+    first = sum(1 for m in model.modules() if isinstance(m, LoraInjectedLinear) and m.drop_stream is not None)
+    for i, (owner, leaf, base) in enumerate(sites):
         layer = LoraInjectedLinear(base.in_features, base.out_features, base.bias is not None, r=r, dropout_p=dropout_p, scale=scale)
         layer.linear = base
+        layer.drop_stream, layer.drop_state = first + i, state
         layer.to(base.weight.device)      # (the factors stay fp32 whatever the base weight's dtype: their gradients arrive in fp32)
         if saved is not None:
             layer.lora_up.weight, layer.lora_down.weight = next(saved), next(saved)
@@ -136,6 +184,11 @@ def inject_trainable_lora(model, target_replace_module=DEFAULT_TARGET_REPLACE, r
         if hook is not None:
             hook()
     return param_iters, names
+
+
+def lora_dropout_state(model):
+    """The LoraDropoutState inject_trainable_lora put on `model`, or None."""
+    return model.__dict__.get("_lora_dropout")
 
 
 def inject_trainable_lora_extended(model, target_replace_module=UNET_EXTENDED_TARGET_REPLACE, r=4, loras=None, verbose=False, scale=1.0):

@@ -527,6 +527,9 @@ class UNetModel(nn.Module):
         anchor = next((p_ for m in P["lora"] for p_ in (m.lora_up.weight, m.lora_down.weight) if p_.requires_grad), None) if lora_live else None
         recompute = (self.recompute_in_backward and self.use_checkpoint and torch.is_grad_enabled()
                      and (context.requires_grad or lora_live))
+        # LoRA dropout: this forward's draw number, taken once and handed down (a recomputed block sets the same number again)
+        drop_state = next((m.drop_state for m in P["lora"] if ops.lora_dropout_live(m)), None) if lora_live else None
+        draw = drop_state.take() if drop_state is not None else None
         if kv_cache is None and TRAIN_KV_BATCH and torch.is_grad_enabled() and (context.requires_grad or lora_live) and P["tblocks"]:
             # training: the [k;v] projections of the context for EVERY cross-attention as one GEMM (N = sum 2C = 24960 for the SD2 UNet)
             # and, in the backward, one input-gradient GEMM over the concatenated d[k;v] (K = 24960) instead of 16 + 16 launches on
@@ -539,7 +542,7 @@ class UNetModel(nn.Module):
                 segs += [(m, off + o_, n_, pm) for m, o_, n_, pm in (pt.attn2.kv.lora or ())]
                 off += pt.attn2.kv.w.shape[0]
             if segs:
-                kv_all = ops.lora_linear(ctx, w_all, None, segs)
+                kv_all = ops.lora_linear(ctx, w_all, None, segs, draw=draw)
             else:
                 kv_all = ops.gemm_conv(ctx, w_all, B=1, H=1, W=N * L, taps=1)
             parts = ops.split_cols(kv_all, [pt.attn2.kv.w.shape[0] for pt in P["tblocks"]])
@@ -583,7 +586,11 @@ class UNetModel(nn.Module):
                         # trainable LoRA factors: the first SpatialTransformer's input depends on no trainable tensor, yet its injected
                         # layers need the differentiable route (train_ops.grad_anchor)
                         act = E.Act(ops.grad_anchor(act.tok, anchor), act.N, act.H, act.W, tok2=act.tok2, gs=act.gs, gs2=act.gs2)
-                    act = ckpt(lambda a_, c_, p=p, d_=half: E.spatial_transformer(a_, c_, L, p, kv_cache, dup=d_), act, ctx)
+                    def st(a_, c_, p=p, d_=half):
+                        with E.lora_draw(draw):
+                            return E.spatial_transformer(a_, c_, L, p, kv_cache, dup=d_)
+
+                    act = ckpt(st, act, ctx)
                     half = False
                 elif kind == "down":
                     act = E.conv(act, p, gn_stats=True)

@@ -116,6 +116,24 @@ class lora_merged:
         _LORA_MERGED[0] = self.prev
 
 
+# LoRA dropout: the draw number of the UNet forward that is running.  UNetModel takes it from the model's LoraDropoutState once per
+# training forward and sets it around each SpatialTransformer (the closure a recomputing backward re-runs sets the same number again);
+# `linear` / `geglu_linear` hand it to train_ops.lora_linear, whose node keeps it in its meta.  None: no dropout layer is live.
+_LORA_DRAW = [None]
+
+
+class lora_draw:
+    def __init__(self, draw):
+        self.draw = draw
+
+    def __enter__(self):
+        self.prev = _LORA_DRAW[0]
+        _LORA_DRAW[0] = self.draw
+
+    def __exit__(self, *exc):
+        _LORA_DRAW[0] = self.prev
+
+
 def is_lora(mod):
     return hasattr(mod, "lora_down") and hasattr(mod, "lora_up") and hasattr(mod, "linear")
 
@@ -327,7 +345,7 @@ def linear(x, pl: PackedLinear, resid=None, M=None, want_stats=False):
     M = x.shape[0] if M is None else M
     if pl.lora:
         # unmerged LoRA: base GEMM + low-rank products as one differentiable op (no row statistics: its consumers run their LayerNorm)
-        y = ops.lora_linear(x, pl.w, pl.b, pl.lora, resid=resid)
+        y = ops.lora_linear(x, pl.w, pl.b, pl.lora, resid=resid, draw=_LORA_DRAW[0])
         return (y, None) if want_stats else y
     return ops.gemm_conv(x, pl.w, B=1, H=1, W=M, taps=1, bias=pl.b, resid=resid, want_stats=want_stats)
 
@@ -337,7 +355,7 @@ def geglu_linear(x, w, b, lora=None):
     projection's unmerged segments (PackedTBlock.geglu_lora) or None.  The one place the un-folded projection is launched from: the
     transformer block's feed-forward (_ffn) and the stand-alone GEGLU module."""
     if lora:
-        return ops.lora_linear(x, w, b, lora, geglu=True)
+        return ops.lora_linear(x, w, b, lora, geglu=True, draw=_LORA_DRAW[0])
     return ops.gemm_conv(x, w, B=1, H=1, W=x.shape[0], taps=1, bias=b, geglu=True)
 
 

@@ -1214,8 +1214,33 @@ def _rows16(t, name):
             and t.data_ptr() % 16 == 0), f"{name}: cuda fp16 / bf16 [rows, cols], unit column stride, 16-byte aligned rows"
 
 
-def lora_down(x, a, alpha=1.0, out=None):
-    """lr_lora_down: t [M, R] = alpha * x [M, K] . a [R, K]^T (R = padded rank 32 | 64; x may be a column slice of a wider buffer)."""
+class LoraDrop:
+    """The dropout mask of one LoRA layer at one draw, as the `drop=` argument of lora_down / lora_up / lora_wgrad (struct lr_lora_drop;
+    leftrefill_amd.lora_dropout states the mask).  colgrp: int32 device table [columns / 4] of the logical group of four columns behind each
+    stored group (lora_dropout.colgrp_of), None = identity."""
+
+    def __init__(self, seed, stream, draw, p, colgrp=None, threshold=None, inv_keep=None):
+        from . import lora_dropout
+        self.p, self.colgrp = float(p), colgrp
+        if colgrp is not None:
+            assert colgrp.is_cuda and colgrp.dtype == torch.int32 and colgrp.is_contiguous()
+        self.c = _lib.LoraDrop(int(seed) & (2 ** 64 - 1), int(stream) & 0xFFFFFFFF, int(draw) & 0xFFFFFFFF,
+                               lora_dropout.threshold(p) if threshold is None else int(threshold),
+                               lora_dropout.inv_keep(p) if inv_keep is None else float(inv_keep),
+                               None if colgrp is None else colgrp.data_ptr())
+
+    @property
+    def inv_keep(self):
+        return float(self.c.inv_keep)
+
+    def ref(self, columns):
+        assert self.colgrp is None or self.colgrp.numel() * 4 == columns, "colgrp: one entry per four columns of the masked operand"
+        return ctypes.byref(self.c)
+
+
+def lora_down(x, a, alpha=1.0, out=None, drop=None):
+    """lr_lora_down: t [M, R] = alpha * x [M, K] . a [R, K]^T (R = padded rank 32 | 64; x may be a column slice of a wider buffer).
+    drop (LoraDrop): lr_lora_down_drop, x masked at its own (row, column)."""
     lib = _lib.load()
     _rows16(x, "x")
     _rows16(a, "a")
@@ -1226,13 +1251,18 @@ def lora_down(x, a, alpha=1.0, out=None):
         out = torch.empty(M, R, device=x.device, dtype=x.dtype)
     _rows16(out, "out")
     assert out.shape == (M, R) and out.dtype == x.dtype
+    if drop is not None:
+        _lib.check(_fn(lib, "lr_lora_down_drop_f16", x.dtype)(_p(x), x.stride(0), _p(a), a.stride(0), _p(out), out.stride(0), M, K, R,
+                                                             float(alpha), drop.ref(K), _stream()), "lora_down_drop")
+        return out
     _lib.check(_fn(lib, "lr_lora_down_f16", x.dtype)(_p(x), x.stride(0), _p(a), a.stride(0), _p(out), out.stride(0), M, K, R, float(alpha),
                                                     _stream()), "lora_down")
     return out
 
 
-def lora_up(t, u, out=None, accumulate=False):
-    """lr_lora_up: out [M, N] (+)= t [M, R] . u [N, R]^T; `out` may be a column slice of a wider buffer (accumulate adds to what it holds)."""
+def lora_up(t, u, out=None, accumulate=False, drop=None):
+    """lr_lora_up: out [M, N] (+)= t [M, R] . u [N, R]^T; `out` may be a column slice of a wider buffer (accumulate adds to what it holds).
+    drop (LoraDrop): lr_lora_up_drop, the product masked (and scaled by inv_keep) at out's own (row, column)."""
     lib = _lib.load()
     _rows16(t, "t")
     _rows16(u, "u")
@@ -1244,6 +1274,10 @@ def lora_up(t, u, out=None, accumulate=False):
         out = torch.empty(M, N, device=t.device, dtype=t.dtype)
     _rows16(out, "out")
     assert out.shape == (M, N) and out.dtype == t.dtype
+    if drop is not None:
+        _lib.check(_fn(lib, "lr_lora_up_drop_f16", t.dtype)(_p(t), t.stride(0), _p(u), u.stride(0), _p(out), out.stride(0), M, N, R,
+                                                           int(bool(accumulate)), drop.ref(N), _stream()), "lora_up_drop")
+        return out
     _lib.check(_fn(lib, "lr_lora_up_f16", t.dtype)(_p(t), t.stride(0), _p(u), u.stride(0), _p(out), out.stride(0), M, N, R,
                                                   int(bool(accumulate)), _stream()), "lora_up")
     return out
@@ -1257,9 +1291,9 @@ def lora_wgrad_workspace(M, R, C, device):
     return torch.empty(nbytes // 4, device=device, dtype=torch.float32)
 
 
-def lora_wgrad(p, q, alpha=1.0, out=None, workspace=None):
+def lora_wgrad(p, q, alpha=1.0, out=None, workspace=None, drop=None):
     """lr_lora_wgrad: d [R, C] fp32 = alpha * p [M, R]^T . q [M, C] (fixed-order split over M, no atomics).  out / workspace
-    (lora_wgrad_workspace): buffers of a caller that keeps them."""
+    (lora_wgrad_workspace): buffers of a caller that keeps them.  drop (LoraDrop): lr_lora_wgrad_drop, q masked at its own (row, column)."""
     lib = _lib.load()
     _rows16(p, "p")
     _rows16(q, "q")
@@ -1270,6 +1304,10 @@ def lora_wgrad(p, q, alpha=1.0, out=None, workspace=None):
     d = torch.empty(R, C, device=p.device, dtype=torch.float32) if out is None else out
     assert ws.is_cuda and ws.dtype == torch.float32 and ws.is_contiguous() and d.is_cuda and d.dtype == torch.float32 and d.shape == (R, C) \
         and d.is_contiguous()
+    if drop is not None:
+        _lib.check(_fn(lib, "lr_lora_wgrad_drop_f16", p.dtype)(_p(p), p.stride(0), _p(q), q.stride(0), _p(d), C, M, R, C, float(alpha), _p(ws),
+                                                              ws.numel() * 4, drop.ref(C), _stream()), "lora_wgrad_drop")
+        return d
     _lib.check(_fn(lib, "lr_lora_wgrad_f16", p.dtype)(_p(p), p.stride(0), _p(q), q.stride(0), _p(d), C, M, R, C, float(alpha), _p(ws),
                                                      ws.numel() * 4, _stream()), "lora_wgrad")
     return d

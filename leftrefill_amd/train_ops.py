@@ -686,7 +686,12 @@ class _LoraLinear(torch.autograd.Function):
 
     backward: dx = g W (the base input-gradient GEMM) + sum_i dT_i down_i (lr_lora_up, accumulate), dT_i = scale_i g_i up_i (lr_lora_down);
               d up_i^T = scale_i T_i^T g_i,  d down_i = dT_i^T x  (lr_lora_wgrad: fp32, fixed-order split sums, no atomics).
-    Saved: x and every T_i = x down_i^T (16-bit, [M, padded rank]); the GEGLU form also keeps the projection, as _GemmConv does."""
+    Saved: x and every T_i = x down_i^T (16-bit, [M, padded rank]); the GEGLU form also keeps the projection, as _GemmConv does.
+
+    LoRA dropout (a segment whose meta carries (seed, stream, draw, p, colgrp)): y_i += scale_i inv_keep (T_i up_i^T) (.) keep_i through
+    lr_lora_up_drop; backward dT_i = scale_i inv_keep (g_i (.) keep_i) up_i (lr_lora_down_drop) and d up_i^T = scale_i inv_keep T_i^T
+    (g_i (.) keep_i) (lr_lora_wgrad_drop); d down_i and dx take dT_i as they are, the base GEMM the unmasked g.  The mask is regenerated
+    from the meta's numbers in every launch -- nothing is saved, and a recomputed forward sees the draw it was given."""
 
     @staticmethod
     def forward(ctx, x, resid, wt, bias, meta, *factors):
@@ -696,14 +701,14 @@ class _LoraLinear(torch.autograd.Function):
         M = x.shape[0]
         y = ops.gemm_conv(x, wt, B=1, H=1, W=M, taps=1, bias=bias, resid=resid)
         ts = []
-        for i, (off, n, scale, perm) in enumerate(segs):
+        for i, (off, n, scale, perm, drop) in enumerate(segs):
             down, up = factors[2 * i].detach(), factors[2 * i + 1].detach()
             R = ops.lora_pad_rank(down.shape[0])
             u = up * scale if scale != 1.0 else up
             if perm is not None:
                 u = u[perm]
             t = ops.lora_down(x, _operand16(down, 0, R, x.dtype))
-            ops.lora_up(t, _operand16(u, 1, R, x.dtype), out=y[:, off:off + n], accumulate=True)
+            ops.lora_up(t, _operand16(u, 1, R, x.dtype), out=y[:, off:off + n], accumulate=True, drop=drop and ops.LoraDrop(*drop))
             ts.append(t)
         ctx.meta, ctx.wt, ctx.has_resid, ctx.n_seg = meta, wt, resid is not None, len(segs)
         ctx.save_for_backward(x, *ts, *factors, *((y,) if geglu else ()))
@@ -723,20 +728,23 @@ class _LoraLinear(torch.autograd.Function):
         M, K = x.shape
         dx = ops.gemm_conv(g, dgrad_weight(ctx.wt, 1, 0, K), B=1, H=1, W=M, taps=1) if ctx.needs_input_grad[0] else None
         grads = []
-        for i, (off, n, scale, perm) in enumerate(segs):
+        for i, (off, n, scale, perm, drop) in enumerate(segs):
             down, up = factors[2 * i].detach(), factors[2 * i + 1].detach()
             r = down.shape[0]
             R = ops.lora_pad_rank(r)
             gi = g[:, off:off + n]
             upk = up if perm is None else up[perm]
-            dt = ops.lora_down(gi, _operand16(upk.t(), 0, R, x.dtype), alpha=scale)                            # [M, R] = scale g_i up
+            if drop:      # the mask of the forward, regenerated on g_i; 1 / (1 - p) rides in alpha
+                drop = ops.LoraDrop(*drop)
+                scale = scale * drop.inv_keep
+            dt = ops.lora_down(gi, _operand16(upk.t(), 0, R, x.dtype), alpha=scale, drop=drop)                 # [M, R] = scale g_i up
             if dx is not None:
                 ops.lora_up(dt, _operand16(down.t(), 1, R, x.dtype), out=dx, accumulate=True)                   # dx += dT down
             d_down = d_up = None
             if ctx.needs_input_grad[5 + 2 * i]:
                 d_down = ops.lora_wgrad(dt, x)[:r]                                                             # [r, K] fp32 (the first rows: contiguous)
             if ctx.needs_input_grad[6 + 2 * i]:
-                d_up = ops.lora_wgrad(ts[i], gi, alpha=scale)[:r].t()                                            # [n, r] fp32 (packed row order)
+                d_up = ops.lora_wgrad(ts[i], gi, alpha=scale, drop=drop)[:r].t()                                 # [n, r] fp32 (packed row order)
                 if perm is not None:
                     unp = torch.empty(n, r, device=d_up.device, dtype=d_up.dtype)
                     unp[perm] = d_up
@@ -747,17 +755,40 @@ class _LoraLinear(torch.autograd.Function):
         return (dx, dresid, None, None, None) + tuple(grads)
 
 
-def lora_linear(x, wt, bias, segs, resid=None, geglu=False):
+def _lora_colgrp(perm):
+    """The masked kernels' column-group table of a packed-row permutation, built once and kept on the permutation (i.e. per packing)."""
+    tab = getattr(perm, "_lr_colgrp", None)
+    if tab is None:
+        from . import lora_dropout
+        tab = perm._lr_colgrp = torch.from_numpy(lora_dropout.colgrp_of(perm.cpu().numpy())).to(perm.device)
+    return tab
+
+
+def lora_dropout_live(mod):
+    """True for a LoraInjectedLinear in training mode with p > 0; NotImplementedError when such a layer has no dropout stream."""
+    if not (mod.training and mod.dropout.p > 0):
+        return False
+    if getattr(mod, "drop_stream", None) is None or getattr(mod, "drop_state", None) is None:
+        raise NotImplementedError("LoRA dropout (dropout_p > 0 in training mode): this layer was not injected with a dropout stream -- only "
+                                  "inject_trainable_lora(..., dropout_p=p) gives a layer the stream id its mask is drawn from")
+    return True
+
+
+def lora_linear(x, wt, bias, segs, resid=None, geglu=False, draw=None):
     """Linear with unmerged LoRA factors.  segs: (LoraInjectedLinear, first output column, columns, packed-row permutation | None) per
     injected Linear whose rows lie in `wt` (engine.lora_segments).  Differentiable w.r.t. x, resid and the fp32 factors; under
-    torch.no_grad() it is the same launches without a graph."""
+    torch.no_grad() it is the same launches without a graph.  draw: the dropout draw number of this forward (LoraDropoutState.take), needed
+    when a segment's layer trains with dropout under autograd; without autograd (or with p == 0, or in eval mode) no mask is applied."""
     meta, factors = [], []
     for mod, off, n, perm in segs:
-        if mod.training and mod.dropout.p > 0:
-            raise NotImplementedError("LoRA dropout (dropout_p > 0 in training mode) is not implemented by the HIP path")
+        drop = None
+        if lora_dropout_live(mod) and torch.is_grad_enabled():
+            if draw is None:
+                raise ValueError("LoRA dropout needs the draw number of this forward (draw=)")
+            drop = (mod.drop_state.seed, mod.drop_stream, int(draw), float(mod.dropout.p), None if perm is None else _lora_colgrp(perm))
         if off % 8 or n % 8:
             raise ValueError("LoRA segment columns must be multiples of 8")
-        meta.append((off, n, float(mod.scale), perm))
+        meta.append((off, n, float(mod.scale), perm, drop))
         factors += [mod.lora_down.weight, mod.lora_up.weight]
     if resid is not None and geglu:
         raise ValueError("the GEGLU projection takes no residual")

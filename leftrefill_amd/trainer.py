@@ -97,6 +97,9 @@ class Trainer:
         assert not unexpected, f"{path}: keys the model does not have: {unexpected[:5]}"
         self.optimizer.load_state_dict(ckpt["optimizer_states"][0])
         self.global_step, self.current_epoch = int(ckpt["global_step"]), int(ckpt.get("epoch", 0))
+        hook = getattr(model, "on_load_checkpoint", None)      # Lightning's hook: state a module keeps outside its state_dict
+        if hook is not None:
+            hook(ckpt)
 
     # ---- the loop ----------------------------------------------------------------------------------------------------------------------
     def _setup(self, model):
