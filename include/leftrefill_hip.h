@@ -941,7 +941,7 @@ int lr_groupnorm_bwd_res_bf16(const lr_half* x1, int C1, const lr_half* x2, int 
     float eps, int silu, float* bwd_partials, lr_half* dx1, lr_half* dx2, lr_stream_t s);
 int lr_nchw_f32_to_nhwc_bf16(const float* x1, int C1, const float* x2, int C2, lr_half* y, int Cpad, int N, int H, int
     W, lr_stream_t s);
-int lr_nhwc_f16_to_nchw_bf16(const lr_half* y, int Cstride, int C, void* out, int out_is_f32, int N, int H, int W,
+int lr_nhwc_f16_to_nchw_bf16(const lr_half* y, int Cstride, int C, void* out_nchw, int out_is_f32, int N, int H, int W,
     lr_stream_t s);
 int lr_timestep_embedding_bf16(const int64_t* t, int N, int dim, lr_half* out, lr_stream_t s);
 int lr_timestep_embedding_f32_bf16(const float* t, int N, int dim, lr_half* out, lr_stream_t s);
@@ -982,10 +982,10 @@ int lr_attention_lse_bf16(const lr_half* q, int ldq, const lr_half* k, int ldk, 
 int lr_attention_vt_bf16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* vt, int ld_vt, lr_half*
     o, int ldo, int B, int heads, int Nq, int Nkv, float scale, lr_stream_t s);
 int lr_transpose_v_bf16(const lr_half* v, int ldv, lr_half* vt, int ld_vt, int B, int heads, int Nkv, lr_stream_t s);
-int lr_attention_bwd_bf16(const lr_attn_bwd_args* a, lr_stream_t s);
+int lr_attention_bwd_bf16(const lr_attn_bwd_args* args, lr_stream_t s);
 int lr_attention_causal_lse_bf16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o,
     int ldo, float* lse, int B, int heads, int N, float scale, lr_stream_t s);
-int lr_attention_causal_bwd_bf16(const lr_attn_bwd_args* a, lr_stream_t s);
+int lr_attention_causal_bwd_bf16(const lr_attn_bwd_args* args, lr_stream_t s);
 int lr_gelu_fwd_bf16(const lr_half* pre, lr_half* y, int64_t n, lr_stream_t s);
 int lr_gelu_bwd_bf16(const lr_half* pre, const lr_half* dy, lr_half* dpre, int64_t n, lr_stream_t s);
 int lr_xattn_block_bf16(const lr_xattn_args* args, lr_stream_t s);

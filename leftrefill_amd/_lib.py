@@ -147,6 +147,12 @@ class OptimGroup(ctypes.Structure):
                 ("lr_table", c_void_p), ("lr_len", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+# struct of include/leftrefill_hip.h -> its mirror above (tests/test_abi_cpu.py holds every field's name, offset and size to the header)
+STRUCTS = {"lr_gemm_args": GemmArgs, "lr_attn_bwd_args": AttnBwdArgs, "lr_xattn_args": XattnArgs, "lr_row_copy_job": RowCopyJob,
+           "lr_stin_args": StinArgs, "lr_rowlin_args": RowlinArgs, "lr_ffn_args": FfnArgs, "lr_lpips_args": LpipsArgs,
+           "lr_prep_job": PrepJob, "lr_nvs_job": NvsJob, "lr_pil_job": PilJob, "lr_lora_drop": LoraDrop, "lr_grid_source": GridSource,
+           "lr_optim_tensor": OptimTensor, "lr_optim_group": OptimGroup}
+
 # symbol -> argtypes; every function returns int
 SIGNATURES = {
     "lr_abi_version": [],

@@ -700,15 +700,9 @@ static int lr_transpose_v_t(const lr_half* v, int ldv, lr_half* vt, int ld_vt, i
 }
 
 // ---- C ABI: every entry point in its fp16 and bf16 form -------------------------------------------------------------
-extern "C" int lr_attention_f16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o, int ldo, int B, int heads, int Nq, int Nkv, float scale, lr_stream_t s) { return lr_attention_t<f16>(q, ldq, k, ldk, v, ldv, o, ldo, B, heads, Nq, Nkv, scale, s); }
-extern "C" int lr_attention_bf16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o, int ldo, int B, int heads, int Nq, int Nkv, float scale, lr_stream_t s) { return lr_attention_t<bf16>(q, ldq, k, ldk, v, ldv, o, ldo, B, heads, Nq, Nkv, scale, s); }
-extern "C" int lr_attention_causal_f16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o, int ldo, int B, int heads, int N, float scale, lr_stream_t s) { return lr_attention_causal_t<f16>(q, ldq, k, ldk, v, ldv, o, ldo, B, heads, N, scale, s); }
-extern "C" int lr_attention_causal_bf16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o, int ldo, int B, int heads, int N, float scale, lr_stream_t s) { return lr_attention_causal_t<bf16>(q, ldq, k, ldk, v, ldv, o, ldo, B, heads, N, scale, s); }
-extern "C" int lr_attention_causal_lse_f16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o, int ldo, float* lse, int B, int heads, int N, float scale, lr_stream_t s) { return lr_attention_causal_lse_t<f16>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, heads, N, scale, s); }
-extern "C" int lr_attention_causal_lse_bf16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o, int ldo, float* lse, int B, int heads, int N, float scale, lr_stream_t s) { return lr_attention_causal_lse_t<bf16>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, heads, N, scale, s); }
-extern "C" int lr_attention_lse_f16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o, int ldo, float* lse, int B, int heads, int Nq, int Nkv, float scale, lr_stream_t s) { return lr_attention_lse_t<f16>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nkv, scale, s); }
-extern "C" int lr_attention_lse_bf16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o, int ldo, float* lse, int B, int heads, int Nq, int Nkv, float scale, lr_stream_t s) { return lr_attention_lse_t<bf16>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nkv, scale, s); }
-extern "C" int lr_attention_vt_f16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* vt, int ld_vt, lr_half* o, int ldo, int B, int heads, int Nq, int Nkv, float scale, lr_stream_t s) { return lr_attention_vt_t<f16>(q, ldq, k, ldk, vt, ld_vt, o, ldo, B, heads, Nq, Nkv, scale, s); }
-extern "C" int lr_attention_vt_bf16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* vt, int ld_vt, lr_half* o, int ldo, int B, int heads, int Nq, int Nkv, float scale, lr_stream_t s) { return lr_attention_vt_t<bf16>(q, ldq, k, ldk, vt, ld_vt, o, ldo, B, heads, Nq, Nkv, scale, s); }
-extern "C" int lr_transpose_v_f16(const lr_half* v, int ldv, lr_half* vt, int ld_vt, int B, int heads, int Nkv, lr_stream_t s) { return lr_transpose_v_t<f16>(v, ldv, vt, ld_vt, B, heads, Nkv, s); }
-extern "C" int lr_transpose_v_bf16(const lr_half* v, int ldv, lr_half* vt, int ld_vt, int B, int heads, int Nkv, lr_stream_t s) { return lr_transpose_v_t<bf16>(v, ldv, vt, ld_vt, B, heads, Nkv, s); }
+LR_ABI_PAIR(lr_attention_f16, lr_attention_bf16, (const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o, int ldo, int B, int heads, int Nq, int Nkv, float scale, lr_stream_t s), lr_attention_t<T>(q, ldq, k, ldk, v, ldv, o, ldo, B, heads, Nq, Nkv, scale, s))
+LR_ABI_PAIR(lr_attention_causal_f16, lr_attention_causal_bf16, (const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o, int ldo, int B, int heads, int N, float scale, lr_stream_t s), lr_attention_causal_t<T>(q, ldq, k, ldk, v, ldv, o, ldo, B, heads, N, scale, s))
+LR_ABI_PAIR(lr_attention_causal_lse_f16, lr_attention_causal_lse_bf16, (const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o, int ldo, float* lse, int B, int heads, int N, float scale, lr_stream_t s), lr_attention_causal_lse_t<T>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, heads, N, scale, s))
+LR_ABI_PAIR(lr_attention_lse_f16, lr_attention_lse_bf16, (const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* v, int ldv, lr_half* o, int ldo, float* lse, int B, int heads, int Nq, int Nkv, float scale, lr_stream_t s), lr_attention_lse_t<T>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nkv, scale, s))
+LR_ABI_PAIR(lr_attention_vt_f16, lr_attention_vt_bf16, (const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* vt, int ld_vt, lr_half* o, int ldo, int B, int heads, int Nq, int Nkv, float scale, lr_stream_t s), lr_attention_vt_t<T>(q, ldq, k, ldk, vt, ld_vt, o, ldo, B, heads, Nq, Nkv, scale, s))
+LR_ABI_PAIR(lr_transpose_v_f16, lr_transpose_v_bf16, (const lr_half* v, int ldv, lr_half* vt, int ld_vt, int B, int heads, int Nkv, lr_stream_t s), lr_transpose_v_t<T>(v, ldv, vt, ld_vt, B, heads, Nkv, s))

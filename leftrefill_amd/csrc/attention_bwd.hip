@@ -429,7 +429,5 @@ static int lr_attention_bwd_t(const lr_attn_bwd_args* a, lr_stream_t s) {
 }
 
 // ---- C ABI: every entry point in its fp16 and bf16 form -------------------------------------------------------------
-extern "C" int lr_attention_bwd_f16(const lr_attn_bwd_args* a, lr_stream_t s) { return lr_attention_bwd_t<f16>(a, s); }
-extern "C" int lr_attention_bwd_bf16(const lr_attn_bwd_args* a, lr_stream_t s) { return lr_attention_bwd_t<bf16>(a, s); }
-extern "C" int lr_attention_causal_bwd_f16(const lr_attn_bwd_args* a, lr_stream_t s) { return lr_attention_bwd_t<f16, true>(a, s); }
-extern "C" int lr_attention_causal_bwd_bf16(const lr_attn_bwd_args* a, lr_stream_t s) { return lr_attention_bwd_t<bf16, true>(a, s); }
+LR_ABI_PAIR(lr_attention_bwd_f16, lr_attention_bwd_bf16, (const lr_attn_bwd_args* a, lr_stream_t s), lr_attention_bwd_t<T>(a, s))
+LR_ABI_PAIR(lr_attention_causal_bwd_f16, lr_attention_causal_bwd_bf16, (const lr_attn_bwd_args* a, lr_stream_t s), lr_attention_bwd_t<T, true>(a, s))

@@ -198,5 +198,4 @@ static int lr_attention_probe_t(const lr_half* q, int ldq, const lr_half* k, int
   return lr_launch_status();
 }
 
-extern "C" int lr_attention_probe_f16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* cols, int ldc, int ncols, float* out, int B, int heads, int Nq, int Nkv, float scale, float alpha, float beta, lr_stream_t s) { return lr_attention_probe_t<f16>(q, ldq, k, ldk, cols, ldc, ncols, out, B, heads, Nq, Nkv, scale, alpha, beta, s); }
-extern "C" int lr_attention_probe_bf16(const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* cols, int ldc, int ncols, float* out, int B, int heads, int Nq, int Nkv, float scale, float alpha, float beta, lr_stream_t s) { return lr_attention_probe_t<bf16>(q, ldq, k, ldk, cols, ldc, ncols, out, B, heads, Nq, Nkv, scale, alpha, beta, s); }
+LR_ABI_PAIR(lr_attention_probe_f16, lr_attention_probe_bf16, (const lr_half* q, int ldq, const lr_half* k, int ldk, const lr_half* cols, int ldc, int ncols, float* out, int B, int heads, int Nq, int Nkv, float scale, float alpha, float beta, lr_stream_t s), lr_attention_probe_t<T>(q, ldq, k, ldk, cols, ldc, ncols, out, B, heads, Nq, Nkv, scale, alpha, beta, s))

@@ -23,7 +23,13 @@ int lr_dev_get(const char* name, int dflt);
 
 typedef _Float16 f16;
 typedef __bf16 bf16;          // the second 16-bit activation / weight type (LR_DTYPE_BF16): same layouts, same kernels
-template <typename T> using vec2 = T __attribute__((ext_vector_type(2)));
+// One fp16/bf16 pair of C ABI entry points (each declared on its own in include/leftrefill_hip.h): the parameter list once and the
+// forwarded call once, written in terms of T -- f16 inside NAME16, bf16 inside NAMEBF.  The call comes last so that it may hold commas:
+//   LR_ABI_PAIR(lr_gelu_fwd_f16, lr_gelu_fwd_bf16, (const lr_half* pre, lr_half* y, int64_t n, lr_stream_t s), lr_gelu_t<T, false>(pre, nullptr, y, n, s))
+#define LR_ABI_PAIR(NAME16, NAMEBF, PARAMS, ...)                       \
+  extern "C" int NAME16 PARAMS { using T = f16; return __VA_ARGS__; }  \
+  extern "C" int NAMEBF PARAMS { using T = bf16; return __VA_ARGS__; }
+template <typename T> using vec2 =T __attribute__((ext_vector_type(2)));
 template <typename T> using vec4 = T __attribute__((ext_vector_type(4)));
 template <typename T> using vec8 = T __attribute__((ext_vector_type(8)));
 typedef f16 f16x2 __attribute__((ext_vector_type(2)));

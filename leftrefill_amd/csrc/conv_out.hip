@@ -200,5 +200,4 @@ static int lr_gn_conv_out_t(const lr_half* x, int B, int H, int W, int C, const 
   return lr_launch_status();
 }
 
-extern "C" int lr_gn_conv_out_f16(const lr_half* x, int B, int H, int W, int C, const float* gpart, int chunks, const float* gamma, const float* beta, float eps, const lr_half* w, int ldw, const float* bias, int Cout, lr_half* y, lr_stream_t s) { return lr_gn_conv_out_t<f16>(x, B, H, W, C, gpart, chunks, gamma, beta, eps, w, ldw, bias, Cout, y, s); }
-extern "C" int lr_gn_conv_out_bf16(const lr_half* x, int B, int H, int W, int C, const float* gpart, int chunks, const float* gamma, const float* beta, float eps, const lr_half* w, int ldw, const float* bias, int Cout, lr_half* y, lr_stream_t s) { return lr_gn_conv_out_t<bf16>(x, B, H, W, C, gpart, chunks, gamma, beta, eps, w, ldw, bias, Cout, y, s); }
+LR_ABI_PAIR(lr_gn_conv_out_f16, lr_gn_conv_out_bf16, (const lr_half* x, int B, int H, int W, int C, const float* gpart, int chunks, const float* gamma, const float* beta, float eps, const lr_half* w, int ldw, const float* bias, int Cout, lr_half* y, lr_stream_t s), lr_gn_conv_out_t<T>(x, B, H, W, C, gpart, chunks, gamma, beta, eps, w, ldw, bias, Cout, y, s))

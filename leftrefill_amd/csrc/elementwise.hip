@@ -934,46 +934,26 @@ static int lr_mv_scatter_bwd_t(const lr_half* dx, lr_half* dseq, int b, int v, i
 }
 
 // ---- C ABI: every entry point in its fp16 and bf16 form -------------------------------------------------------------
-extern "C" int lr_nchw_f32_to_nhwc_f16(const float* x1, int C1, const float* x2, int C2, lr_half* y, int Cpad, int N, int H, int W, lr_stream_t s) { return lr_nchw_f32_to_nhwc_t<f16>(x1, C1, x2, C2, y, Cpad, N, H, W, s); }
-extern "C" int lr_nchw_f32_to_nhwc_bf16(const float* x1, int C1, const float* x2, int C2, lr_half* y, int Cpad, int N, int H, int W, lr_stream_t s) { return lr_nchw_f32_to_nhwc_t<bf16>(x1, C1, x2, C2, y, Cpad, N, H, W, s); }
-extern "C" int lr_nhwc_f16_to_nchw(const lr_half* y, int Cstride, int C, void* out, int out_is_f32, int N, int H, int W, lr_stream_t s) { return lr_nhwc_f16_to_nchw_t<f16>(y, Cstride, C, out, out_is_f32, N, H, W, s); }
-extern "C" int lr_nhwc_f16_to_nchw_bf16(const lr_half* y, int Cstride, int C, void* out, int out_is_f32, int N, int H, int W, lr_stream_t s) { return lr_nhwc_f16_to_nchw_t<bf16>(y, Cstride, C, out, out_is_f32, N, H, W, s); }
-extern "C" int lr_timestep_embedding(const int64_t* t, int N, int dim, lr_half* out, lr_stream_t s) { return lr_timestep_embedding_t<int64_t, f16>(t, N, dim, out, s); }
-extern "C" int lr_timestep_embedding_bf16(const int64_t* t, int N, int dim, lr_half* out, lr_stream_t s) { return lr_timestep_embedding_t<int64_t, bf16>(t, N, dim, out, s); }
-extern "C" int lr_timestep_embedding_f32(const float* t, int N, int dim, lr_half* out, lr_stream_t s) { return lr_timestep_embedding_t<float, f16>(t, N, dim, out, s); }
-extern "C" int lr_timestep_embedding_f32_bf16(const float* t, int N, int dim, lr_half* out, lr_stream_t s) { return lr_timestep_embedding_t<float, bf16>(t, N, dim, out, s); }
-extern "C" int lr_linear_small_m(const lr_half* a, int lda, const lr_half* w, const float* bias, lr_half* out, int ldo, int M, int N, int K, int act_in, int act_out, lr_stream_t s) { return lr_linear_small_m_t<f16>(a, lda, w, bias, out, ldo, M, N, K, act_in, act_out, s); }
-extern "C" int lr_linear_small_m_bf16(const lr_half* a, int lda, const lr_half* w, const float* bias, lr_half* out, int ldo, int M, int N, int K, int act_in, int act_out, lr_stream_t s) { return lr_linear_small_m_t<bf16>(a, lda, w, bias, out, ldo, M, N, K, act_in, act_out, s); }
-extern "C" int lr_mv_gather(const lr_half* x, lr_half* seq, int b, int v, int s, int C, lr_stream_t st) { return lr_mv_gather_t<f16>(x, seq, b, v, s, C, st); }
-extern "C" int lr_mv_gather_bf16(const lr_half* x, lr_half* seq, int b, int v, int s, int C, lr_stream_t st) { return lr_mv_gather_t<bf16>(x, seq, b, v, s, C, st); }
-extern "C" int lr_mv_scatter(const lr_half* seq, lr_half* x, int b, int v, int s, int C, lr_stream_t st) { return lr_mv_scatter_t<f16>(seq, x, b, v, s, C, st); }
-extern "C" int lr_mv_scatter_bf16(const lr_half* seq, lr_half* x, int b, int v, int s, int C, lr_stream_t st) { return lr_mv_scatter_t<bf16>(seq, x, b, v, s, C, st); }
-extern "C" int lr_ddim_cfg_step(const float* x, const void* eps, int eps_is_f32, const float* noise, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, lr_stream_t s) { return lr_ddim_cfg_step_t<f16>(x, eps, eps_is_f32, noise, x_prev, pred_x0, numel, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, s); }
-extern "C" int lr_ddim_cfg_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* noise, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, lr_stream_t s) { return lr_ddim_cfg_step_t<bf16>(x, eps, eps_is_f32, noise, x_prev, pred_x0, numel, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, s); }
-extern "C" int lr_plms_cfg_step(const float* x, const void* eps, int eps_is_f32, const float* const* hist, int n_hist, const float* weights, float divisor, float* e_out, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float a_t, float a_prev, float sqrt_one_minus_at, lr_stream_t s) { return lr_plms_cfg_step_t<f16>(x, eps, eps_is_f32, hist, n_hist, weights, divisor, e_out, x_prev, pred_x0, numel, cfg_scale, a_t, a_prev, sqrt_one_minus_at, s); }
-extern "C" int lr_plms_cfg_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* const* hist, int n_hist, const float* weights, float divisor, float* e_out, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float a_t, float a_prev, float sqrt_one_minus_at, lr_stream_t s) { return lr_plms_cfg_step_t<bf16>(x, eps, eps_is_f32, hist, n_hist, weights, divisor, e_out, x_prev, pred_x0, numel, cfg_scale, a_t, a_prev, sqrt_one_minus_at, s); }
-extern "C" int lr_dpmpp_cfg_step(const float* x, const void* eps, int eps_is_f32, const float* x0_prev, float* x0_out, float* x_next, int64_t numel, float cfg_scale, float sigma_s, float alpha_s, float ratio, float c, float c_half, float inv_r0, lr_stream_t s) { return lr_dpmpp_cfg_step_t<f16>(x, eps, eps_is_f32, x0_prev, x0_out, x_next, numel, cfg_scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0, s); }
-extern "C" int lr_dpmpp_cfg_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* x0_prev, float* x0_out, float* x_next, int64_t numel, float cfg_scale, float sigma_s, float alpha_s, float ratio, float c, float c_half, float inv_r0, lr_stream_t s) { return lr_dpmpp_cfg_step_t<bf16>(x, eps, eps_is_f32, x0_prev, x0_out, x_next, numel, cfg_scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0, s); }
-extern "C" int lr_ddim_inv_cfg_step(const float* x, const void* eps, int eps_is_f32, float* x_next, int64_t numel, float cfg_scale, float c1, float c2, lr_stream_t s) { return lr_ddim_inv_cfg_step_t<f16>(x, eps, eps_is_f32, x_next, numel, cfg_scale, c1, c2, s); }
-extern "C" int lr_ddim_inv_cfg_step_bf16(const float* x, const void* eps, int eps_is_f32, float* x_next, int64_t numel, float cfg_scale, float c1, float c2, lr_stream_t s) { return lr_ddim_inv_cfg_step_t<bf16>(x, eps, eps_is_f32, x_next, numel, cfg_scale, c1, c2, s); }
-extern "C" int lr_ddim_cfg3_step(const float* x, const void* eps, int eps_is_f32, const float* noise, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float cond_weight, float one_minus_cond_weight, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, lr_stream_t s) { return lr_ddim_cfg3_step_t<f16>(x, eps, eps_is_f32, noise, x_prev, pred_x0, numel, cfg_scale, cond_weight, one_minus_cond_weight, a_t, a_prev, sigma_t, sqrt_one_minus_at, s); }
-extern "C" int lr_ddim_cfg3_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* noise, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float cond_weight, float one_minus_cond_weight, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, lr_stream_t s) { return lr_ddim_cfg3_step_t<bf16>(x, eps, eps_is_f32, noise, x_prev, pred_x0, numel, cfg_scale, cond_weight, one_minus_cond_weight, a_t, a_prev, sigma_t, sqrt_one_minus_at, s); }
-extern "C" int lr_ddpm_step(const float* x, const void* eps, int eps_is_f32, const float* noise, const float* known_x0, const float* known_noise, const float* mask, int64_t mask_chw, int64_t mask_hw, int clip_denoised, float* x_prev, float* x0_out, int64_t numel, float sqrt_recip_ac, float sqrt_recipm1_ac, float coef1, float coef2, float sigma, float sqrt_ac, float sqrt_one_minus_ac, lr_stream_t s) { return lr_ddpm_step_t<f16>(x, eps, eps_is_f32, noise, known_x0, known_noise, mask, mask_chw, mask_hw, clip_denoised, x_prev, x0_out, numel, sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, sigma, sqrt_ac, sqrt_one_minus_ac, s); }
-extern "C" int lr_ddpm_step_bf16(const float* x, const void* eps, int eps_is_f32, const float* noise, const float* known_x0, const float* known_noise, const float* mask, int64_t mask_chw, int64_t mask_hw, int clip_denoised, float* x_prev, float* x0_out, int64_t numel, float sqrt_recip_ac, float sqrt_recipm1_ac, float coef1, float coef2, float sigma, float sqrt_ac, float sqrt_one_minus_ac, lr_stream_t s) { return lr_ddpm_step_t<bf16>(x, eps, eps_is_f32, noise, known_x0, known_noise, mask, mask_chw, mask_hw, clip_denoised, x_prev, x0_out, numel, sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, sigma, sqrt_ac, sqrt_one_minus_ac, s); }
-extern "C" int lr_geglu_fwd(const lr_half* pre, lr_half* out, int M, int H, lr_stream_t s) { return lr_geglu_fwd_t<f16>(pre, out, M, H, s); }
-extern "C" int lr_geglu_fwd_bf16(const lr_half* pre, lr_half* out, int M, int H, lr_stream_t s) { return lr_geglu_fwd_t<bf16>(pre, out, M, H, s); }
-extern "C" int lr_geglu_bwd(const lr_half* pre, const lr_half* dy, lr_half* dpre, int M, int H, lr_stream_t s) { return lr_geglu_bwd_t<f16>(pre, dy, dpre, M, H, s); }
-extern "C" int lr_geglu_bwd_bf16(const lr_half* pre, const lr_half* dy, lr_half* dpre, int M, int H, lr_stream_t s) { return lr_geglu_bwd_t<bf16>(pre, dy, dpre, M, H, s); }
-extern "C" int lr_gelu_fwd_f16(const lr_half* pre, lr_half* y, int64_t n, lr_stream_t s) { return lr_gelu_t<f16, false>(pre, nullptr, y, n, s); }
-extern "C" int lr_gelu_fwd_bf16(const lr_half* pre, lr_half* y, int64_t n, lr_stream_t s) { return lr_gelu_t<bf16, false>(pre, nullptr, y, n, s); }
-extern "C" int lr_gelu_bwd_f16(const lr_half* pre, const lr_half* dy, lr_half* dpre, int64_t n, lr_stream_t s) { return lr_gelu_t<f16, true>(pre, dy, dpre, n, s); }
-extern "C" int lr_gelu_bwd_bf16(const lr_half* pre, const lr_half* dy, lr_half* dpre, int64_t n, lr_stream_t s) { return lr_gelu_t<bf16, true>(pre, dy, dpre, n, s); }
-extern "C" int lr_sumpool2x2(const lr_half* x, lr_half* y, int N, int H, int W, int C, lr_stream_t s) { return lr_sumpool2x2_t<f16>(x, y, N, H, W, C, s); }
-extern "C" int lr_sumpool2x2_bf16(const lr_half* x, lr_half* y, int N, int H, int W, int C, lr_stream_t s) { return lr_sumpool2x2_t<bf16>(x, y, N, H, W, C, s); }
-extern "C" int lr_mv_gather_bwd(const lr_half* dseq, lr_half* dx, int b, int v, int s, int C, lr_stream_t st) { return lr_mv_gather_bwd_t<f16>(dseq, dx, b, v, s, C, st); }
-extern "C" int lr_mv_gather_bwd_bf16(const lr_half* dseq, lr_half* dx, int b, int v, int s, int C, lr_stream_t st) { return lr_mv_gather_bwd_t<bf16>(dseq, dx, b, v, s, C, st); }
-extern "C" int lr_mv_scatter_bwd(const lr_half* dx, lr_half* dseq, int b, int v, int s, int C, lr_stream_t st) { return lr_mv_scatter_bwd_t<f16>(dx, dseq, b, v, s, C, st); }
-extern "C" int lr_mv_scatter_bwd_bf16(const lr_half* dx, lr_half* dseq, int b, int v, int s, int C, lr_stream_t st) { return lr_mv_scatter_bwd_t<bf16>(dx, dseq, b, v, s, C, st); }
+LR_ABI_PAIR(lr_nchw_f32_to_nhwc_f16, lr_nchw_f32_to_nhwc_bf16, (const float* x1, int C1, const float* x2, int C2, lr_half* y, int Cpad, int N, int H, int W, lr_stream_t s), lr_nchw_f32_to_nhwc_t<T>(x1, C1, x2, C2, y, Cpad, N, H, W, s))
+LR_ABI_PAIR(lr_nhwc_f16_to_nchw, lr_nhwc_f16_to_nchw_bf16, (const lr_half* y, int Cstride, int C, void* out, int out_is_f32, int N, int H, int W, lr_stream_t s), lr_nhwc_f16_to_nchw_t<T>(y, Cstride, C, out, out_is_f32, N, H, W, s))
+LR_ABI_PAIR(lr_timestep_embedding, lr_timestep_embedding_bf16, (const int64_t* t, int N, int dim, lr_half* out, lr_stream_t s), lr_timestep_embedding_t<int64_t, T>(t, N, dim, out, s))
+LR_ABI_PAIR(lr_timestep_embedding_f32, lr_timestep_embedding_f32_bf16, (const float* t, int N, int dim, lr_half* out, lr_stream_t s), lr_timestep_embedding_t<float, T>(t, N, dim, out, s))
+LR_ABI_PAIR(lr_linear_small_m, lr_linear_small_m_bf16, (const lr_half* a, int lda, const lr_half* w, const float* bias, lr_half* out, int ldo, int M, int N, int K, int act_in, int act_out, lr_stream_t s), lr_linear_small_m_t<T>(a, lda, w, bias, out, ldo, M, N, K, act_in, act_out, s))
+LR_ABI_PAIR(lr_mv_gather, lr_mv_gather_bf16, (const lr_half* x, lr_half* seq, int b, int v, int s, int C, lr_stream_t st), lr_mv_gather_t<T>(x, seq, b, v, s, C, st))
+LR_ABI_PAIR(lr_mv_scatter, lr_mv_scatter_bf16, (const lr_half* seq, lr_half* x, int b, int v, int s, int C, lr_stream_t st), lr_mv_scatter_t<T>(seq, x, b, v, s, C, st))
+LR_ABI_PAIR(lr_ddim_cfg_step, lr_ddim_cfg_step_bf16, (const float* x, const void* eps, int eps_is_f32, const float* noise, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, lr_stream_t s), lr_ddim_cfg_step_t<T>(x, eps, eps_is_f32, noise, x_prev, pred_x0, numel, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, s))
+LR_ABI_PAIR(lr_plms_cfg_step, lr_plms_cfg_step_bf16, (const float* x, const void* eps, int eps_is_f32, const float* const* hist, int n_hist, const float* weights, float divisor, float* e_out, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float a_t, float a_prev, float sqrt_one_minus_at, lr_stream_t s), lr_plms_cfg_step_t<T>(x, eps, eps_is_f32, hist, n_hist, weights, divisor, e_out, x_prev, pred_x0, numel, cfg_scale, a_t, a_prev, sqrt_one_minus_at, s))
+LR_ABI_PAIR(lr_dpmpp_cfg_step, lr_dpmpp_cfg_step_bf16, (const float* x, const void* eps, int eps_is_f32, const float* x0_prev, float* x0_out, float* x_next, int64_t numel, float cfg_scale, float sigma_s, float alpha_s, float ratio, float c, float c_half, float inv_r0, lr_stream_t s), lr_dpmpp_cfg_step_t<T>(x, eps, eps_is_f32, x0_prev, x0_out, x_next, numel, cfg_scale, sigma_s, alpha_s, ratio, c, c_half, inv_r0, s))
+LR_ABI_PAIR(lr_ddim_inv_cfg_step, lr_ddim_inv_cfg_step_bf16, (const float* x, const void* eps, int eps_is_f32, float* x_next, int64_t numel, float cfg_scale, float c1, float c2, lr_stream_t s), lr_ddim_inv_cfg_step_t<T>(x, eps, eps_is_f32, x_next, numel, cfg_scale, c1, c2, s))
+LR_ABI_PAIR(lr_ddim_cfg3_step, lr_ddim_cfg3_step_bf16, (const float* x, const void* eps, int eps_is_f32, const float* noise, float* x_prev, float* pred_x0, int64_t numel, float cfg_scale, float cond_weight, float one_minus_cond_weight, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, lr_stream_t s), lr_ddim_cfg3_step_t<T>(x, eps, eps_is_f32, noise, x_prev, pred_x0, numel, cfg_scale, cond_weight, one_minus_cond_weight, a_t, a_prev, sigma_t, sqrt_one_minus_at, s))
+LR_ABI_PAIR(lr_ddpm_step, lr_ddpm_step_bf16, (const float* x, const void* eps, int eps_is_f32, const float* noise, const float* known_x0, const float* known_noise, const float* mask, int64_t mask_chw, int64_t mask_hw, int clip_denoised, float* x_prev, float* x0_out, int64_t numel, float sqrt_recip_ac, float sqrt_recipm1_ac, float coef1, float coef2, float sigma, float sqrt_ac, float sqrt_one_minus_ac, lr_stream_t s), lr_ddpm_step_t<T>(x, eps, eps_is_f32, noise, known_x0, known_noise, mask, mask_chw, mask_hw, clip_denoised, x_prev, x0_out, numel, sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, sigma, sqrt_ac, sqrt_one_minus_ac, s))
+LR_ABI_PAIR(lr_geglu_fwd, lr_geglu_fwd_bf16, (const lr_half* pre, lr_half* out, int M, int H, lr_stream_t s), lr_geglu_fwd_t<T>(pre, out, M, H, s))
+LR_ABI_PAIR(lr_geglu_bwd, lr_geglu_bwd_bf16, (const lr_half* pre, const lr_half* dy, lr_half* dpre, int M, int H, lr_stream_t s), lr_geglu_bwd_t<T>(pre, dy, dpre, M, H, s))
+LR_ABI_PAIR(lr_gelu_fwd_f16, lr_gelu_fwd_bf16, (const lr_half* pre, lr_half* y, int64_t n, lr_stream_t s), lr_gelu_t<T, false>(pre, nullptr, y, n, s))
+LR_ABI_PAIR(lr_gelu_bwd_f16, lr_gelu_bwd_bf16, (const lr_half* pre, const lr_half* dy, lr_half* dpre, int64_t n, lr_stream_t s), lr_gelu_t<T, true>(pre, dy, dpre, n, s))
+LR_ABI_PAIR(lr_sumpool2x2, lr_sumpool2x2_bf16, (const lr_half* x, lr_half* y, int N, int H, int W, int C, lr_stream_t s), lr_sumpool2x2_t<T>(x, y, N, H, W, C, s))
+LR_ABI_PAIR(lr_mv_gather_bwd, lr_mv_gather_bwd_bf16, (const lr_half* dseq, lr_half* dx, int b, int v, int s, int C, lr_stream_t st), lr_mv_gather_bwd_t<T>(dseq, dx, b, v, s, C, st))
+LR_ABI_PAIR(lr_mv_scatter_bwd, lr_mv_scatter_bwd_bf16, (const lr_half* dx, lr_half* dseq, int b, int v, int s, int C, lr_stream_t st), lr_mv_scatter_bwd_t<T>(dx, dseq, b, v, s, C, st))
 extern "C" int lr_row_copy(const lr_row_copy_job* jobs, int n_jobs, lr_stream_t st) {
   if (!jobs || n_jobs < 1 || n_jobs > 4) return LR_E_ARG;
   RowCopyJobs J;

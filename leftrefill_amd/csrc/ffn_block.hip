@@ -414,5 +414,4 @@ static int ffn_block_t(const lr_ffn_args* a, lr_stream_t s) {
                        (hipStream_t)s, P);
 }
 
-extern "C" int lr_ffn_block_f16(const lr_ffn_args* a, lr_stream_t s) { return ffn_block_t<f16>(a, s); }
-extern "C" int lr_ffn_block_bf16(const lr_ffn_args* a, lr_stream_t s) { return ffn_block_t<bf16>(a, s); }
+LR_ABI_PAIR(lr_ffn_block_f16, lr_ffn_block_bf16, (const lr_ffn_args* a, lr_stream_t s), ffn_block_t<T>(a, s))

@@ -398,31 +398,9 @@ extern "C" int lr_lora_merge_f32(const float* w, const float* b, const float* a,
 }
 
 // ---- C ABI: fp16 and bf16 forms, unmasked and masked ------------------------------------------------------------------------
-#define LORA_ABI(SUF, TY)                                                                                                                  \
-  extern "C" int lr_lora_down_##SUF(const lr_half* x, int ldx, const lr_half* a, int lda, lr_half* t, int ldt, int M, int K, int R,       \
-                                    float alpha, lr_stream_t s) {                                                                        \
-    return lora_down_t<TY, false>(x, ldx, a, lda, t, ldt, M, K, R, alpha, nullptr, s);                                                    \
-  }                                                                                                                                        \
-  extern "C" int lr_lora_up_##SUF(const lr_half* t, int ldt, const lr_half* u, int ldu, lr_half* y, int ldy, int M, int N, int R,         \
-                                  int accumulate, lr_stream_t s) {                                                                       \
-    return lora_up_t<TY, false>(t, ldt, u, ldu, y, ldy, M, N, R, accumulate, nullptr, s);                                                 \
-  }                                                                                                                                        \
-  extern "C" int lr_lora_wgrad_##SUF(const lr_half* p, int ldp, const lr_half* q, int ldq, float* d, int ldd, int M, int R, int C,        \
-                                     float alpha, void* workspace, int64_t workspace_bytes, lr_stream_t s) {                             \
-    return lora_wgrad_t<TY, false>(p, ldp, q, ldq, d, ldd, M, R, C, alpha, workspace, workspace_bytes, nullptr, s);                       \
-  }                                                                                                                                        \
-  extern "C" int lr_lora_down_drop_##SUF(const lr_half* x, int ldx, const lr_half* a, int lda, lr_half* t, int ldt, int M, int K, int R,  \
-                                         float alpha, const lr_lora_drop* drop, lr_stream_t s) {                                         \
-    return lora_down_t<TY, true>(x, ldx, a, lda, t, ldt, M, K, R, alpha, drop, s);                                                        \
-  }                                                                                                                                        \
-  extern "C" int lr_lora_up_drop_##SUF(const lr_half* t, int ldt, const lr_half* u, int ldu, lr_half* y, int ldy, int M, int N, int R,    \
-                                       int accumulate, const lr_lora_drop* drop, lr_stream_t s) {                                        \
-    return lora_up_t<TY, true>(t, ldt, u, ldu, y, ldy, M, N, R, accumulate, drop, s);                                                     \
-  }                                                                                                                                        \
-  extern "C" int lr_lora_wgrad_drop_##SUF(const lr_half* p, int ldp, const lr_half* q, int ldq, float* d, int ldd, int M, int R, int C,   \
-                                          float alpha, void* workspace, int64_t workspace_bytes, const lr_lora_drop* drop,               \
-                                          lr_stream_t s) {                                                                               \
-    return lora_wgrad_t<TY, true>(p, ldp, q, ldq, d, ldd, M, R, C, alpha, workspace, workspace_bytes, drop, s);                           \
-  }
-LORA_ABI(f16, f16)
-LORA_ABI(bf16, bf16)
+LR_ABI_PAIR(lr_lora_down_f16, lr_lora_down_bf16, (const lr_half* x, int ldx, const lr_half* a, int lda, lr_half* t, int ldt, int M, int K, int R, float alpha, lr_stream_t s), lora_down_t<T, false>(x, ldx, a, lda, t, ldt, M, K, R, alpha, nullptr, s))
+LR_ABI_PAIR(lr_lora_up_f16, lr_lora_up_bf16, (const lr_half* t, int ldt, const lr_half* u, int ldu, lr_half* y, int ldy, int M, int N, int R, int accumulate, lr_stream_t s), lora_up_t<T, false>(t, ldt, u, ldu, y, ldy, M, N, R, accumulate, nullptr, s))
+LR_ABI_PAIR(lr_lora_wgrad_f16, lr_lora_wgrad_bf16, (const lr_half* p, int ldp, const lr_half* q, int ldq, float* d, int ldd, int M, int R, int C, float alpha, void* workspace, int64_t workspace_bytes, lr_stream_t s), lora_wgrad_t<T, false>(p, ldp, q, ldq, d, ldd, M, R, C, alpha, workspace, workspace_bytes, nullptr, s))
+LR_ABI_PAIR(lr_lora_down_drop_f16, lr_lora_down_drop_bf16, (const lr_half* x, int ldx, const lr_half* a, int lda, lr_half* t, int ldt, int M, int K, int R, float alpha, const lr_lora_drop* drop, lr_stream_t s), lora_down_t<T, true>(x, ldx, a, lda, t, ldt, M, K, R, alpha, drop, s))
+LR_ABI_PAIR(lr_lora_up_drop_f16, lr_lora_up_drop_bf16, (const lr_half* t, int ldt, const lr_half* u, int ldu, lr_half* y, int ldy, int M, int N, int R, int accumulate, const lr_lora_drop* drop, lr_stream_t s), lora_up_t<T, true>(t, ldt, u, ldu, y, ldy, M, N, R, accumulate, drop, s))
+LR_ABI_PAIR(lr_lora_wgrad_drop_f16, lr_lora_wgrad_drop_bf16, (const lr_half* p, int ldp, const lr_half* q, int ldq, float* d, int ldd, int M, int R, int C, float alpha, void* workspace, int64_t workspace_bytes, const lr_lora_drop* drop, lr_stream_t s), lora_wgrad_t<T, true>(p, ldp, q, ldq, d, ldd, M, R, C, alpha, workspace, workspace_bytes, drop, s))

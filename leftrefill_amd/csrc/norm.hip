@@ -426,8 +426,7 @@ static int lr_gn_fold_weights_t(const float* gpart, int chunks, int B, int HW, i
                      gamma, beta, eps, (const T*)w, bias, N, (T*)w_out, bias_out);
   return lr_launch_status();
 }
-extern "C" int lr_gn_fold_weights_f16(const float* gpart, int chunks, int B, int HW, int C, const float* gamma, const float* beta, float eps, const lr_half* w, const float* bias, int N, lr_half* w_out, float* bias_out, lr_stream_t s) { return lr_gn_fold_weights_t<f16>(gpart, chunks, B, HW, C, gamma, beta, eps, w, bias, N, w_out, bias_out, s); }
-extern "C" int lr_gn_fold_weights_bf16(const float* gpart, int chunks, int B, int HW, int C, const float* gamma, const float* beta, float eps, const lr_half* w, const float* bias, int N, lr_half* w_out, float* bias_out, lr_stream_t s) { return lr_gn_fold_weights_t<bf16>(gpart, chunks, B, HW, C, gamma, beta, eps, w, bias, N, w_out, bias_out, s); }
+LR_ABI_PAIR(lr_gn_fold_weights_f16, lr_gn_fold_weights_bf16, (const float* gpart, int chunks, int B, int HW, int C, const float* gamma, const float* beta, float eps, const lr_half* w, const float* bias, int N, lr_half* w_out, float* bias_out, lr_stream_t s), lr_gn_fold_weights_t<T>(gpart, chunks, B, HW, C, gamma, beta, eps, w, bias, N, w_out, bias_out, s))
 #endif  // LR_DEV_VARIANTS
 
 template <typename T>
@@ -825,21 +824,13 @@ static int lr_groupnorm_bwd_t(const lr_half* x1, int C1, const lr_half* x2, int 
 }
 
 // ---- C ABI: every entry point in its fp16 and bf16 form -------------------------------------------------------------
-extern "C" int lr_groupnorm_stats(const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, float* partials, lr_stream_t s) { return lr_groupnorm_stats_t<f16>(x1, C1, x2, C2, N, HW, partials, s); }
-extern "C" int lr_groupnorm_stats_bf16(const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, float* partials, lr_stream_t s) { return lr_groupnorm_stats_t<bf16>(x1, C1, x2, C2, N, HW, partials, s); }
-extern "C" int lr_groupnorm_apply(const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, const float* partials, const float* gamma, const float* beta, float eps, int silu, lr_half* y, lr_stream_t s) { return lr_groupnorm_apply_t<f16>(x1, C1, x2, C2, N, HW, partials, gamma, beta, eps, silu, y, s); }
-extern "C" int lr_groupnorm_apply_bf16(const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, const float* partials, const float* gamma, const float* beta, float eps, int silu, lr_half* y, lr_stream_t s) { return lr_groupnorm_apply_t<bf16>(x1, C1, x2, C2, N, HW, partials, gamma, beta, eps, silu, y, s); }
-extern "C" int lr_groupnorm_apply_n(const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, const float* partials, int nchunks, const float* gamma, const float* beta, float eps, int silu, lr_half* y, lr_stream_t s) { return lr_groupnorm_apply_n_t<f16>(x1, C1, x2, C2, N, HW, partials, nchunks, gamma, beta, eps, silu, y, s); }
-extern "C" int lr_groupnorm_apply_n_bf16(const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, const float* partials, int nchunks, const float* gamma, const float* beta, float eps, int silu, lr_half* y, lr_stream_t s) { return lr_groupnorm_apply_n_t<bf16>(x1, C1, x2, C2, N, HW, partials, nchunks, gamma, beta, eps, silu, y, s); }
-extern "C" int lr_layernorm(const lr_half* x, const float* gamma, const float* beta, float eps, lr_half* y, int M, int C, lr_stream_t s) { return lr_layernorm_t<f16>(x, gamma, beta, eps, y, M, C, s); }
-extern "C" int lr_layernorm_bf16(const lr_half* x, const float* gamma, const float* beta, float eps, lr_half* y, int M, int C, lr_stream_t s) { return lr_layernorm_t<bf16>(x, gamma, beta, eps, y, M, C, s); }
-extern "C" int lr_layernorm_bwd(const lr_half* x, const lr_half* dy, const float* gamma, float eps, lr_half* dx, int M, int C, lr_stream_t s) { return lr_layernorm_bwd_t<f16>(x, dy, gamma, eps, dx, M, C, s); }
-extern "C" int lr_layernorm_bwd_bf16(const lr_half* x, const lr_half* dy, const float* gamma, float eps, lr_half* dx, int M, int C, lr_stream_t s) { return lr_layernorm_bwd_t<bf16>(x, dy, gamma, eps, dx, M, C, s); }
-extern "C" int lr_groupnorm_bwd(const lr_half* x1, int C1, const lr_half* x2, int C2, const lr_half* dy, int N, int HW, const float* fwd_partials, const float* gamma, const float* beta, float eps, int silu, float* bwd_partials, lr_half* dx1, lr_half* dx2, lr_stream_t s) { return lr_groupnorm_bwd_t<f16>(x1, C1, x2, C2, dy, N, HW, fwd_partials, gamma, beta, eps, silu, bwd_partials, dx1, dx2, s); }
-extern "C" int lr_groupnorm_bwd_bf16(const lr_half* x1, int C1, const lr_half* x2, int C2, const lr_half* dy, int N, int HW, const float* fwd_partials, const float* gamma, const float* beta, float eps, int silu, float* bwd_partials, lr_half* dx1, lr_half* dx2, lr_stream_t s) { return lr_groupnorm_bwd_t<bf16>(x1, C1, x2, C2, dy, N, HW, fwd_partials, gamma, beta, eps, silu, bwd_partials, dx1, dx2, s); }
+LR_ABI_PAIR(lr_groupnorm_stats, lr_groupnorm_stats_bf16, (const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, float* partials, lr_stream_t s), lr_groupnorm_stats_t<T>(x1, C1, x2, C2, N, HW, partials, s))
+LR_ABI_PAIR(lr_groupnorm_apply, lr_groupnorm_apply_bf16, (const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, const float* partials, const float* gamma, const float* beta, float eps, int silu, lr_half* y, lr_stream_t s), lr_groupnorm_apply_t<T>(x1, C1, x2, C2, N, HW, partials, gamma, beta, eps, silu, y, s))
+LR_ABI_PAIR(lr_groupnorm_apply_n, lr_groupnorm_apply_n_bf16, (const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, const float* partials, int nchunks, const float* gamma, const float* beta, float eps, int silu, lr_half* y, lr_stream_t s), lr_groupnorm_apply_n_t<T>(x1, C1, x2, C2, N, HW, partials, nchunks, gamma, beta, eps, silu, y, s))
+LR_ABI_PAIR(lr_layernorm, lr_layernorm_bf16, (const lr_half* x, const float* gamma, const float* beta, float eps, lr_half* y, int M, int C, lr_stream_t s), lr_layernorm_t<T>(x, gamma, beta, eps, y, M, C, s))
+LR_ABI_PAIR(lr_layernorm_bwd, lr_layernorm_bwd_bf16, (const lr_half* x, const lr_half* dy, const float* gamma, float eps, lr_half* dx, int M, int C, lr_stream_t s), lr_layernorm_bwd_t<T>(x, dy, gamma, eps, dx, M, C, s))
+LR_ABI_PAIR(lr_groupnorm_bwd, lr_groupnorm_bwd_bf16, (const lr_half* x1, int C1, const lr_half* x2, int C2, const lr_half* dy, int N, int HW, const float* fwd_partials, const float* gamma, const float* beta, float eps, int silu, float* bwd_partials, lr_half* dx1, lr_half* dx2, lr_stream_t s), lr_groupnorm_bwd_t<T>(x1, C1, x2, C2, dy, N, HW, fwd_partials, gamma, beta, eps, silu, bwd_partials, dx1, dx2, s))
 // ABI 25: the same backward passes with the residual-branch gradient(s) of the input added before the rounding (dres* may be NULL), and
 // GroupNorm forward partials with their own chunk count (the producer-epilogue [N][fwd_chunks][32][2] sums of lr_gemm_args.gn_group_out)
-extern "C" int lr_layernorm_bwd_res(const lr_half* x, const lr_half* dy, const lr_half* dres, const float* gamma, float eps, lr_half* dx, int M, int C, lr_stream_t s) { return lr_layernorm_bwd_t<f16>(x, dy, gamma, eps, dx, M, C, s, dres); }
-extern "C" int lr_layernorm_bwd_res_bf16(const lr_half* x, const lr_half* dy, const lr_half* dres, const float* gamma, float eps, lr_half* dx, int M, int C, lr_stream_t s) { return lr_layernorm_bwd_t<bf16>(x, dy, gamma, eps, dx, M, C, s, dres); }
-extern "C" int lr_groupnorm_bwd_res(const lr_half* x1, int C1, const lr_half* x2, int C2, const lr_half* dy, const lr_half* dres1, const lr_half* dres2, int N, int HW, const float* fwd_partials, int fwd_chunks, const float* gamma, const float* beta, float eps, int silu, float* bwd_partials, lr_half* dx1, lr_half* dx2, lr_stream_t s) { return lr_groupnorm_bwd_t<f16>(x1, C1, x2, C2, dy, N, HW, fwd_partials, gamma, beta, eps, silu, bwd_partials, dx1, dx2, s, fwd_chunks, dres1, dres2); }
-extern "C" int lr_groupnorm_bwd_res_bf16(const lr_half* x1, int C1, const lr_half* x2, int C2, const lr_half* dy, const lr_half* dres1, const lr_half* dres2, int N, int HW, const float* fwd_partials, int fwd_chunks, const float* gamma, const float* beta, float eps, int silu, float* bwd_partials, lr_half* dx1, lr_half* dx2, lr_stream_t s) { return lr_groupnorm_bwd_t<bf16>(x1, C1, x2, C2, dy, N, HW, fwd_partials, gamma, beta, eps, silu, bwd_partials, dx1, dx2, s, fwd_chunks, dres1, dres2); }
+LR_ABI_PAIR(lr_layernorm_bwd_res, lr_layernorm_bwd_res_bf16, (const lr_half* x, const lr_half* dy, const lr_half* dres, const float* gamma, float eps, lr_half* dx, int M, int C, lr_stream_t s), lr_layernorm_bwd_t<T>(x, dy, gamma, eps, dx, M, C, s, dres))
+LR_ABI_PAIR(lr_groupnorm_bwd_res, lr_groupnorm_bwd_res_bf16, (const lr_half* x1, int C1, const lr_half* x2, int C2, const lr_half* dy, const lr_half* dres1, const lr_half* dres2, int N, int HW, const float* fwd_partials, int fwd_chunks, const float* gamma, const float* beta, float eps, int silu, float* bwd_partials, lr_half* dx1, lr_half* dx2, lr_stream_t s), lr_groupnorm_bwd_t<T>(x1, C1, x2, C2, dy, N, HW, fwd_partials, gamma, beta, eps, silu, bwd_partials, dx1, dx2, s, fwd_chunks, dres1, dres2))

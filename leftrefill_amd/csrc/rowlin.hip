@@ -580,5 +580,4 @@ static int rowlin_t(const lr_rowlin_args* a, lr_stream_t s) {
 #endif
 }
 
-extern "C" int lr_rowlin_f16(const lr_rowlin_args* a, lr_stream_t s) { return rowlin_t<f16>(a, s); }
-extern "C" int lr_rowlin_bf16(const lr_rowlin_args* a, lr_stream_t s) { return rowlin_t<bf16>(a, s); }
+LR_ABI_PAIR(lr_rowlin_f16, lr_rowlin_bf16, (const lr_rowlin_args* a, lr_stream_t s), rowlin_t<T>(a, s))

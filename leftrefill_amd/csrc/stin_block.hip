@@ -285,5 +285,4 @@ static int stin_block_t(const lr_stin_args* a, lr_stream_t s) {
                        (hipStream_t)s, P);
 }
 
-extern "C" int lr_stin_block_f16(const lr_stin_args* a, lr_stream_t s) { return stin_block_t<f16>(a, s); }
-extern "C" int lr_stin_block_bf16(const lr_stin_args* a, lr_stream_t s) { return stin_block_t<bf16>(a, s); }
+LR_ABI_PAIR(lr_stin_block_f16, lr_stin_block_bf16, (const lr_stin_args* a, lr_stream_t s), stin_block_t<T>(a, s))

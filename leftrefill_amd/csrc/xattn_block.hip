@@ -504,7 +504,5 @@ static int xattn_block_t(const lr_xattn_args* a, lr_stream_t s) {
   return lr_launch_dyn(fns[v], &attr_done[v], dim3(P.nblocks), dim3(XA_THREADS), smem, (hipStream_t)s, P);
 }
 
-extern "C" int lr_xattn_block_f16(const lr_xattn_args* a, lr_stream_t s) { return xattn_block_t<f16>(a, s); }
-extern "C" int lr_xattn_block_bf16(const lr_xattn_args* a, lr_stream_t s) { return xattn_block_t<bf16>(a, s); }
-extern "C" int lr_xattn_pack_vt_f16(const lr_half* v, int ldv, lr_half* vt, int B, int heads, int Lc, lr_stream_t s) { return xattn_pack_vt_t<f16>(v, ldv, vt, B, heads, Lc, s); }
-extern "C" int lr_xattn_pack_vt_bf16(const lr_half* v, int ldv, lr_half* vt, int B, int heads, int Lc, lr_stream_t s) { return xattn_pack_vt_t<bf16>(v, ldv, vt, B, heads, Lc, s); }
+LR_ABI_PAIR(lr_xattn_block_f16, lr_xattn_block_bf16, (const lr_xattn_args* a, lr_stream_t s), xattn_block_t<T>(a, s))
+LR_ABI_PAIR(lr_xattn_pack_vt_f16, lr_xattn_pack_vt_bf16, (const lr_half* v, int ldv, lr_half* vt, int B, int heads, int Lc, lr_stream_t s), xattn_pack_vt_t<T>(v, ldv, vt, B, heads, Lc, s))

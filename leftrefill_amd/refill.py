@@ -18,12 +18,12 @@ import math
 
 import numpy as np
 
+from . import _lib
+
 FILTER_SUPPORT = {"bicubic": 2.0, "bilinear": 1.0}
 PRECISION_BITS = 22            # Pillow's Resample.c: 32 - 8 - 2
 MAX_KSIZE = 1025               # LR_PIL_MAX_KSIZE
-JOB_DTYPE = np.dtype([("src_off", "<i8"), ("tmp_off", "<i8"), ("dst_off", "<i8"), ("h_off", "<i8"), ("v_off", "<i8"),
-                      ("hs", "<i4"), ("ws", "<i4"), ("hd", "<i4"), ("wd", "<i4"), ("c", "<i4"), ("h_ksize", "<i4"), ("v_ksize", "<i4"),
-                      ("reserved", "<i4")])      # struct lr_pil_job
+JOB_DTYPE = np.dtype(_lib.PilJob)      # numpy image of struct lr_pil_job
 
 
 def _filter(name, x):

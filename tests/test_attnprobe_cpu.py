@@ -2,7 +2,6 @@
 the C-ABI surface of lr_attention_probe_f16 and the logger's `att_scores` panels."""
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
@@ -98,11 +97,11 @@ def test_read_outs_and_nan_where_the_mass_is_zero():
 
 
 def test_header_binding_and_wrapper_agree():
+    import abi_helpers as abi
     from leftrefill_amd import _lib, build, ops
-    header = open(os.path.join(ROOT, "include", "leftrefill_hip.h")).read()
+    header = abi.header().text
     for name in ("lr_attention_probe_f16", "lr_attention_probe_bf16"):
-        m = re.search(r"^int " + name + r"\(([^;]*)\);", header, flags=re.M)
-        assert m and len(m.group(1).split(",")) == len(_lib.SIGNATURES[name]) == 16, name
+        assert len(abi.c_params(name)) == 16, name       # header against binding: tests/test_abi_cpu.py
     assert "lr_attention_probe_f16" in _lib.BF16_TWINS and _lib.SIGNATURES["lr_attention_probe_bf16"] is _lib.SIGNATURES["lr_attention_probe_f16"]
     sig = _lib.SIGNATURES["lr_attention_probe_f16"]
     assert sig[12:15] == [_lib.c_float] * 3 and sig[7] == _lib.c_void_p and sig[6] == _lib.c_int

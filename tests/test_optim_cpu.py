@@ -4,7 +4,6 @@ import ctypes
 import importlib
 import json
 import os
-import re
 import types
 
 import numpy as np
@@ -27,14 +26,10 @@ def _json(gold, key):
 def test_symbol_declared_bound_and_exported_under_abi_30():
     from leftrefill_amd import _lib, ops
     assert _lib.ABI_VERSION == 30
-    with open(os.path.join(ROOT, "include", "leftrefill_hip.h")) as f:
-        src = f.read()
-    m = re.search(r"int lr_amp_adamw_step\(([^;]*)\);", src)
-    assert m, "lr_amp_adamw_step is not declared in include/leftrefill_hip.h"
-    args = [a.strip() for a in m.group(1).replace("\n", " ").split(",")]
-    sig = _lib.SIGNATURES["lr_amp_adamw_step"]
-    assert len(args) == len(sig) == 12
-    for a, ct in zip(args, sig):
+    import abi_helpers as abi
+    args = abi.c_params("lr_amp_adamw_step")
+    assert len(args) == 12       # header against binding: tests/test_abi_cpu.py; this entry's exact ctypes kinds stay here
+    for a, ct in zip(args, _lib.SIGNATURES["lr_amp_adamw_step"]):
         if "*" in a or a.startswith("lr_stream_t"):
             assert ct in (ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)), a
         else:
@@ -43,11 +38,11 @@ def test_symbol_declared_bound_and_exported_under_abi_30():
     assert hasattr(lib, "lr_amp_adamw_step") and lib.lr_abi_version() == 30
     # the structs and constants the binding restates
     for name, val in (("LR_OPT_MAX_GROUPS", ops.OPT_MAX_GROUPS), ("LR_OPT_MAX_BLOCKS", ops.OPT_MAX_BLOCKS), ("LR_OPT_CONSTS", ops.OPT_CONSTS)):
-        assert int(re.search(rf"#define {name} (\d+)", src).group(1)) == val
+        assert abi.define(name) == val
     assert ops.OPT_STATE_WORDS == ops.OPT_CONSTS + 4 * ops.OPT_MAX_GROUPS
     for i, n in enumerate(ops.OPT_STATE_FIELDS):
         word = {"scale": "SCALE", "sched_steps": "SCHED_STEPS", "applied_steps": "APPLIED_STEPS"}.get(n, n.upper())
-        assert int(re.search(rf"#define LR_OPT_{word} (\d+)", src).group(1)) == i, n
+        assert abi.define(f"LR_OPT_{word}") == i, n
     assert ctypes.sizeof(_lib.OptimTensor) == 48 and ctypes.sizeof(_lib.OptimGroup) == 48
     assert "optim.hip" in importlib.import_module("leftrefill_amd.build").SOURCES
 

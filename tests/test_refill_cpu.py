@@ -1,14 +1,12 @@
 """CPU: the numpy statement of the one-call inpainting route (leftrefill_amd/refill.py) against Pillow itself -- the resampler, the luma
 threshold, the edge pad, `prepare_numpy` against a transcription with PIL calls, the sizes -- and the binding of the two new symbols."""
-import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 from PIL import Image
 
+import abi_helpers as abi
 from leftrefill_amd import refill
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -181,30 +179,10 @@ def test_resize_table_shares_axes_and_places_results():
 
 def test_header_binding_and_source_list_agree_on_the_new_symbols():
     from leftrefill_amd import _lib, build
-    header = open(os.path.join(ROOT, "include", "leftrefill_hip.h")).read()
     for name, count in (("lr_pil_resize", 13), ("lr_refill_canvas", 13)):
-        m = re.search(rf"^int {name}\(([^;]*)\);", header, re.M)
-        assert m and len(m.group(1).split(",")) == len(_lib.SIGNATURES[name]) == count, name
+        assert len(abi.c_params(name)) == count, name
     assert "pil_resample.hip" in build.SOURCES and _lib.ABI_VERSION == 30
     assert "lr_abi_version(void) { return 30; }" in open(os.path.join(ROOT, "leftrefill_amd", "csrc", "elementwise.hip")).read()
-    assert re.search(rf"#define LR_PIL_MAX_KSIZE {refill.MAX_KSIZE}\b", header)
+    assert abi.define("LR_PIL_MAX_KSIZE") == refill.MAX_KSIZE
     from leftrefill_amd import ops
     assert ops.PIL_MAX_KSIZE == refill.MAX_KSIZE
-    fields = re.search(r"typedef struct lr_pil_job \{(.*?)\} lr_pil_job;", header, re.S).group(1)
-    fields = re.sub(r"/\*.*?\*/", "", fields, flags=re.S)
-    names = [n.strip() for decl in fields.split(";") if decl.strip() for n in decl.strip().split(" ", 1)[1].split(",")]
-    assert names == [n for n, *_ in _lib.PilJob._fields_] == list(refill.JOB_DTYPE.names)
-    assert [refill.JOB_DTYPE.fields[n][1] for n in names] == [getattr(_lib.PilJob, n).offset for n in names]
-    assert refill.JOB_DTYPE.itemsize == ctypes.sizeof(_lib.PilJob)
-
-
-def test_pil_job_struct_layout_matches_header(tmp_path):
-    """sizeof / offsets of lr_pil_job as the C compiler lays it out vs the ctypes mirror."""
-    from leftrefill_amd._lib import PilJob
-    names = [n for n, *_ in PilJob._fields_]
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "leftrefill_hip.h"\nint main(){ printf("%zu", sizeof(lr_pil_job));\n' + \
-        "".join(f'printf(" %zu", offsetof(lr_pil_job, {n}));\n' for n in names) + 'printf("\\n"); return 0; }\n'
-    (tmp_path / "t.c").write_text(prog)
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "t.c"), "-o", str(tmp_path / "t")], check=True)
-    out = [int(v) for v in subprocess.run([str(tmp_path / "t")], capture_output=True, text=True, check=True).stdout.split()]
-    assert out == [ctypes.sizeof(PilJob)] + [getattr(PilJob, n).offset for n in names]
