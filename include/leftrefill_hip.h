@@ -920,6 +920,73 @@ int lr_lora_up_drop_bf16(const lr_half* t, int ldt, const lr_half* u, int ldu, l
 int lr_lora_wgrad_drop_bf16(const lr_half* p, int ldp, const lr_half* q, int ldq, float* d, int ldd, int M, int R, int C, float alpha,
                             void* workspace, int64_t workspace_bytes, const lr_lora_drop* drop, lr_stream_t s);
 
+/* ---- FID features and statistics on the device: the pool3 features of pytorch-fid's Inception network and the float64 sums of a set
+ *      (added under ABI 30 like lr_lpips_alex: four new symbols, no struct, nothing renumbered or re-typed; a library without them
+ *      fails to bind; csrc/inception.hip) -----------------------------------------------------------------------------------------------
+ * replaces: the outside program the reference leaves FID to -- its harnesses only write every prediction to disk "for fid metric"
+ *           (test_inpainting.py --save_single, test_multiview_inpainting.py); in this tree leftrefill_amd/fid.py states the network
+ *           (FIDInception), the table (FID_PROGRAM) and the distance, and its float64 form is the yardstick.  Parity-unpinned: neither
+ *           pytorch-fid nor its weights are available to this tree.
+ * lr_fid_input: N source images -> dst fp16 NHWC [N][out][out][4] (8-byte aligned: LR_E_ALIGN), channel 3 zero, one launch.
+ *   kind LR_FID_SRC_U8: src uint8 [N][H][W][3]; kind LR_EVAL_PRED_F32 / _F16 / _BF16: src [N][3][H][W] in [-1, 1], first made 8-bit as
+ *   lr_eval_metrics makes its rgb8: v = mask ? v * m + origin * (1 - m) : v (fp32, not contracted; mask [N][1][H][W], origin
+ *   [N][3][H][W] fp32, both NULL for no composite), b = (uint8_t)((min(max(v, -1), 1) + 1) / 2 * 255).  Columns [x0, x0 + Wc) are the
+ *   image.  From the bytes on in float64 (2 v - 1 cancels around mid-grey, where the stored fp16 is finer than fp32 arithmetic near 1):
+ *   p = b / 255; per axis of n_in cells: f = max(0, (d + 0.5) * ((double)n_in / out) - 0.5), i0 = min((int)f, n_in - 1),
+ *   i1 = min(i0 + 1, n_in - 1), l = f - i0; v = (1 - ly) ((1 - lx) p00 + lx p01) + ly ((1 - lx) p10 + lx p11); stored fp16(2 v - 1).
+ *   F.interpolate(mode='bilinear', align_corners=False) without antialiasing, whether it enlarges or shrinks.
+ * lr_fid_run: an interpreter over `program`, n_rows rows of LR_FID_ROW_WORDS int32 words in HOST memory (words LR_FID_*), for a batch
+ *   of B images.  An activation is a region [B][H][W][ld] of fp16 in `arena`; a row names a region by its offset PER IMAGE in halves
+ *   (multiplied by B here, so one table serves every batch size; a multiple of 8), its channel stride ld and the first channel c0 it
+ *   reads / writes.  LR_FID_OP_CONV: out[.., c0 + o] = fp16(relu(bias[o] + sum_{ky, kx, c} wt[o][(ky kw + kx) Cin + c] in[.., c])),
+ *   fp32 accumulation on the matrix cores; kh x kw in {1x1, 3x3, 5x5, 1x7, 7x1, 1x3, 3x1}, stride 1 | 2, pads ph < kh, pw < kw,
+ *   Cin the STORED channels per tap (a multiple of 8, or 4), wt fp16 [Cout][Kpad] at W_OFF halves (a multiple of 8) of `wt`, Kpad =
+ *   kh kw Cin rounded up to 64 with zero weights, bias fp32 [Cout] at B_OFF floats (a multiple of 4) of `bias`; Cout, c0 and ld of
+ *   the destination multiples of 4.  LR_FID_OP_MAXPOOL_S2: MaxPool(3, 2), floor, no padding; LR_FID_OP_MAXPOOL_S1: MaxPool(3, 1, 1),
+ *   padding never wins; LR_FID_OP_AVGPOOL_S1: AvgPool(3, 1, 1, count_include_pad=False), fp32 sum in (dy, dx) order; C, c0 and ld
+ *   multiples of 8.  Channels of the destination outside [c0, c0 + Cout) keep their bits.  HOUT / WOUT must equal
+ *   (in + 2 pad - k) / stride + 1.  EVERY row is checked before the first launch against arena_halfs, wt_halfs and bias_floats:
+ *   LR_E_ARG for an unknown op, a negative word, a size or range that breaks the rules above, a region, weight or bias range past its
+ *   buffer, B outside 1 .. 32767; arena, wt, bias 16-byte aligned (LR_E_ALIGN).  Then one launch per row, in order, on one stream.
+ * lr_fid_head: src [B][HW][ld] fp16 -> out [B][C] fp32, the mean over the HW pixels added in index order.  One launch.
+ * lr_fid_accumulate: feats fp32 [n][D] (D a multiple of 64) -> sum[D] += sum_r f_r, gram[D][D] += sum_r f_r f_r^T in float64; every
+ *   element is owned by one thread and the rows are added in order, each product exact.  One launch; a second call accumulates.
+ * launches: host counter incremented once per kernel launch, or NULL.  No atomics, no allocation, no synchronisation, nothing read
+ * back: capturable, bitwise reproducible, and an image's features do not depend on the rest of the batch. */
+#define LR_FID_SRC_U8 3          /* kind of lr_fid_input next to LR_EVAL_PRED_* */
+#define LR_FID_OP_CONV 1
+#define LR_FID_OP_MAXPOOL_S2 2
+#define LR_FID_OP_MAXPOOL_S1 3
+#define LR_FID_OP_AVGPOOL_S1 4
+#define LR_FID_ROW_WORDS 24
+#define LR_FID_OP 0
+#define LR_FID_SRC_OFF 1
+#define LR_FID_SRC_LD 2
+#define LR_FID_SRC_C0 3
+#define LR_FID_DST_OFF 4
+#define LR_FID_DST_LD 5
+#define LR_FID_DST_C0 6
+#define LR_FID_HIN 7
+#define LR_FID_WIN 8
+#define LR_FID_CIN 9
+#define LR_FID_HOUT 10
+#define LR_FID_WOUT 11
+#define LR_FID_COUT 12
+#define LR_FID_KH 13
+#define LR_FID_KW 14
+#define LR_FID_STRIDE 15
+#define LR_FID_PH 16
+#define LR_FID_PW 17
+#define LR_FID_W_OFF 18
+#define LR_FID_B_OFF 19
+#define LR_FID_KPAD 20           /* words 21 .. 23: reserved, zero */
+int lr_fid_input(const void* src, int kind, const float* origin, const float* mask, int N, int H, int W, int x0, int Wc, lr_half* dst,
+                 int out, int* launches, lr_stream_t s);
+int lr_fid_run(const int32_t* program, int n_rows, int B, lr_half* arena, int64_t arena_halfs, const lr_half* wt, int64_t wt_halfs,
+               const float* bias, int64_t bias_floats, int* launches, lr_stream_t s);
+int lr_fid_head(const lr_half* src, int B, int HW, int C, int ld, float* out, int* launches, lr_stream_t s);
+int lr_fid_accumulate(const float* feats, int n, int D, double* sum, double* gram, int* launches, lr_stream_t s);
+
 /* ---- bfloat16 twins: same signatures and semantics as the fp16 entry points above, every lr_half is bfloat16 bits -------- */
 int lr_groupnorm_stats_bf16(const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, float* partials,
     lr_stream_t s);

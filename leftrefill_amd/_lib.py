@@ -261,6 +261,12 @@ SIGNATURES = {
                             c_void_p],
     "lr_lora_wgrad_drop_f16": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int64,
                                ctypes.POINTER(LoraDrop), c_void_p],
+    # added under ABI 30 as well: FID features and float64 statistics on the device (csrc/inception.hip); no struct: scalars, pointers
+    # and the int32 program in host memory
+    "lr_fid_input": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, ctypes.POINTER(c_int), c_void_p],
+    "lr_fid_run": [c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, ctypes.POINTER(c_int), c_void_p],
+    "lr_fid_head": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, ctypes.POINTER(c_int), c_void_p],
+    "lr_fid_accumulate": [c_void_p, c_int, c_int, c_void_p, c_void_p, ctypes.POINTER(c_int), c_void_p],
 }
 INT64_RETURNS = ("lr_gemm_workspace_bytes", "lr_lpips_workspace_bytes", "lr_lora_wgrad_workspace_bytes")
 

@@ -1119,6 +1119,74 @@ def lpips_alex(pred, origin, mask, x0, Wc, r, packed, out=None):
     return out
 
 
+# kernel launches of the four lr_fid_* entry points so far, as the library itself counted them (no profiler involved)
+FID_LAUNCHES = ctypes.c_int(0)
+FID_SRC_U8 = 3      # LR_FID_SRC_U8
+
+
+def fid_input(src, dst, out, x0=0, Wc=None, origin=None, mask=None):
+    """lr_fid_input: src uint8 [N,H,W,3], or [N,3,H,W] fp32|fp16|bf16 in [-1, 1] (truncated to 8 bits; with mask [N,1,H,W] and origin
+    [N,3,H,W] after the composite src * mask + origin * (1 - mask)), columns [x0, x0 + Wc) -> dst, fp16 [N, out, out, 4]: / 255,
+    bilinear resize without antialiasing, 2 x - 1, channel 3 zero.  One launch, nothing read back."""
+    lib = _lib.load()
+    assert src.is_cuda and src.dim() == 4, "src: cuda [N,H,W,3] uint8 or [N,3,H,W]"
+    if src.dtype == torch.uint8:
+        assert src.shape[3] == 3 and mask is None and origin is None, "uint8 src: [N,H,W,3], no composite"
+        N, H, W, _ = src.shape
+        kind = FID_SRC_U8
+    else:
+        assert src.shape[1] == 3 and src.dtype in EVAL_PRED_KIND, "src: [N,3,H,W] fp32 / fp16 / bf16"
+        N, _, H, W = src.shape
+        kind = EVAL_PRED_KIND[src.dtype]
+    src = src.contiguous()
+    if mask is not None:
+        assert origin is not None and origin.shape == src.shape and mask.shape == (N, 1, H, W), "origin like src, mask [N,1,H,W]"
+        origin, mask = origin.float().contiguous(), mask.float().contiguous()
+    else:
+        origin = None
+    Wc = W - x0 if Wc is None else Wc
+    assert dst.is_cuda and dst.dtype == torch.float16 and dst.is_contiguous() and dst.numel() == N * out * out * 4, "dst: fp16 [N,out,out,4]"
+    _lib.check(lib.lr_fid_input(_p(src), kind, _p(origin), _p(mask), N, H, W, int(x0), int(Wc), _p(dst), int(out),
+                                ctypes.byref(FID_LAUNCHES), _stream()), "fid_input")
+    return dst
+
+
+def fid_run(program, B, arena, wt, bias):
+    """lr_fid_run: the rows of `program` (int32 numpy [n, 24], words LR_FID_*; leftrefill_amd.fid.FID_PROGRAM is the network) on a batch
+    of B images whose activations live in `arena` (fp16); wt (fp16) / bias (fp32): the packed blobs (fid.pack_fid).  Every row is
+    checked against the three sizes before the first launch (RuntimeError "bad argument", nothing launched); one launch per row."""
+    import numpy as np
+    lib = _lib.load()
+    program = np.ascontiguousarray(program, dtype=np.int32)
+    assert program.ndim == 2 and program.shape[1] == 24, "program: int32 [n, LR_FID_ROW_WORDS]"
+    assert arena.is_cuda and arena.dtype == torch.float16 and arena.is_contiguous(), "arena: contiguous cuda fp16"
+    assert wt is None or (wt.dtype == torch.float16 and wt.device == arena.device and wt.is_contiguous()), "wt: fp16 on the arena's device"
+    assert bias is None or (bias.dtype == torch.float32 and bias.device == arena.device and bias.is_contiguous()), "bias: fp32 on the arena's device"
+    _lib.check(lib.lr_fid_run(program.ctypes.data, program.shape[0], int(B), _p(arena), arena.numel(), _p(wt),
+                              0 if wt is None else wt.numel(), _p(bias), 0 if bias is None else bias.numel(),
+                              ctypes.byref(FID_LAUNCHES), _stream()), "fid_run")
+
+
+def fid_head(src, B, HW, C, ld, out):
+    """lr_fid_head: src fp16 [B, HW, ld] -> out fp32 [B, C], the mean over the pixels in index order.  One launch."""
+    lib = _lib.load()
+    assert src.is_cuda and src.dtype == torch.float16 and src.is_contiguous() and src.numel() >= B * HW * ld, "src: fp16 [B,HW,ld]"
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * C, "out: fp32 [B,C]"
+    _lib.check(lib.lr_fid_head(_p(src), int(B), int(HW), int(C), int(ld), _p(out), ctypes.byref(FID_LAUNCHES), _stream()), "fid_head")
+    return out
+
+
+def fid_accumulate(feats, total, gram):
+    """lr_fid_accumulate: total[D] += sum_r feats[r], gram[D,D] += sum_r feats[r] feats[r]^T in float64, rows added in order by the
+    one thread that owns an element: no atomics, bitwise reproducible.  feats fp32 [n, D], D a multiple of 64.  One launch."""
+    lib = _lib.load()
+    n, D = feats.shape
+    assert feats.is_cuda and feats.dtype == torch.float32 and feats.is_contiguous(), "feats: contiguous cuda fp32 [n,D]"
+    for t, shape in ((total, (D,)), (gram, (D, D))):
+        assert t.dtype == torch.float64 and t.device == feats.device and t.is_contiguous() and tuple(t.shape) == shape, "sums: float64 [D], [D,D]"
+    _lib.check(lib.lr_fid_accumulate(_p(feats), int(n), int(D), _p(total), _p(gram), ctypes.byref(FID_LAUNCHES), _stream()), "fid_accumulate")
+
+
 PIL_MAX_KSIZE = 1025      # LR_PIL_MAX_KSIZE
 
 

@@ -37,6 +37,12 @@ all B x V canvases of a batch in that one launch.
 --device_lpips (with --device_metrics and --lpips_weights): the LPIPS line comes from `evalglue.DeviceLPIPS.score*` -- the HIP AlexNet
 of csrc/lpips.hip on the whole batch, the composite formed inside its first convolution -- and joins the batch's one read-back; the
 torch composite and the per-sample eager module are not run.  Same printed lines and metric file.
+
+--fid_weights FILE (a state dict of pytorch-fid's / torchvision's Inception network; none ships): a final `FID:` line in the printout
+and the metric file -- the Frechet Inception Distance between the composited predictions and the originals, both as the 8-bit images the
+reference writes to disk "for fid metric" (`leftrefill_amd.fid`, parity-unpinned).  --device_fid routes the network and the float64
+statistics through the HIP kernels of csrc/inception.hip (`fid.DeviceFID`); without it `fid.HostFID` runs the eager network in fp32.
+Without --fid_weights nothing changes.
 """
 import argparse
 import glob
@@ -137,7 +143,11 @@ def main():
     ap.add_argument("--device_metrics", action="store_true", help="score on the device: PSNR / SSIM / finite check / PNG bytes from one HIP kernel")
     ap.add_argument("--device_prep", action="store_true", help="assemble the --test_path batches on the device from raw decoded images")
     ap.add_argument("--device_lpips", action="store_true", help="LPIPS from the HIP kernels (needs --device_metrics and --lpips_weights)")
+    ap.add_argument("--fid_weights", type=str, default=None, help="state-dict file of the FID Inception network: adds the FID line")
+    ap.add_argument("--device_fid", action="store_true", help="FID features and statistics from the HIP kernels (needs --fid_weights)")
     a = ap.parse_args()
+    if a.device_fid and not a.fid_weights:
+        raise SystemExit("--device_fid requires --fid_weights")
     if a.device_lpips and not (a.device_metrics and a.lpips_weights):
         raise SystemExit("--device_lpips requires --device_metrics and --lpips_weights")
 
@@ -170,6 +180,18 @@ def main():
     lpips_fn = None
     if a.lpips_weights:
         lpips_fn = (evalglue.DeviceLPIPS if a.device_lpips else evalglue.LPIPSAlex)().load_weights(*[torch.load(f, map_location="cpu") for f in a.lpips_weights.split(",")]).cuda()
+    fid_fn = None
+    if a.fid_weights:
+        from leftrefill_amd import fid
+        fid_fn = (fid.DeviceFID if a.device_fid else fid.HostFID)().load_weights(torch.load(a.fid_weights, map_location="cpu")).cuda()
+
+    def fid_update(out, mask, view_num):      # one more pass over what the batch's metrics scored; nothing is read back here
+        with torch.autocast("cuda", enabled=False):
+            if a.multiview:
+                fid_fn.update_multiview(out, mask, a.batch_size, view_num)
+            else:
+                fid_fn.update(out, mask)
+
     psnrs, ssims, lpipss = [], [], []
     with torch.no_grad(), torch.autocast("cuda"):
         for bi, batch in enumerate(batches):
@@ -182,6 +204,8 @@ def main():
                                                                            a.metric_size, want_rgb8=True)
                 else:
                     m = evalglue.device_metrics(out, batch["mask"], test_size=a.test_size, metric_size=a.metric_size, want_rgb8=True)
+                if fid_fn is not None:
+                    fid_update(out, batch["mask"], global_view_num)
                 rows = [m["psnr"], m["ssim"], m["nonfinite"]]
                 if a.device_lpips:      # one more kernel call on the same tensors, one more row of the same read-back
                     if a.multiview:
@@ -219,6 +243,8 @@ def main():
                                                                                       a.test_size, a.metric_size)
             else:
                 pred, origin = evalglue.compose_prediction(out, batch["mask"], a.test_size, a.metric_size)
+            if fid_fn is not None:
+                fid_update(out, batch["mask"], global_view_num)
             psnrs.extend(evalglue.psnr01(pred, origin).tolist())
             if lpips_fn is not None:
                 with torch.autocast("cuda", enabled=False):
@@ -237,9 +263,11 @@ def main():
     print(f"SSIM: {float(np.mean(ssims)):.4f}")
     lp = f"{float(np.mean(lpipss)):.4f}" if lpipss else "not computed (no --lpips_weights)"
     print(f"LPIPS: {lp}")
+    fid_line = f"FID: {fid_fn.compute():.4f}\n" if fid_fn is not None else ""
+    print(fid_line, end="")
     os.makedirs(a.metric_output, exist_ok=True)
     with open(os.path.join(a.metric_output, os.path.basename(os.path.normpath(a.model_path)) + ".txt"), "w") as f:
-        f.write(f"PSNR: {float(np.mean(psnrs)):.4f}\nSSIM: {float(np.mean(ssims)):.4f}\nLPIPS: {lp}\n")
+        f.write(f"PSNR: {float(np.mean(psnrs)):.4f}\nSSIM: {float(np.mean(ssims)):.4f}\nLPIPS: {lp}\n" + fid_line)
 
 
 if __name__ == "__main__":
