@@ -987,6 +987,23 @@ int lr_fid_run(const int32_t* program, int n_rows, int B, lr_half* arena, int64_
 int lr_fid_head(const lr_half* src, int B, int HW, int C, int ld, float* out, int* launches, lr_stream_t s);
 int lr_fid_accumulate(const float* feats, int n, int D, double* sum, double* gram, int* launches, lr_stream_t s);
 
+/* ---- seeded sampling noise: per-sample Philox normals (added under ABI 30 like lr_eval_metrics: one new symbol, nothing renumbered or
+ *      re-typed; a library without it fails to bind; csrc/seeded_noise.hip) -------------------------------------------------------------
+ * replaces: the `torch.randn` / `randn_like` / `noise_like` draws of the samplers when the caller passes `seeds=` -- the start code
+ *           (ddim.py:235, 489; ddpm.py:1013, 1066), the noise of every step (ddim.py:378, 642; ddpm.py:986), the q_sample noise of the
+ *           known region in the masked loops (ddpm.py:368 under ddim.py:259, 517 and ddpm.py:1046, 1094), stochastic_encode (ddim.py:447) and the
+ *           VAE posterior sample (distributions.py:36-39); leftrefill_amd/noise.py states it (normal_numpy, float64) and is the yardstick.
+ * keys [B][2]: the uint64 seed bits and the sub-sample number (low 32 bits used) of every sample, in DEVICE memory.  stream, step: the
+ * uint32 names of the draw, passed as their int32 bits.  out [B][per_sample] fp32, 4-byte aligned (LR_E_ALIGN).  Element i of sample b,
+ * g = i >> 2:
+ *   w0..w3 = philox4x32_10(counter = (g, sub_b, step, stream), key = (seed_b & 0xffffffff, seed_b >> 32))
+ *   u(w) = ((w >> 9) + 0.5) 2^-23 (exact in fp32);  pair p in {0, 1}: r = sqrtf(-2 logf(u(w[2p]))), (z[4g + 2p + 1], z[4g + 2p]) =
+ *   r * sincospif(2 u(w[2p+1])) -- the accurate forms, the argument of sincospif exact.
+ * One launch.  A value depends on (key, stream, step, i) alone: not on B, the row's place in the batch, per_sample, the alignment of
+ * `out` (16-byte stores where out + b per_sample is 16-byte aligned, scalar stores for a row's tail and for unaligned rows) or anything
+ * run before.  LR_E_ARG, before any launch: a null pointer, B <= 0, per_sample <= 0, per_sample / 4 >= 2^32. */
+int lr_seeded_normal(const int64_t* keys, int B, int64_t per_sample, int32_t stream, int32_t step, float* out, lr_stream_t s);
+
 /* ---- bfloat16 twins: same signatures and semantics as the fp16 entry points above, every lr_half is bfloat16 bits -------- */
 int lr_groupnorm_stats_bf16(const lr_half* x1, int C1, const lr_half* x2, int C2, int N, int HW, float* partials,
     lr_stream_t s);

@@ -267,6 +267,9 @@ SIGNATURES = {
     "lr_fid_run": [c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, ctypes.POINTER(c_int), c_void_p],
     "lr_fid_head": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, ctypes.POINTER(c_int), c_void_p],
     "lr_fid_accumulate": [c_void_p, c_int, c_int, c_void_p, c_void_p, ctypes.POINTER(c_int), c_void_p],
+    # added under ABI 30 as well: seeded sampling noise (csrc/seeded_noise.hip); fp32 only, no bf16 twin.  A library built before it
+    # fails the getattr in load() like every other additive entry: rebuild
+    "lr_seeded_normal": [c_void_p, c_int, c_int64, ctypes.c_int32, ctypes.c_int32, c_void_p, c_void_p],
 }
 INT64_RETURNS = ("lr_gemm_workspace_bytes", "lr_lpips_workspace_bytes", "lr_lora_wgrad_workspace_bytes")
 

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libleftrefill_hip.so")
-SOURCES = ["norm.hip", "elementwise.hip", "gemm_conv.hip", "conv_halo.hip", "attention.hip", "attention_probe.hip", "attention_bwd.hip", "xattn_block.hip", "xattn_block640.hip", "stin_block.hip", "rowlin.hip", "ffn_block.hip", "conv_out.hip", "eval_metrics.hip", "optim.hip", "lpips.hip", "batch_prep.hip", "nvs_prep.hip", "pil_resample.hip", "image_grid.hip", "lora.hip", "inception.hip"]
+SOURCES = ["norm.hip", "elementwise.hip", "gemm_conv.hip", "conv_halo.hip", "attention.hip", "attention_probe.hip", "attention_bwd.hip", "xattn_block.hip", "xattn_block640.hip", "stin_block.hip", "rowlin.hip", "ffn_block.hip", "conv_out.hip", "eval_metrics.hip", "optim.hip", "lpips.hip", "batch_prep.hip", "nvs_prep.hip", "pil_resample.hip", "image_grid.hip", "lora.hip", "inception.hip", "seeded_noise.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 # attention: keep MFMA accumulators in VGPRs -- the softmax VALU stream reads every S^T value and rescales O, and
 # AGPR accumulators cost ~150 v_accvgpr_read/write per 64-key tile.

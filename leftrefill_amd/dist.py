@@ -45,14 +45,21 @@ def all_gather_cat(x, total=None):
     return torch.cat([o[:n] for o, n in zip(outs, sizes)], dim=0)
 
 
-def sample_sharded(sample_fn, cond, uncond, x_T, batch_size):
-    """Run `sample_fn(cond_shard, uncond_shard, x_T_shard, local_batch)` on this rank's slice and gather all latents."""
+def sample_sharded(sample_fn, cond, uncond, x_T, batch_size, seeds=None):
+    """Run `sample_fn(cond_shard, uncond_shard, x_T_shard, local_batch)` on this rank's slice and gather all latents.
+    seeds: None, or the samplers' `seeds=` argument for the whole batch (B ints, a [B] / [B, 2] tensor, a noise.SeededNoise): its rows
+    are sharded with the batch and handed to `sample_fn` as a fifth argument -- every sample keeps its own key, so with seeded noise a
+    sharded run at eta > 0 is the single-process run.  Four-argument callers (seeds=None) are called as before."""
+    from .noise import shard_seeds
+    extra = () if seeds is None else (seeds,)
     if not (dist.is_available() and dist.is_initialized()):
-        return sample_fn(cond, uncond, x_T, batch_size)
+        return sample_fn(cond, uncond, x_T, batch_size, *extra)
     rank, world = dist.get_rank(), dist.get_world_size()
     s, e = shard_range(batch_size, rank, world)
+    if seeds is not None:
+        extra = (shard_seeds(seeds, s, e),)
     out = sample_fn(shard_tree(cond, rank, world, batch_size), shard_tree(uncond, rank, world, batch_size),
-                    None if x_T is None else x_T[s:e], e - s)
+                    None if x_T is None else x_T[s:e], e - s, *extra)
     return all_gather_cat(out)
 
 

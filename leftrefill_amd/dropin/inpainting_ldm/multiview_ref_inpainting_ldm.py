@@ -59,21 +59,24 @@ class RefInpaintLDM(_SingleViewLDM):
         loss_dict[f'{prefix}/loss'] = loss
         return loss, loss_dict
 
-    def get_input(self, batch, k, cond_key=None, bs=None, return_first_stage_outputs=False, force_c_encode=True):
+    def get_input(self, batch, k, cond_key=None, bs=None, return_first_stage_outputs=False, force_c_encode=True, seeds=None):
         if batch['image'].dim() == 5:            # [b, v, h, w, c] -> (b v) canvases, in place like the reference (100-104)
             for key in ('image', 'masked_image', 'mask'):
                 t = batch[key]
                 batch[key] = t.reshape(t.shape[0] * t.shape[1], *t.shape[2:])
         return super().get_input(batch, k, cond_key=cond_key, bs=bs,
-                                 return_first_stage_outputs=return_first_stage_outputs, force_c_encode=force_c_encode)
+                                 return_first_stage_outputs=return_first_stage_outputs, force_c_encode=force_c_encode, seeds=seeds)
 
     @torch.no_grad()
-    def log_images(self, batch, N=4, ddim_steps=50, ddim_eta=0.0, unconditional_guidance_scale=9.0, **kwargs):
+    def log_images(self, batch, N=4, ddim_steps=50, ddim_eta=0.0, unconditional_guidance_scale=9.0, seeds=None, **kwargs):
+        """seeds: None, or one key per CANVAS, (b v) of them in the batch's order (the samplers' `seeds=`): the posterior sample of
+        the masked-image encoding and every draw of the sampler are then that canvas's own seeded draws."""
         img = batch['image']
+        sd = {} if seeds is None else {"seeds": seeds}
         N = img.shape[0] * img.shape[1] if img.dim() == 5 else img.shape[0]      # every canvas of every sample (114-117)
         v = self.view_num - 1 if self.concat_target else self.view_num
         use_ddim = ddim_steps is not None
-        z, c = self.get_input(batch, self.first_stage_key, bs=N)
+        z, c = self.get_input(batch, self.first_stage_key, bs=N, **sd)
         c_concat, c_crossattn = c["c_concat"][0][:N], c["c_crossattn"][0][:N]
         N = min(z.shape[0], N)
         if unconditional_guidance_scale > 1.0:
@@ -81,14 +84,14 @@ class RefInpaintLDM(_SingleViewLDM):
             samples, _ = self.sample_log(cond={"c_concat": [c_concat], "c_crossattn": [c_crossattn]}, batch_size=N,
                                          ddim=use_ddim, ddim_steps=ddim_steps, eta=ddim_eta,
                                          unconditional_guidance_scale=unconditional_guidance_scale,
-                                         unconditional_conditioning=uc_full)
+                                         unconditional_conditioning=uc_full, **sd)
         elif unconditional_guidance_scale == 0.0:
             uc_cross = self.get_unconditional_conditioning(N)
             samples, _ = self.sample_log(cond={"c_concat": [c_concat], "c_crossattn": [uc_cross]}, batch_size=N,
-                                         ddim=use_ddim, ddim_steps=ddim_steps, eta=ddim_eta)
+                                         ddim=use_ddim, ddim_steps=ddim_steps, eta=ddim_eta, **sd)
         else:
             samples, _ = self.sample_log(cond={"c_concat": [c_concat], "c_crossattn": [c_crossattn]}, batch_size=N,
-                                         ddim=use_ddim, ddim_steps=ddim_steps, eta=ddim_eta)
+                                         ddim=use_ddim, ddim_steps=ddim_steps, eta=ddim_eta, **sd)
         pred = self.decode_first_stage(samples)
 
         def by_view(t):      # '(b v) c h w -> b v c h w'

@@ -64,20 +64,25 @@ class RefInpaintLDM(LatentInpaintDiffusion):
 
     @torch.no_grad()
     def log_images(self, batch, N=4, ddim_steps=50, ddim_eta=0.0, unconditional_guidance_scale=9.0, sampler="ddim", return_attn=False,
-                   **kwargs):
+                   seeds=None, **kwargs):
         """sampler: "ddim" (the reference's), "plms" or "dpm_solver"; ddim_steps is the step count of any of them.  "ddpm": the
         ancestral sampler over the full schedule (ddim_steps is ignored), which has no guidance -- unconditional_guidance_scale must
         be 1 (or 0: the empty-prompt condition).  return_attn (the reference's keyword, passed from the config's `return_attn`; DDIM
-        only): adds log["att_scores"], the sampler's per-layer reference-attention maps (DDIMSampler.ddim_sampling)."""
+        only): adds log["att_scores"], the sampler's per-layer reference-attention maps (DDIMSampler.ddim_sampling).
+        seeds: None, or one key per sample of the batch (the samplers' `seeds=`): the posterior sample of the masked-image encoding and
+        every draw of the sampler are then that sample's own seeded draws (leftrefill_amd/noise.py)."""
         if return_attn and sampler != "ddim":
             raise NotImplementedError(f"log_images: return_attn is served by the DDIM sampler, not {sampler!r} (wrap the call in a "
                                       "leftrefill_amd.attnprobe.AttentionProbe instead)")
         attn = {"return_attn": True} if return_attn else {}
+        if seeds is not None:
+            from leftrefill_amd.noise import shard_seeds
+            attn["seeds"] = shard_seeds(seeds, 0, min(N, batch[self.first_stage_key].shape[0]))
         if sampler == "ddpm" and unconditional_guidance_scale not in (0.0, 1.0):
             _ddpm_has_no_guidance(unconditional_guidance_scale)
         use_ddim = ddim_steps is not None
         log = dict()
-        z, c = self.get_input(batch, self.first_stage_key, bs=N)
+        z, c = self.get_input(batch, self.first_stage_key, bs=N, **({} if seeds is None else {"seeds": attn["seeds"]}))
         c_concat, c_crossattn = c["c_concat"][0][:N], c["c_crossattn"][0][:N]
         N = min(z.shape[0], N)
         log["masked_image"] = batch['masked_image'].permute(0, 3, 1, 2)

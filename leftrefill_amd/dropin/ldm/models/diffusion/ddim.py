@@ -22,6 +22,7 @@ import torch
 
 from leftrefill_amd import ops
 from ldm.modules.diffusionmodules.util import make_ddim_sampling_parameters, make_ddim_timesteps, noise_like
+from leftrefill_amd import noise as lrn
 
 
 def _unsupported(who, what):
@@ -180,8 +181,12 @@ class DDIMSampler(CFGModelEval):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
-               unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None, return_attn=False, **kwargs):
-        """return_attn: also return `att_scores` (reference ddim.py:139-141), see `ddim_sampling`."""
+               unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None, return_attn=False, seeds=None, **kwargs):
+        """return_attn: also return `att_scores` (reference ddim.py:139-141), see `ddim_sampling`.
+        seeds: None (every draw comes from torch's global generator, as in the reference), or one key per sample -- B ints, an integer
+        tensor [B] or [B, 2] of (seed, sub) rows, or a leftrefill_amd.noise.SeededNoise: the start code (x_T None), the noise of every
+        step and the q_sample noise of the masked loop are then that sample's own seeded draws (streams START, STEP, KNOWN of
+        leftrefill_amd/noise.py at step = the loop counter), the same whatever else is in the batch, and no generator is touched."""
         self._warn_conditioning_count(conditioning, batch_size, dict_only=True)
         if quantize_x0 or score_corrector is not None or dynamic_threshold is not None or noise_dropout > 0.:
             raise NotImplementedError("quantize_x0 / score_corrector / dynamic_threshold / noise_dropout are unused")
@@ -190,6 +195,8 @@ class DDIMSampler(CFGModelEval):
         if isinstance(conditioning, list) and return_attn:
             _unsupported("DDIMSampler", "return_attn with list conditioning (ddim_multi_sampling)")
         if isinstance(conditioning, list):       # NVS consistency sampler (ddim.py:103-120)
+            if seeds is not None:
+                _unsupported("DDIMSampler", "seeds with list conditioning (ddim_multi_sampling)")
             return self.ddim_multi_sampling(conditioning, (batch_size, C, H, W), callback=callback, temperature=temperature,
                                             x_T=x_T, unconditional_guidance_scale=unconditional_guidance_scale,
                                             unconditional_conditioning=unconditional_conditioning,
@@ -198,13 +205,14 @@ class DDIMSampler(CFGModelEval):
                                   mask=mask, x0=x0, temperature=temperature, x_T=x_T, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, ucg_schedule=ucg_schedule,
-                                  return_attn=return_attn)
+                                  return_attn=return_attn, seeds=seeds)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, callback=None, timesteps=None, mask=None, x0=None,
                       img_callback=None, log_every_t=100, temperature=1., unconditional_guidance_scale=1.,
-                      unconditional_conditioning=None, ucg_schedule=None, return_attn=False, **kwargs):
-        """return_attn: returns (samples, intermediates, att_scores) as the reference does (ddim.py:298-300).  att_scores: a list over
+                      unconditional_conditioning=None, ucg_schedule=None, return_attn=False, seeds=None, **kwargs):
+        """seeds: as in `sample`.
+        return_attn: returns (samples, intermediates, att_scores) as the reference does (ddim.py:298-300).  att_scores: a list over
         the UNet's self-attention layers (execution order) of fp32 [b, h_l, w_l] device tensors -- the step mean of the head-averaged
         attention mass every query puts on the reference (left) half of the canvas, recorded by a leftrefill_amd.attnprobe.AttentionProbe
         around the loop (the UNet then runs its eager route) and, under guidance, folded like the reference's scores:
@@ -218,7 +226,7 @@ class DDIMSampler(CFGModelEval):
             probe = AttentionProbe(self._unet())
         with probe:
             img, intermediates = self._ddim_loop(cond, shape, x_T, callback, timesteps, mask, x0, img_callback, log_every_t, temperature,
-                                                 unconditional_guidance_scale, unconditional_conditioning, ucg_schedule)
+                                                 unconditional_guidance_scale, unconditional_conditioning, ucg_schedule, seeds)
         if return_attn:
             return img, intermediates, self._att_scores(probe, shape[0], unconditional_guidance_scale, unconditional_conditioning)
         return img, intermediates
@@ -236,11 +244,30 @@ class DDIMSampler(CFGModelEval):
             maps.append(fold_cfg(m[:b], m[b:], float(scale)) if guided else m)
         return maps
 
+    @staticmethod
+    def _start_code(sn, shape, device):
+        """x_T when the caller gives none: torch.randn, or the START draw of every sample's key."""
+        return torch.randn(shape, device=device) if sn is None else sn.normal(lrn.START, 0, shape[1:])
+
+    @staticmethod
+    def _known_noise(sn, i, x0):
+        """The q_sample noise of the known region at loop counter i: None (q_sample draws randn_like) or the KNOWN draw."""
+        return None if sn is None else sn.normal(lrn.KNOWN, i, x0.shape[1:])
+
+    @staticmethod
+    def _step_noise(shape, device, repeat_noise, seeds, step):
+        """The noise of one step: noise_like, or the STEP draw at loop counter `step` (row 0's key for every row under repeat_noise)."""
+        if seeds is None:
+            return noise_like(shape, device, repeat_noise)
+        sn = lrn.as_seeded(seeds, shape[0], device)
+        return (sn.row0() if repeat_noise else sn).normal(lrn.STEP, 0 if step is None else step, shape[1:])
+
     def _ddim_loop(self, cond, shape, x_T, callback, timesteps, mask, x0, img_callback, log_every_t, temperature,
-                   unconditional_guidance_scale, unconditional_conditioning, ucg_schedule):
+                   unconditional_guidance_scale, unconditional_conditioning, ucg_schedule, seeds=None):
         device = self.model.betas.device
         b = shape[0]
-        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
+        sn = lrn.as_seeded(seeds, b, device)
+        img = self._start_code(sn, shape, device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
         steps = self.ddim_timesteps
         if timesteps is not None:
             end = int(min(timesteps / steps.shape[0], 1) * steps.shape[0]) - 1
@@ -255,13 +282,14 @@ class DDIMSampler(CFGModelEval):
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
             if mask is not None:
                 assert x0 is not None
-                img = self.model.q_sample(x0, ts) * mask + (1. - mask) * img
+                img = self.model.q_sample(x0, ts, noise=self._known_noise(sn, i, x0)) * mask + (1. - mask) * img
             if ucg_schedule is not None:
                 unconditional_guidance_scale = ucg_schedule[i]
             # t_host: the timestep of `ts` as a host integer -- p_sample_ddim names it to the UNet around its own model calls
             img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, temperature=temperature,
                                               unconditional_guidance_scale=unconditional_guidance_scale,
-                                              unconditional_conditioning=unconditional_conditioning, t_host=int(step))
+                                              unconditional_conditioning=unconditional_conditioning, t_host=int(step),
+                                              seeds=sn, step=i)
             if callback:
                 callback(i)
             if img_callback:
@@ -321,17 +349,18 @@ class DDIMSampler(CFGModelEval):
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, dynamic_threshold=None,
-                      t_host=None, **kwargs):
+                      t_host=None, seeds=None, step=None, **kwargs):
         """t_host: the timestep every entry of `t` holds, as a host integer (the sampling loops pass it; None = unknown).  It is named
-        to the UNet only around this method's own apply_model calls (precomputed embedding rows, UNetModel.prepare_timesteps)."""
+        to the UNet only around this method's own apply_model calls (precomputed embedding rows, UNetModel.prepare_timesteps).
+        seeds, step: the samples' keys (as in `sample`) and the loop counter that names this step's seeded noise; None = noise_like."""
         with self._step_hint(t_host):
             return self._p_sample_ddim(x, c, t, index, repeat_noise, use_original_steps, quantize_denoised, temperature, noise_dropout,
                                        score_corrector, corrector_kwargs, unconditional_guidance_scale, unconditional_conditioning,
-                                       dynamic_threshold)
+                                       dynamic_threshold, seeds, step)
 
     def _p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                        temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
-                       unconditional_guidance_scale=1., unconditional_conditioning=None, dynamic_threshold=None):
+                       unconditional_guidance_scale=1., unconditional_conditioning=None, dynamic_threshold=None, seeds=None, step=None):
         if use_original_steps or quantize_denoised or score_corrector is not None or dynamic_threshold is not None:
             raise NotImplementedError
         if self.model.parameterization != "eps":
@@ -345,7 +374,7 @@ class DDIMSampler(CFGModelEval):
                 # cond / uncond passes on two ranks (or, without a process group, one after the other): batch B each, one
                 # all-gather of the eps halves per step -- leftrefill_amd/dist.py.  (The [uncond; cond] batch is not built here.)
                 # The ranks of a pair must hold the same x and draw the same DDIM noise: the caller seeds them identically
-                # (bench.py: seed 1234 + rank // 2).
+                # (bench.py: seed 1234 + rank // 2), or passes both the same `seeds`.
                 role = lrd.split_cfg_role()
                 if role is None:
                     # one process runs both passes: each gets its own captured step (graph slot), so the per-context K / V cache
@@ -363,13 +392,13 @@ class DDIMSampler(CFGModelEval):
                     eps = torch.cat(halves)
                 else:
                     eps = lrd.cfg_exchange(self.model.apply_model(x, t, unconditional_conditioning if role == 0 else c))
-                noise = noise_like(x.shape, device, repeat_noise)
+                noise = self._step_noise(x.shape, device, repeat_noise, seeds, step)
                 sigma = float(self.ddim_sigmas[index])
                 return ops.ddim_cfg_step(x, eps.contiguous(), noise, scale, self.ddim_alphas[index], self.ddim_alphas_prev[index],
                                          sigma * float(temperature), self.ddim_sqrt_one_minus_alphas[index])
         eps, scale = self._cfg_eps(x, c, t, unconditional_conditioning, scale)
         # randn is drawn every step like the reference (ddim.py:378), also when sigma_t == 0
-        noise = noise_like(x.shape, device, repeat_noise)
+        noise = self._step_noise(x.shape, device, repeat_noise, seeds, step)
         sigma = float(self.ddim_sigmas[index])
         x_prev, pred_x0 = ops.ddim_cfg_step(x, eps, noise, scale, self.ddim_alphas[index], self.ddim_alphas_prev[index],
                                             sigma * float(temperature), self.ddim_sqrt_one_minus_alphas[index])
@@ -454,13 +483,16 @@ class DDIMSampler(CFGModelEval):
         return sa, s1ma
 
     @torch.no_grad()
-    def stochastic_encode(self, x0, t, use_original_steps=False, noise=None):
+    def stochastic_encode(self, x0, t, use_original_steps=False, noise=None, seeds=None):
         """Re-noise a clean latent to DDIM step t[b] of each sample (ddim.py:436-449): sqrt(a_t) x0 + sqrt(1 - a_t) noise, one
-        lr_ddim_q_sample launch.  noise=None draws randn_like(x0) like the reference."""
+        lr_ddim_q_sample launch.  noise=None draws randn_like(x0) like the reference, or with `seeds` (as in `sample`) the ENCODE draw
+        of every sample's key."""
         if use_original_steps:
             _unsupported("DDIMSampler.stochastic_encode", "use_original_steps")
         sa, s1ma = self.q_sample_coefficients(t)
         assert sa.shape[0] == x0.shape[0], "one DDIM step index per sample"
+        if noise is None and seeds is not None:
+            noise = lrn.as_seeded(seeds, x0.shape[0], x0.device).normal(lrn.ENCODE, 0, x0.shape[1:])
         if noise is None:
             noise = torch.randn_like(x0)
         return ops.ddim_q_sample(x0.float(), noise.float(), sa, s1ma)
@@ -505,14 +537,14 @@ class StructureDDIMSampler(DDIMSampler):
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
                unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None, Tm=None, cond_simple=None,
-               cond_weight=None, mask_dir='right', **kwargs):
+               cond_weight=None, mask_dir='right', seeds=None, **kwargs):
         if isinstance(conditioning, list):       # the reference routes list conditioning to ddim_multi_sampling (no Tm)
             return super().sample(S, batch_size, shape, conditioning=conditioning, callback=callback, img_callback=img_callback,
                                   quantize_x0=quantize_x0, eta=eta, mask=mask, x0=x0, temperature=temperature,
                                   noise_dropout=noise_dropout, score_corrector=score_corrector, verbose=verbose, x_T=x_T,
                                   log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, dynamic_threshold=dynamic_threshold,
-                                  ucg_schedule=ucg_schedule)
+                                  ucg_schedule=ucg_schedule, seeds=seeds)
         self._warn_conditioning_count(conditioning, batch_size, dict_only=True)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
@@ -523,7 +555,7 @@ class StructureDDIMSampler(DDIMSampler):
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, dynamic_threshold=dynamic_threshold,
                                   ucg_schedule=ucg_schedule, Tm=Tm, cond_simple=cond_simple, cond_weight=cond_weight,
-                                  mask_dir=mask_dir, **kwargs)
+                                  mask_dir=mask_dir, seeds=seeds, **kwargs)
 
     def _check_guide(self, use_original_steps=False, quantize_denoised=False, noise_dropout=0., score_corrector=None,
                      dynamic_threshold=None, return_attn=False):
@@ -539,7 +571,8 @@ class StructureDDIMSampler(DDIMSampler):
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.,
                       noise_dropout=0., score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.,
                       unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None, Tm=None, cond_simple=None,
-                      cond_weight=None, mask_dir='right', **kwargs):
+                      cond_weight=None, mask_dir='right', seeds=None, **kwargs):
+        """seeds: as in DDIMSampler.sample (start code, step noise of both phases, known-region noise)."""
         self._check_guide(ddim_use_original_steps, quantize_denoised, noise_dropout, score_corrector, dynamic_threshold,
                           kwargs.get('return_attn', False))
         if Tm is None or cond_simple is None or cond_weight is None:
@@ -547,7 +580,8 @@ class StructureDDIMSampler(DDIMSampler):
         import copy
         device = self.model.betas.device
         b = shape[0]
-        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
+        sn = lrn.as_seeded(seeds, b, device)
+        img = self._start_code(sn, shape, device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
         steps = self.ddim_timesteps
         if timesteps is not None:
             end = int(min(timesteps / steps.shape[0], 1) * steps.shape[0]) - 1
@@ -568,7 +602,7 @@ class StructureDDIMSampler(DDIMSampler):
                 ts = torch.full((b,), int(step), device=device, dtype=torch.long)
                 if mask is not None:
                     assert x0 is not None
-                    img = self.model.q_sample(x0, ts) * mask + (1. - mask) * img
+                    img = self.model.q_sample(x0, ts, noise=self._known_noise(sn, i, x0)) * mask + (1. - mask) * img
                 if ucg_schedule is not None:
                     assert len(ucg_schedule) == len(time_range)
                     scale = ucg_schedule[i]
@@ -576,11 +610,11 @@ class StructureDDIMSampler(DDIMSampler):
                     img, pred_x0 = self.p_sample_ddim_guide(img, cond, cond_simple, cond_weight, ts, index=index,
                                                             temperature=temperature, unconditional_guidance_scale=scale,
                                                             unconditional_conditioning=unconditional_conditioning,
-                                                            t_host=int(step))
+                                                            t_host=int(step), seeds=sn, step=i)
                 else:
                     img, pred_x0 = self.p_sample_ddim(img, new_cond_simple, ts, index=index, temperature=temperature,
                                                       unconditional_guidance_scale=scale, unconditional_conditioning=new_uc,
-                                                      t_host=int(step))
+                                                      t_host=int(step), seeds=sn, step=i)
                 if callback:
                     callback(i)
                 if img_callback:
@@ -597,9 +631,9 @@ class StructureDDIMSampler(DDIMSampler):
     def p_sample_ddim_guide(self, x, c, c_simple, c_weight, t, index, repeat_noise=False, use_original_steps=False,
                             quantize_denoised=False, temperature=1., noise_dropout=0., score_corrector=None,
                             corrector_kwargs=None, unconditional_guidance_scale=1., unconditional_conditioning=None,
-                            dynamic_threshold=None, t_host=None, **kwargs):
+                            dynamic_threshold=None, t_host=None, seeds=None, step=None, **kwargs):
         """One three-way guided DDIM step (ddim.py:579-647).  Without an unconditional pass (or at scale 1) the model sees c alone
-        (ddim.py:585-586) and the step is lr_ddim_cfg_step's.  t_host: as in p_sample_ddim."""
+        (ddim.py:585-586) and the step is lr_ddim_cfg_step's.  t_host, seeds, step: as in p_sample_ddim."""
         self._check_guide(use_original_steps, quantize_denoised, noise_dropout, score_corrector, dynamic_threshold,
                           kwargs.get('return_attn', False))
         x = x.float().contiguous()
@@ -612,7 +646,7 @@ class StructureDDIMSampler(DDIMSampler):
                 eps = self._cfg3_eps(x, c, c_simple, t, unconditional_conditioning)
             else:
                 eps, _ = self._cfg_eps(x, c, t, None, 1.)
-        noise = noise_like(x.shape, x.device, repeat_noise)      # drawn every step like the reference (ddim.py:643)
+        noise = self._step_noise(x.shape, x.device, repeat_noise, seeds, step)      # drawn every step like the reference (ddim.py:643)
         sigma = float(self.ddim_sigmas[index]) * float(temperature)
         a_t, a_prev, s1 = self.ddim_alphas[index], self.ddim_alphas_prev[index], self.ddim_sqrt_one_minus_alphas[index]
         if not three:

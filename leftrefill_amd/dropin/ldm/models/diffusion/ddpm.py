@@ -12,6 +12,8 @@ On the hot path only `apply_model` -> `DiffusionWrapper.forward` ('hybrid': chan
 [mask | masked-image latent], cross-attention context) -> `UNetModel.forward` is exercised; VAE encode/decode and the
 prompt encoder stay PyTorch-ROCm host code as the north star prescribes.
 """
+import contextlib
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -19,6 +21,7 @@ import torch.nn as nn
 from leftrefill_amd import ops
 from ldm.models.diffusion.ddim import CFGModelEval, DDIMSampler
 from ldm.modules.diffusionmodules.util import extract_into_tensor, make_beta_schedule, noise_like
+from leftrefill_amd import noise as lrn
 from ldm.modules.distributions.distributions import DiagonalGaussianDistribution
 from ldm.util import default, exists, instantiate_from_config
 
@@ -269,9 +272,10 @@ class LatentDiffusion(DDPM):
             self.cond_stage_model = instantiate_from_config(cond_stage_config)
 
     # ---- first stage (KL-VAE; PyTorch-ROCm host code) -----------------------------------------------------------
-    def get_first_stage_encoding(self, encoder_posterior):
+    def get_first_stage_encoding(self, encoder_posterior, noise=None):
+        """noise: a ready standard-normal tensor for the posterior sample (DiagonalGaussianDistribution.sample), or None."""
         if isinstance(encoder_posterior, DiagonalGaussianDistribution):
-            z = encoder_posterior.sample()
+            z = encoder_posterior.sample(noise=noise)
         elif isinstance(encoder_posterior, torch.Tensor):
             z = encoder_posterior
         else:
@@ -388,21 +392,27 @@ class LatentDiffusion(DDPM):
                              0.0 if i == 0 else tab["std"][i], clip_denoised=clip_denoised, return_x0=return_x0, known=known)
 
     def _p_sample(self, ev, x, c, t, t_host, clip_denoised=False, repeat_noise=False, return_x0=False, temperature=1.,
-                  noise_dropout=0., known=None):
+                  noise_dropout=0., known=None, seeded=None):
         """One ancestral step.  t_host: the timestep every entry of `t` holds, as a host integer (the loops), or None (read `t`
         back).  known: None or (x0, mask) -- the blend with q_sample(x0, t) of the masked loops, whose randn_like is drawn AFTER
-        the step's own noise, as in the reference."""
+        the step's own noise, as in the reference.  seeded: None, or (SeededNoise, loop counter): the step's noise and the known
+        region's are then the STEP and KNOWN draws of every sample's key (leftrefill_amd/noise.py) and no generator is touched."""
         x = x.float().contiguous()
         with ev._step_hint(t_host):
             eps = self.apply_model(x, t, c)
-        noise = noise_like(x.shape, x.device, repeat_noise)      # drawn every step like the reference (986), also at t == 0
+        if seeded is None:
+            noise = noise_like(x.shape, x.device, repeat_noise)      # drawn every step like the reference (986), also at t == 0
+        else:
+            sn, k = seeded
+            noise = (sn.row0() if repeat_noise else sn).normal(lrn.STEP, k, x.shape[1:])
         if temperature != 1.:
             noise = noise * temperature
         if noise_dropout > 0.:
             noise = torch.nn.functional.dropout(noise, p=noise_dropout)
         if known is not None:
             x0, mask = known
-            known = (x0.float().contiguous(), torch.randn_like(x0).float(), mask.to(device=x.device, dtype=torch.float32).contiguous())
+            q_noise = torch.randn_like(x0).float() if seeded is None else seeded[0].normal(lrn.KNOWN, seeded[1], x0.shape[1:])
+            known = (x0.float().contiguous(), q_noise, mask.to(device=x.device, dtype=torch.float32).contiguous())
         if t_host is not None:
             return self._posterior_step(x, eps, t_host, noise, clip_denoised, return_x0, known)
         assert known is None
@@ -440,11 +450,14 @@ class LatentDiffusion(DDPM):
     def p_sample(self, x, c, t, clip_denoised=False, repeat_noise=False, return_codebook_ids=False, quantize_denoised=False,
                  return_x0=False, temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None):
         """x_{t-1} ~ p(x_{t-1} | x_t) (reference 969-997): model call + one lr_ddpm_step per run of equal `t` (read back once here;
-        the loops name their timestep on the host instead).  Returns x_prev, or (x_prev, x0) with return_x0."""
+        the loops name their timestep on the host instead).  Returns x_prev, or (x_prev, x0) with return_x0.
+        Inside `with model.seeded_noise(seeds, step=k):` the noise is the STEP draw at loop counter k of every sample's key."""
         self._ddpm_unsupported("LatentDiffusion.p_sample", return_codebook_ids=return_codebook_ids,
                                quantize_denoised=quantize_denoised, score_corrector=score_corrector is not None)
+        seeds, step = self._seeded
+        sn = lrn.as_seeded(seeds, x.shape[0], x.device)
         x_prev, x0 = self._p_sample(self._model_eval(), x, c, t, None, clip_denoised, repeat_noise, return_x0, temperature,
-                                    noise_dropout)
+                                    noise_dropout, seeded=None if sn is None else (sn, int(step)))
         return (x_prev, x0) if return_x0 else x_prev
 
     @staticmethod
@@ -456,8 +469,34 @@ class LatentDiffusion(DDPM):
                     for key in cond}
         return [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
 
-    def _ancestral_chain(self, who, cond, img, timesteps, step_kwargs, mask, x0, quantize_denoised, score_corrector=None):
-        """Generator over the chain timesteps-1 .. 0: yields (i, img, x0_partial) after each step."""
+    # The reference's signatures of the ancestral sampler are kept name for name (p_sample, p_sample_loop and progressive_denoising take
+    # no **kwargs), so the samples' keys reach them through the model: `sample(..., seeds=...)` / `sample_log(ddim=False, seeds=...)`
+    # set them for the call, and a direct call of a loop or of p_sample is wrapped in `with model.seeded_noise(seeds):`.
+    _seeded = (None, 0)
+
+    @contextlib.contextmanager
+    def seeded_noise(self, seeds, step=0):
+        """While active, p_sample_loop / progressive_denoising / p_sample of this model draw from the samples' keys instead of torch's
+        global generator.  seeds: None (the reference's draws), or one key per sample -- B ints, an integer tensor [B] or [B, 2] of
+        (seed, sub) rows, or a leftrefill_amd.noise.SeededNoise.  The loops draw the start code (x_T None), every step's noise and the
+        known region's q_sample noise (streams START, STEP, KNOWN at step = the loop counter); step names the draw of a direct p_sample."""
+        prev = self._seeded
+        self._seeded = (seeds, int(step))
+        try:
+            yield self
+        finally:
+            self._seeded = prev
+
+    def _start_code(self, shape, device, x_T):
+        """(x_T, SeededNoise | None); when the caller gives no x_T it is torch.randn, or the START draw of every sample's key."""
+        sn = lrn.as_seeded(self._seeded[0], shape[0], device)
+        if x_T is None:
+            x_T = torch.randn(shape, device=device) if sn is None else sn.normal(lrn.START, 0, shape[1:])
+        return x_T, sn
+
+    def _ancestral_chain(self, who, cond, img, timesteps, step_kwargs, mask, x0, quantize_denoised, score_corrector=None, sn=None):
+        """Generator over the chain timesteps-1 .. 0: yields (i, img, x0_partial) after each step.  sn: the samples' keys (SeededNoise)
+        or None; the draws of the k-th step executed are named by the loop counter k = timesteps - 1 - i."""
         self._ddpm_unsupported(who, quantize_denoised=quantize_denoised, score_corrector=score_corrector is not None,
                                shorten_cond_schedule=getattr(self, "shorten_cond_schedule", False))
         b = img.shape[0]
@@ -470,14 +509,16 @@ class LatentDiffusion(DDPM):
         ev._prepare_timesteps(range(timesteps))
         for i in reversed(range(0, timesteps)):
             ts = torch.full((b,), i, device=img.device, dtype=torch.long)
-            img, x0_partial = self._p_sample(ev, img, cond, ts, i, known=known, **step_kwargs(i))
+            img, x0_partial = self._p_sample(ev, img, cond, ts, i, known=known, seeded=None if sn is None else (sn, timesteps - 1 - i),
+                                             **step_kwargs(i))
             yield i, img, x0_partial
 
     @torch.no_grad()
     def progressive_denoising(self, cond, shape, verbose=True, callback=None, quantize_denoised=False, img_callback=None,
                               mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                               batch_size=None, x_T=None, start_T=None, log_every_t=None):
-        """The chain with the x0 predictions as intermediates (reference 1000-1053).  Returns (img, intermediates)."""
+        """The chain with the x0 predictions as intermediates (reference 1000-1053).  Returns (img, intermediates).
+        Seeded draws: inside `with model.seeded_noise(seeds):`."""
         if not log_every_t:
             log_every_t = self.log_every_t
         timesteps = self.num_timesteps
@@ -485,7 +526,7 @@ class LatentDiffusion(DDPM):
             shape = [batch_size] + list(shape)
         else:
             batch_size = shape[0]
-        img = torch.randn(shape, device=self.device) if x_T is None else x_T
+        img, sn = self._start_code(shape, self.device, x_T)
         intermediates = []
         cond = self._slice_cond(cond, batch_size)
         if start_T is not None:
@@ -495,7 +536,7 @@ class LatentDiffusion(DDPM):
         kw = lambda i: dict(clip_denoised=self.clip_denoised, return_x0=True, temperature=temperature[i],
                             noise_dropout=noise_dropout)
         for i, img, x0_partial in self._ancestral_chain("LatentDiffusion.progressive_denoising", cond, img, timesteps, kw, mask, x0,
-                                                        quantize_denoised, score_corrector):
+                                                        quantize_denoised, score_corrector, sn=sn):
             if i % log_every_t == 0 or i == timesteps - 1:
                 intermediates.append(x0_partial)
             if callback:
@@ -507,10 +548,11 @@ class LatentDiffusion(DDPM):
     @torch.no_grad()
     def p_sample_loop(self, cond, shape, return_intermediates=False, x_T=None, verbose=True, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, start_T=None, log_every_t=None):
-        """The ancestral chain from x_T over `timesteps` (default: all) steps (reference 1056-1104)."""
+        """The ancestral chain from x_T over `timesteps` (default: all) steps (reference 1056-1104).
+        Seeded draws: `sample(..., seeds=...)`, or inside `with model.seeded_noise(seeds):`."""
         if not log_every_t:
             log_every_t = self.log_every_t
-        img = torch.randn(shape, device=self.betas.device) if x_T is None else x_T
+        img, sn = self._start_code(shape, self.betas.device, x_T)
         intermediates = [img]
         if timesteps is None:
             timesteps = self.num_timesteps
@@ -521,7 +563,7 @@ class LatentDiffusion(DDPM):
             assert x0.shape[2:3] == mask.shape[2:3], "mask and x0 differ in height (the reference's check, 1081)"
         kw = lambda i: dict(clip_denoised=self.clip_denoised)
         for i, img, _ in self._ancestral_chain("LatentDiffusion.p_sample_loop", cond, img, timesteps, kw, mask, x0,
-                                               quantize_denoised):
+                                               quantize_denoised, sn=sn):
             if i % log_every_t == 0 or i == timesteps - 1:
                 intermediates.append(img)
             if callback:
@@ -535,12 +577,13 @@ class LatentDiffusion(DDPM):
     @torch.no_grad()
     def sample(self, cond, batch_size=16, return_intermediates=False, x_T=None, verbose=True, timesteps=None,
                quantize_denoised=False, mask=None, x0=None, shape=None, **kwargs):
-        """reference 1107-1122"""
+        """reference 1107-1122.  seeds= (through **kwargs): one key per sample, see `seeded_noise`; None = the reference's draws."""
         if shape is None:
             shape = (batch_size, self.channels, self.image_size, self.image_size)
         cond = self._slice_cond(cond, batch_size)
-        return self.p_sample_loop(cond, shape, return_intermediates=return_intermediates, x_T=x_T, verbose=verbose,
-                                  timesteps=timesteps, quantize_denoised=quantize_denoised, mask=mask, x0=x0)
+        with self.seeded_noise(kwargs.get("seeds", self._seeded[0])):
+            return self.p_sample_loop(cond, shape, return_intermediates=return_intermediates, x_T=x_T, verbose=verbose,
+                                      timesteps=timesteps, quantize_denoised=quantize_denoised, mask=mask, x0=x0)
 
     @torch.no_grad()
     def sample_log(self, cond, batch_size, ddim, ddim_steps, **kwargs):
@@ -615,7 +658,10 @@ class LatentInpaintDiffusion(LatentFinetuneDiffusion):
         self.masked_image_key = masked_image_key
         assert self.masked_image_key in concat_keys
 
-    def get_input(self, batch, k, cond_key=None, bs=None, return_first_stage_outputs=False, force_c_encode=True):
+    def get_input(self, batch, k, cond_key=None, bs=None, return_first_stage_outputs=False, force_c_encode=True, seeds=None):
+        """seeds: None, or one key per sample (as in DDIMSampler.sample): the posterior sample of the masked-image encoding -- the only
+        posterior sample the sampling reads -- is then the POSTERIOR draw of every sample's key instead of the reference's re-seeded
+        host draw, whose value for a sample depends on the sample's place in the batch."""
         z, c, x, xrec, xc = super().get_input(batch, self.first_stage_key, return_first_stage_outputs=True,
                                               force_c_encode=force_c_encode, return_original_cond=True, bs=bs)
         assert exists(self.concat_keys)
@@ -628,7 +674,10 @@ class LatentInpaintDiffusion(LatentFinetuneDiffusion):
             if ck != self.masked_image_key:
                 cc = torch.nn.functional.interpolate(cc, size=z.shape[-2:])      # mask: nearest to latent size
             else:
-                cc = self.get_first_stage_encoding(self.encode_first_stage(cc))  # VAE(masked image) * scale_factor
+                posterior = self.encode_first_stage(cc)
+                sn = lrn.as_seeded(seeds, cc.shape[0], cc.device) if isinstance(posterior, DiagonalGaussianDistribution) else None
+                noise = None if sn is None else sn.normal(lrn.POSTERIOR, 0, posterior.mean.shape[1:])
+                cc = self.get_first_stage_encoding(posterior, noise=noise)  # VAE(masked image) * scale_factor
             c_cat.append(cc)
         all_conds = {"c_concat": [torch.cat(c_cat, dim=1)], "c_crossattn": [c]}
         if return_first_stage_outputs:

@@ -11,8 +11,9 @@ The reference's fixed configuration (ldm/models/diffusion/dpm_solver/sampler.py)
 """
 import torch
 
+from leftrefill_amd import noise as lrn
 from leftrefill_amd import ops
-from ldm.models.diffusion.ddim import CFGModelEval
+from ldm.models.diffusion.ddim import CFGModelEval, DDIMSampler
 from .dpm_solver import NoiseScheduleVP, multistep_plan
 
 MODEL_TYPES = {"eps": "noise", "v": "v"}
@@ -50,7 +51,9 @@ class DPMSolverSampler(CFGModelEval):
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
                unconditional_conditioning=None, method="multistep", order=2, skip_type="time_uniform",
-               thresholding=False, lower_order_final=True, dynamic_threshold=None, use_original_steps=False, **kwargs):
+               thresholding=False, lower_order_final=True, dynamic_threshold=None, use_original_steps=False, seeds=None, **kwargs):
+        """seeds: None, or one key per sample as in DDIMSampler.sample -- the start code (x_T None) is then the START draw of every
+        sample's key; the solver is deterministic afterwards."""
         if method != "multistep":
             _unsupported(f"method {method!r}")
         if order != 2:
@@ -77,7 +80,10 @@ class DPMSolverSampler(CFGModelEval):
         self._warn_conditioning_count(conditioning, batch_size)
         C, H, W = shape
         device = self.model.betas.device
-        x = torch.randn((batch_size, C, H, W), device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
+        if x_T is None:
+            x = DDIMSampler._start_code(lrn.as_seeded(seeds, batch_size, device), (batch_size, C, H, W), device)
+        else:
+            x = x_T.to(device=device, dtype=torch.float32)
         x = x.contiguous()
         plan = self.schedule(S, lower_order_final=lower_order_final)
         t_model = [float(v) for v in plan["t_model"]]           # exact fp32 values as python floats

@@ -13,6 +13,7 @@ combine + multistep combination + pred_x0 / x_prev), with the schedule on the ho
 import numpy as np
 import torch
 
+from leftrefill_amd import noise as lrn
 from leftrefill_amd import ops
 from ldm.models.diffusion.ddim import CFGModelEval, DDIMSampler
 from ldm.modules.diffusionmodules.util import noise_like
@@ -48,7 +49,9 @@ class PLMSSampler(CFGModelEval):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
-               unconditional_conditioning=None, dynamic_threshold=None, **kwargs):
+               unconditional_conditioning=None, dynamic_threshold=None, seeds=None, **kwargs):
+        """seeds: None, or one key per sample as in DDIMSampler.sample -- the start code (x_T None) is then the START draw of every
+        sample's key.  PLMS is deterministic afterwards; its discarded draws stay discarded (noise_like, the global generator)."""
         if isinstance(conditioning, list):
             _unsupported("list conditioning (the multi-conditioning NVS sampler)")
         self._warn_conditioning_count(conditioning, batch_size)
@@ -59,7 +62,8 @@ class PLMSSampler(CFGModelEval):
                                   noise_dropout=noise_dropout, temperature=temperature, score_corrector=score_corrector,
                                   corrector_kwargs=corrector_kwargs, x_T=x_T, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning, dynamic_threshold=dynamic_threshold)
+                                  unconditional_conditioning=unconditional_conditioning, dynamic_threshold=dynamic_threshold,
+                                  seeds=seeds)
 
     def _check(self, use_original_steps=False, quantize_denoised=False, noise_dropout=0., score_corrector=None,
                dynamic_threshold=None, unconditional_conditioning=None, scale=1.):
@@ -82,14 +86,17 @@ class PLMSSampler(CFGModelEval):
     def plms_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.,
                       noise_dropout=0., score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.,
-                      unconditional_conditioning=None, dynamic_threshold=None):
+                      unconditional_conditioning=None, dynamic_threshold=None, seeds=None):
         self._check(ddim_use_original_steps, quantize_denoised, noise_dropout, score_corrector, dynamic_threshold,
                     unconditional_conditioning, unconditional_guidance_scale)
         if isinstance(cond, list):
             _unsupported("list conditioning (the multi-conditioning NVS sampler)")
         device = self.model.betas.device
         b = shape[0]
-        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
+        if x_T is None:
+            img = DDIMSampler._start_code(lrn.as_seeded(seeds, b, device), shape, device)
+        else:
+            img = x_T.to(device=device, dtype=torch.float32)
         steps = self.ddim_timesteps
         if timesteps is not None:
             end = int(min(timesteps / steps.shape[0], 1) * steps.shape[0]) - 1

@@ -18,7 +18,12 @@ class DiagonalGaussianDistribution(object):
         if deterministic:
             self.var = self.std = torch.zeros_like(self.mean)
 
-    def sample(self):
+    def sample(self, noise=None):
+        """noise: a ready standard-normal tensor shaped like the mean (leftrefill_amd.noise: the POSTERIOR stream) -- used as it is,
+        and no generator is re-seeded or drawn from; None: the reference's draw."""
+        if noise is not None:
+            assert noise.shape == self.mean.shape, "noise: shaped like the posterior mean"
+            return self.mean + self.std * noise.to(device=self.parameters.device)
         torch.manual_seed(42)
         if torch.cuda.is_available():
             torch.cuda.manual_seed_all(42)

@@ -989,6 +989,25 @@ def ddim_q_sample(x0, noise, sa, s1ma):
     return out
 
 
+def seeded_normal(keys, stream, step, out):
+    """Fill out [B, ...] (fp32, cuda, contiguous as [B][per_sample]; its base may sit at any 4-byte offset) with the seeded normals of
+    the B keys (lr_seeded_normal, one launch; leftrefill_amd/noise.py states the values).  keys: int64 [B, 2] on out's device -- the
+    uint64 seed bits and the sub-sample number of every row; stream, step: uint32 names of the draw.  Returns out.  Draws nothing from
+    torch's generators."""
+    lib = _lib.load()
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() >= 1, "out: contiguous cuda fp32 [B, ...]"
+    B = out.shape[0]
+    assert keys.dtype == torch.int64 and keys.device == out.device and keys.is_contiguous() and tuple(keys.shape) == (B, 2), \
+        "keys: contiguous int64 [B, 2] on out's device"
+    stream, step = int(stream), int(step)
+    assert 0 <= stream < 2 ** 32 and 0 <= step < 2 ** 32, "stream, step: uint32"
+    per = out.numel() // B if B else 0
+    with torch.cuda.device(out.device):
+        _lib.check(lib.lr_seeded_normal(_p(keys), B, per, ctypes.c_int32(stream).value, ctypes.c_int32(step).value, _p(out), _stream()),
+                   "seeded_normal")
+    return out
+
+
 EVAL_TILE_H, EVAL_TILE_W, EVAL_SLOT_FLOATS = 32, 64, 8      # LR_EVAL_TILE_H / _W / LR_EVAL_SLOT_FLOATS
 EVAL_PRED_KIND = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}      # LR_EVAL_PRED_*
 

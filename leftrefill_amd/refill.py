@@ -298,15 +298,25 @@ def _rgb(img):
     return np.asarray(img.convert("RGB"))
 
 
-def sample_latents(model, image, masked_image, mask, txt, steps, scale, seeds, num_samples, sampler=None, attn=None):
+def sample_latents(model, image, masked_image, mask, txt, steps, scale, seeds, num_samples, sampler=None, attn=None, noise="torch"):
     """The reference's `inpaint` 88-130 on a prepared batch (NCHW fp32 device tensors of P * num_samples canvases): conditioning, the
     seeded start code, DDIM at eta 1 with classifier-free guidance, the VAE decode.  -> the decoded prediction [N,3,H,2W].
-    attn: a dict to fill with the reference-attention maps of the sampling (`refill(return_attn=True)`), or None."""
+    attn: a dict to fill with the reference-attention maps of the sampling (`refill(return_attn=True)`), or None.
+    noise: "torch" -- the start code from numpy.random.RandomState(seed), everything else from torch's global generators, as in the
+    reference; "seeded" -- sample j of the pair with seed s has the key (s, j) of leftrefill_amd/noise.py, and the posterior sample
+    of the masked-image encoding, the start code and the noise of every step are that key's draws (lr_seeded_normal)."""
     import torch
     import torch.nn.functional as F
     from ldm.models.diffusion.ddim import DDIMSampler
     N, _, H, W2 = image.shape
     h, w = H // 8, W2 // 8
+    if noise not in ("torch", "seeded"):
+        raise ValueError(f"noise: 'torch' or 'seeded', not {noise!r}")
+    sn = None
+    if noise == "seeded":
+        from .noise import POSTERIOR, SeededNoise
+        sn = SeededNoise([s for s in seeds for _ in range(num_samples)], subs=list(range(num_samples)) * len(seeds), device=image.device)
+        assert len(sn) == N
     batch = {"image": image, "masked_image": masked_image, "mask": mask}
     c = model.cond_stage_model.encode([txt] * N)
     c_cat = []
@@ -315,13 +325,19 @@ def sample_latents(model, image, masked_image, mask, txt, steps, scale, seeds, n
         if ck != model.masked_image_key:
             cc = F.interpolate(cc, size=(h, w))
         else:
-            cc = model.get_first_stage_encoding(model.encode_first_stage(cc))
+            posterior = model.encode_first_stage(cc)
+            if sn is not None and hasattr(posterior, "mean"):
+                cc = model.get_first_stage_encoding(posterior, noise=sn.normal(POSTERIOR, 0, posterior.mean.shape[1:]))
+            else:
+                cc = model.get_first_stage_encoding(posterior)
         c_cat.append(cc)
     c_cat = torch.cat(c_cat, dim=1)
     cond = {"c_concat": [c_cat], "c_crossattn": [c]}
     uc_full = {"c_concat": [c_cat], "c_crossattn": [model.get_unconditional_conditioning(N)]}
-    start = np.concatenate([np.random.RandomState(s).randn(num_samples, 4, h, w) for s in seeds], axis=0)
-    start = torch.from_numpy(start).to(device=image.device, dtype=torch.float32)
+    start = None
+    if sn is None:
+        start = np.concatenate([np.random.RandomState(s).randn(num_samples, 4, h, w) for s in seeds], axis=0)
+        start = torch.from_numpy(start).to(device=image.device, dtype=torch.float32)
     sampler = DDIMSampler(model) if sampler is None else sampler
     import contextlib
     probe = contextlib.nullcontext()
@@ -330,7 +346,7 @@ def sample_latents(model, image, masked_image, mask, txt, steps, scale, seeds, n
         probe = AttentionProbe(model.model.diffusion_model)
     with probe:
         samples, _ = sampler.sample(steps, N, [model.channels, h, w], cond, verbose=False, eta=1.0, unconditional_guidance_scale=scale,
-                                    unconditional_conditioning=uc_full, x_T=start)
+                                    unconditional_conditioning=uc_full, x_T=start, seeds=sn)
     if attn is not None:
         # the conditional half of the guided [uncond; cond] batch (all of it at scale 1): the maps of the pass that saw the prompt
         rows = slice(N, 2 * N) if float(scale) != 1. else slice(0, N)
@@ -340,16 +356,21 @@ def sample_latents(model, image, masked_image, mask, txt, steps, scale, seeds, n
 
 
 def refill(model, source, mask, reference, steps=50, scale=2.5, seed=0, num_samples=1, size=512, device_prep=True, sampler=None,
-           return_attn=False):
+           return_attn=False, noise="torch"):
     """Fill the masked part of `source` guided by `reference`: `predict` of the reference's ref_inpainting_gradio.py.
 
     source, mask, reference: PIL images or uint8 arrays (`.convert("RGB")` is host work on both routes), or lists of equal length: a
     batch of P pairs sampled together at UNet batch 2 * P * num_samples; `seed` is then an int or one int per pair.  Returns the list
     of `num_samples` PIL images of size `(int(size / ratio), size)` -- for lists, one such list per pair.
 
-    Randomness: the start code of a pair is `numpy.random.RandomState(seed).randn(num_samples, 4, H / 8, 2W / 8)`, as in the reference.
-    Everything else that draws random numbers -- the sample of the VAE posterior, the eta = 1 noise of every DDIM step -- uses torch's
-    global generators, as in the reference: call `torch.manual_seed` first for a reproducible result.
+    Randomness, noise="torch" (the default, the reference's behaviour): the start code of a pair is
+    `numpy.random.RandomState(seed).randn(num_samples, 4, H / 8, 2W / 8)`; the sample of the VAE posterior and the eta = 1 noise of every
+    DDIM step come from torch's global generators.
+    noise="seeded": sample j of a pair with seed s has the key (s, j) of leftrefill_amd/noise.py, and the start code, the noise of every
+    step and the posterior sample of the masked-image encoding are that key's draws (one lr_seeded_normal launch each).  The result
+    then depends only on the inputs and the seed -- not on torch's or numpy's generators, on what ran before, on the pair's place in
+    the batch or on the pairs beside it -- up to the UNet's batch-dependent kernel plans: a pair sampled alone and in a batch gets
+    bit-identical noise, but its latents may differ in the last fp16 bits where a GEMM's plan depends on the batch size.
 
     device_prep=True: resizes, canvas, composite and 8-bit tail are HIP kernels (lr_pil_resize, lr_refill_canvas, lr_eval_metrics);
     an image whose resize the library refuses is resized on the host and uploaded.  device_prep=False: `prepare_numpy` / `finish_numpy`
@@ -387,7 +408,7 @@ def refill(model, source, mask, reference, steps=50, scale=2.5, seed=0, num_samp
             parts = [prepare_numpy(s, m, r, size, n, resize=resize_pil) for s, m, r in zip(sources, masks, references)]
             image, masked_image, mask_t = (torch.from_numpy(np.concatenate([p[k] for p in parts], axis=0)).to(device) for k in range(3))
         attn = {} if return_attn else None
-        pred = sample_latents(model, image, masked_image, mask_t, txt, steps, scale, seeds, n, sampler, attn=attn)
+        pred = sample_latents(model, image, masked_image, mask_t, txt, steps, scale, seeds, n, sampler, attn=attn, noise=noise)
         if device_prep:
             arrays = finish_device(pred, image, mask_t, out_whs)
         else:

@@ -9,7 +9,8 @@ The model is loaded the way tools/run_inpainting.py loads it: create_model(model
 --pretrained when the model saves its prompt only.  The mask is white where the source is to be filled.  Writes out_00.png ...
 out_{num_samples - 1}.png of size (int(size / ratio), size) into --out.  The resizes, the canvas and the 8-bit tail run as HIP kernels;
 --host_prep runs them on the host with Pillow and numpy instead and writes the same bytes.  The seed fixes the start code and
-torch's generators (the VAE posterior sample and the eta = 1 noise draw from those).
+torch's generators (the VAE posterior sample and the eta = 1 noise draw from those).  --seeded_noise: every draw of sample j comes
+from the key (seed, j) of leftrefill_amd/noise.py instead (`refill(noise="seeded")`): the result depends on the inputs and the seed alone.
 --attn_maps DIR: also writes, per output image XX and self-attention layer YY of the UNet, attn_XX_lYY.png (viridis over [0, 1] of how
 much each target token attends to the reference, nearest-resized to the result's size) and corr_XX_lYY.npy ([h, w / 2, 2] float32: the
 reference-half token (x, y) each target token looks at; leftrefill_amd.attnprobe).
@@ -55,6 +56,7 @@ def main():
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--host_prep", action="store_true", help="image work on the host with Pillow and numpy (the yardstick route)")
     ap.add_argument("--pretrained", type=str, default="pretrained_models/512-inpainting-ema.ckpt")
+    ap.add_argument("--seeded_noise", action="store_true", help="per-sample seeded noise for every draw (refill(noise='seeded'))")
     ap.add_argument("--attn_maps", type=str, default=None, help="directory for the reference-attention maps (attn_XX_lYY.png, corr_XX_lYY.npy)")
     a = ap.parse_args()
 
@@ -75,7 +77,8 @@ def main():
     model = model.to("cuda").eval()
     torch.manual_seed(a.seed)
     images = refill(model, Image.open(a.source), Image.open(a.mask), Image.open(a.reference), steps=a.steps, scale=a.scale, seed=a.seed,
-                    num_samples=a.num_samples, size=a.size, device_prep=not a.host_prep, return_attn=a.attn_maps is not None)
+                    num_samples=a.num_samples, size=a.size, device_prep=not a.host_prep, return_attn=a.attn_maps is not None,
+                    noise="seeded" if a.seeded_noise else "torch")
     if a.attn_maps is not None:
         images, attn = images
         write_attn_maps(a.attn_maps, images, attn, a.size)

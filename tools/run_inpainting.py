@@ -43,6 +43,11 @@ and the metric file -- the Frechet Inception Distance between the composited pre
 reference writes to disk "for fid metric" (`leftrefill_amd.fid`, parity-unpinned).  --device_fid routes the network and the float64
 statistics through the HIP kernels of csrc/inception.hip (`fid.DeviceFID`); without it `fid.HostFID` runs the eager network in fp32.
 Without --fid_weights nothing changes.
+
+--seeded_noise [--seed N]: every random draw of an item -- the posterior sample of its masked-image encoding, its start code, the noise
+of every sampler step -- comes from the item's own key (N, dataset index of the item) of leftrefill_amd/noise.py (under --multiview one
+key per canvas: sub = index * views + view) instead of torch's global generators, so the images and the printed metrics do not depend
+on --batch_size or on what ran before, up to the UNet's batch-dependent kernel plans.  Without it nothing changes.
 """
 import argparse
 import glob
@@ -145,6 +150,8 @@ def main():
     ap.add_argument("--device_lpips", action="store_true", help="LPIPS from the HIP kernels (needs --device_metrics and --lpips_weights)")
     ap.add_argument("--fid_weights", type=str, default=None, help="state-dict file of the FID Inception network: adds the FID line")
     ap.add_argument("--device_fid", action="store_true", help="FID features and statistics from the HIP kernels (needs --fid_weights)")
+    ap.add_argument("--seeded_noise", action="store_true", help="per-item seeded noise: results do not depend on --batch_size")
+    ap.add_argument("--seed", type=int, default=0, help="the seed of --seeded_noise; an item's key is (seed, its dataset index)")
     a = ap.parse_args()
     if a.device_fid and not a.fid_weights:
         raise SystemExit("--device_fid requires --fid_weights")
@@ -193,11 +200,20 @@ def main():
                 fid_fn.update(out, mask)
 
     psnrs, ssims, lpipss = [], [], []
+    items_seen = 0
     with torch.no_grad(), torch.autocast("cuda"):
         for bi, batch in enumerate(batches):
             batch = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in batch.items()}
+            seeded = {}
+            if a.seeded_noise:      # one key per canvas, named by the item's place in the dataset (the loaders do not shuffle)
+                from leftrefill_amd.noise import SeededNoise
+                img = batch["image"]
+                per_item = img.shape[1] if img.dim() == 5 else 1
+                subs = [(items_seen + j) * per_item + v_ for j in range(img.shape[0]) for v_ in range(per_item)]
+                seeded = {"seeds": SeededNoise([a.seed] * len(subs), subs=subs, device=img.device)}
+                items_seen += img.shape[0]
             out = model.log_images(batch, batch["image"].shape[0], unconditional_guidance_scale=a.cfg, ddim_eta=a.eta,
-                                       ddim_steps=a.steps, **({} if a.sampler == "ddim" else {"sampler": a.sampler}))
+                                       ddim_steps=a.steps, **({} if a.sampler == "ddim" else {"sampler": a.sampler}), **seeded)
             if a.device_metrics:
                 if a.multiview:
                     m, global_view_num = evalglue.device_metrics_multiview(out, batch["mask"], a.batch_size, global_view_num, a.test_size,
